@@ -18,6 +18,15 @@ and gradient accumulation.
 
     python bench.py                                  # 1 GPU
     torchrun --nproc-per-node 8 bench.py --gpus 8    # PP = 8
+
+A plain run sets up, warms up, times ``--steps`` steps and prints the result
+line.  ``--full`` adds what the headline figure does not need: the clock /
+power telemetry of the timed region and the extra instrumented step behind
+``bubble_pct`` / ``stage_busy_ms`` (both null in a plain run).
+``--dump-outputs DIR`` writes what the last timed step computed (the
+micro-batch losses, and fixed seeded samples of the updated fp32 master
+weights and of the gradients) as ``DIR/<name>.npy``: the inputs are the same
+from run to run, so two builds can be compared output for output.
 """
 from __future__ import annotations
 
@@ -75,7 +84,14 @@ def parse():
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp32"])
     ap.add_argument("--lr", type=float, default=1e-4)
     ap.add_argument("--clip", type=float, default=0.5)
-    ap.add_argument("--no-bubble", action="store_true", help="skip the extra instrumented step")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: GPU clock / power telemetry over the "
+                         "timed steps, and one extra instrumented step for bubble_pct / stage_busy_ms")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32): the "
+                         "micro-batch losses, and fixed seeded samples of the updated master weights and of the "
+                         "gradients (at most 64 MB over all ranks)")
+    ap.add_argument("--no-bubble", action="store_true", help="--full: skip the extra instrumented step")
     ap.add_argument("--device", default="cuda", choices=["cuda", "cpu"],
                     help="cpu = gloo + fp32 plumbing check of the multi-rank path (tests only)")
     ap.add_argument("--plan", default="auto", choices=["auto", "analytic", "measured"],
@@ -372,7 +388,7 @@ def main() -> int:
     sync()
     startup["warmup_steps"] = time.perf_counter() - t_
     startup["total_before_timed_steps"] = time.perf_counter() - t_main
-    tele = _telemetry(device) if on_gpu else None
+    tele = _telemetry(device) if on_gpu and args.full else None
     t0 = time.perf_counter()
     for k in range(args.steps):
         mark(f"timed step {k}")
@@ -394,11 +410,13 @@ def main() -> int:
     loss_val = None
     if is_last and st.loss is not None:
         loss_val = float(st.loss.item())
+    if args.dump_outputs:
+        _dump_outputs(args.dump_outputs, opt, st.losses, rank, world)
 
-    # Bubble: one extra instrumented step, per-stage GPU busy time vs step time.
+    # Bubble (--full): one extra instrumented step, per-stage GPU busy time vs step time.
     bubble = None
     stage_busy = None
-    if not args.no_bubble and on_gpu:
+    if args.full and not args.no_bubble and on_gpu:
         mark("instrumented step")
         engine.measure = True
         sync()
@@ -511,6 +529,39 @@ def main() -> int:
         dist.barrier()
         dist.destroy_process_group()
     return 0
+
+
+DUMP_BUDGET_BYTES = 48 * 2**20  # --dump-outputs: all sampled arrays of all ranks together (the limit is 64 MB)
+DUMP_SEED = 20240607
+
+
+def _dump_outputs(path, opt, losses, rank: int, world: int) -> None:
+    """``--dump-outputs``: what the last timed step left its caller, as float32
+    ``.npy`` files -- ``losses`` (one per micro-batch; the rank that owns the
+    loss), ``params`` (the fp32 master weights after the optimizer step) and
+    ``grads`` (the fp32 gradients the step accumulated), one pair per device
+    group of the optimizer.  Flat buffers larger than their share of the
+    budget are sampled at fixed seeded indices (sorted; the same for every run
+    of the same arguments).  Ranks of a multi-rank run add ``_rank<r>``."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    suffix = f"_rank{rank}" if world > 1 else ""
+    opt.wait_step()  # an overlapped optimizer step finishes on its side stream
+    arrays = {}
+    if losses:
+        arrays["losses"] = torch.stack([l.detach().reshape(()) for l in losses]).float()
+    per_array = DUMP_BUDGET_BYTES // 4 // (2 * len(opt.groups) * max(world, 1))
+    for gi, g in enumerate(opt.groups):
+        tag = f"_group{gi}" if len(opt.groups) > 1 else ""
+        for name, flat in (("params", g.master), ("grads", g.main_grad)):
+            if flat.numel() > per_array:
+                gen = torch.Generator(device="cpu").manual_seed(DUMP_SEED)
+                idx = torch.randint(0, flat.numel(), (per_array,), generator=gen).sort().values
+                flat = flat.index_select(0, idx.to(flat.device))
+            arrays[name + tag] = flat.detach().float()
+    for name, t in arrays.items():
+        np.save(os.path.join(path, name + suffix + ".npy"), t.cpu().numpy())
 
 
 def _telemetry(device):
@@ -657,6 +708,8 @@ def run_pipe(args) -> int:
         loss = train_step()
     sync()
     ms = (time.perf_counter() - t0) / max(args.steps, 1) * 1e3
+    if args.dump_outputs:
+        _dump_outputs(args.dump_outputs, opt, [loss], 0, 1)
     value = m * mb * S / (ms / 1e3)
     ref_match = matches_reference(cfg, args, m, mb)
     peaks = [torch.cuda.max_memory_allocated(d) / 2**30 for d in devices_used] if on_gpu else None

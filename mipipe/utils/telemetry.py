@@ -1,6 +1,6 @@
 """GPU clock / power / temperature telemetry around a timed region (amdsmi).
 
-The bench brackets its timed steps with :class:`GpuTelemetry` so every JSON
+``bench.py --full`` brackets its timed steps with :class:`GpuTelemetry` so its JSON
 line says what the chip was doing while it was measured: the graphics clock
 it held (per-XCD ``current_gfxclks``, sampled), socket power, hotspot and HBM
 temperature, and how much of the region the firmware spent power-limited

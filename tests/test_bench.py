@@ -133,6 +133,64 @@ def test_bench_pipe_impl_cpu():
     assert rec["n_gpus"] == 2 and rec["config"]["chunks"] == 8 and rec["value"] > 0
 
 
+def test_bench_dump_outputs_repeatable_and_full_cpu(tmp_path):
+    """--dump-outputs writes the last timed step's losses, updated master weights and gradients as float32
+    .npy files; the inputs are the same from run to run, so a second run (here with --full, which adds
+    measurements but must not change what the steps compute) reproduces them; --steps sets the timed steps."""
+    import numpy as np
+
+    base = ["--gpus", "1", "--warmup", "1", "--device", "cpu", "--config", "tiny", "--micro-batch", "2"]
+    dumps = {}
+    for name, extra in (("a", ["--steps", "1"]), ("b", ["--steps", "1", "--full"]), ("c", ["--steps", "2"])):
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + base + extra
+                             + ["--dump-outputs", str(tmp_path / name)], capture_output=True, text=True,
+                             timeout=600, cwd="/tmp", env={**os.environ, "CUDA_VISIBLE_DEVICES": ""})
+        assert out.returncode == 0, out.stderr[-3000:]
+        (rec,) = _json_lines(out.stdout)
+        assert REQUIRED <= set(rec) and rec["steps"] == int(extra[1]) and rec["ms_per_step"] > 0
+        # the measurements behind --full are absent from a plain run's line (and from every CPU run's)
+        assert rec["telemetry"] is None and rec["bubble_pct"] is None and rec["stage_busy_ms"] is None
+        dumps[name] = {f[:-4]: np.load(tmp_path / name / f) for f in sorted(os.listdir(tmp_path / name))}
+    a, b, c = dumps["a"], dumps["b"], dumps["c"]
+    assert set(a) == set(b) == set(c) == {"losses", "params", "grads"}
+    assert a["losses"].shape == (4,) and a["params"].shape == a["grads"].shape and a["params"].size > 0
+    total = 0
+    for k in a:
+        assert a[k].dtype == np.float32 and np.isfinite(a[k]).all()
+        np.testing.assert_allclose(a[k], b[k], rtol=1e-5, atol=1e-7)
+        total += a[k].nbytes
+    assert total <= 64 * 2**20
+    assert np.abs(a["grads"]).max() > 0
+    # one more timed step is one more optimizer step: the weights moved on
+    assert np.abs(a["params"] - c["params"]).max() > 0
+
+
+def test_dump_outputs_samples_large_buffers(tmp_path):
+    """Flat buffers beyond the budget are sampled at fixed seeded indices: the same elements every time,
+    and all ranks together stay under 64 MB."""
+    import importlib.util
+    import types
+
+    import numpy as np
+    import torch
+
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    n, world = 5_000_000, 8
+    master = torch.arange(n, dtype=torch.float32)
+    group = types.SimpleNamespace(master=master, main_grad=-master)
+    opt = types.SimpleNamespace(groups=[group], wait_step=lambda: None)
+    for d in ("x", "y"):
+        bench._dump_outputs(str(tmp_path / d), opt, [torch.tensor(1.5), torch.tensor(2.5)], 3, world)
+    assert sorted(os.listdir(tmp_path / "x")) == ["grads_rank3.npy", "losses_rank3.npy", "params_rank3.npy"]
+    p, g = np.load(tmp_path / "x" / "params_rank3.npy"), np.load(tmp_path / "x" / "grads_rank3.npy")
+    assert p.dtype == np.float32 and 0 < p.size < n and (p.nbytes + g.nbytes) * world <= 64 * 2**20
+    assert (np.diff(p) >= 0).all() and np.array_equal(g, -p)  # sorted indices, the same ones for both buffers
+    assert np.array_equal(p, np.load(tmp_path / "y" / "params_rank3.npy"))
+    assert np.load(tmp_path / "x" / "losses_rank3.npy").tolist() == [1.5, 2.5]
+
+
 def test_vs_baseline_only_on_reference_config():
     import argparse
     import importlib.util

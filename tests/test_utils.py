@@ -83,7 +83,7 @@ def test_example_driver_runs_on_cpu(tmp_path):
 
 
 def test_gpu_telemetry_degrades_without_a_gpu():
-    """bench.py brackets its timed steps with GpuTelemetry; with no driver (or no
+    """bench.py --full brackets its timed steps with GpuTelemetry; with no driver (or no
     amdsmi) it must report itself unavailable instead of raising."""
     from mipipe.utils.telemetry import GpuTelemetry
 

@@ -66,7 +66,8 @@ def run_one(k: int, bench_args: list[str], out_dir: str, timeout: float) -> dict
 def main() -> int:
     ap = argparse.ArgumentParser()
     ap.add_argument("--ks", default="0,1,2,4,8,16,0")
-    ap.add_argument("--bench", default="--steps 20 --warmup 5", help="bench.py arguments")
+    ap.add_argument("--bench", default="--full --steps 20 --warmup 5",
+                    help="bench.py arguments (--full: the JSON telemetry printed per run)")
     ap.add_argument("--label", default="enc12 PP=1")
     ap.add_argument("--timeout", type=float, default=400.0)
     ap.add_argument("--out-dir", default=os.path.join(ROOT, "gpurun_out"))

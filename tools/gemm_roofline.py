@@ -1,13 +1,13 @@
 """Per-GEMM-class roofline of the enc12 PP=1 training step from a rocprofv3 kernel trace.
 
-    rocprofv3 --kernel-trace -d gpurun_out/prof -o run -- python3 bench.py --steps 4 --warmup 2 --no-bubble
-    python tools/gemm_roofline.py gpurun_out/prof/run_results.db --steps 6 --gfxclk 1930
+    rocprofv3 --kernel-trace -d prof -o run -- python3 bench.py --steps 4 --warmup 2
+    python tools/gemm_roofline.py prof/run_results.db --steps 6 --gfxclk 1930
 
 The bench's default shapes (enc12_d4096, micro-batch 128 x 128 = 16,384 tokens, chunks 4, 'never'): every GEMM
 class is identified by its kernel instantiation and grid (tiles = grid_x / 512 threads), its FLOPs follow from
 the model, and the dgrads -- one instantiation and grid for K = 4096 / 12,288 / 28,782 -- are told apart by
 duration (about 1x / 3x / 7x the K = 4096 median).  The roofline is the dense bf16 MFMA peak at the given
-gfxclk: 2.5 PF/s x gfxclk / 2400 MHz (the step's mean clock from the bench JSON telemetry; the GEMM phases
+gfxclk: 2.5 PF/s x gfxclk / 2400 MHz (the step's mean clock from the telemetry in the JSON of `bench.py --full`; the GEMM phases
 themselves sit at the 1400 W cap, ~1.8 GHz, profiles/gemm_clock_r5.txt).
 """
 from __future__ import annotations
@@ -57,7 +57,7 @@ def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("db")
     ap.add_argument("--steps", type=int, required=True, help="steps in the trace (warm-up included)")
-    ap.add_argument("--gfxclk", type=float, required=True, help="MHz, the step's mean (bench JSON telemetry)")
+    ap.add_argument("--gfxclk", type=float, required=True, help="MHz, the step's mean (bench.py --full: JSON telemetry)")
     ap.add_argument("--tokens", type=int, default=16384, help="tokens per micro-batch (micro-batch x 128)")
     args = ap.parse_args()
     global T, TSTEP
