@@ -17,8 +17,11 @@ namespace {
 
 constexpr int kT = 256;
 
-// Online (max, sum-of-exp) update with one value.
+// Online (max, sum-of-exp) update with one value.  A -inf value (a masked
+// logit) adds nothing; pushed while the running max is still -inf it would
+// evaluate exp(-inf - (-inf)) = NaN.
 __device__ __forceinline__ void lse_push(float& m, float& s, float v) {
+  if (v == -INFINITY) return;
   if (v > m) {
     s = s * __expf(m - v) + 1.f;
     m = v;
@@ -50,6 +53,7 @@ __device__ __forceinline__ float block_row_lse(const T* __restrict__ x, int64_t 
       float cm = a[0];
 #pragma unroll
       for (int i = 1; i < 8; ++i) cm = fmaxf(cm, a[i]);
+      if (cm == -INFINITY) continue;  // an all -inf chunk adds nothing (and exp(-inf - m) is NaN while m is -inf)
       if (cm > m) {
         s *= __expf(m - cm);
         m = cm;

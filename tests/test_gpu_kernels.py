@@ -186,8 +186,11 @@ def test_embedding(k):
 @pytest.mark.parametrize("variant", [0, 1, 2])
 def test_flat_adam_matches_torch(k, variant):
     """Every Adam kernel (grid-stride, one-shot tiles, tiles with streaming
-    stores -- the default; the flat group spans several tiles and ends in a
-    scalar tail) against torch.optim.Adam."""
+    stores -- the default) against torch.optim.Adam with L2 decay and a binding
+    clip.  The flat group has 7,399 elements: two 4096-element tiles and a
+    scalar tail, but in the grid-stride kernel one vector per thread at most --
+    its unrolled U = 2 loop needs more than 4,194,304 elements and runs in
+    test_gpu_rowwise_edges.py::test_adam_step_large_flat_buffer."""
     from mipipe.optim import FlatAdam
 
     k.adam_set_variant(variant)
