@@ -215,6 +215,185 @@ void dispatch_fb(const Tensor& t, const char* what, F&& f) {
   }
 }
 
+// ------------------------------------------------------------------ RMSNorm
+std::tuple<Tensor, std::optional<Tensor>, Tensor, int64_t, int64_t> py_rmsnorm_fwd(
+    Tensor x, std::optional<Tensor> res, Tensor gamma, double eps, double p, bool save_z) {
+  check_cuda(x, "x");
+  check_cuda(gamma, "gamma");
+  MP_CHECK(x.dim() >= 1, "rmsnorm: x needs a hidden dimension");
+  const int64_t cols = x.size(-1);
+  MP_CHECK(cols > 0 && cols % 8 == 0, "rmsnorm: hidden size must be a positive multiple of 8, got ", cols);
+  MP_CHECK(rms_max_vec((int)std::min<int64_t>(cols, 1 << 20)) > 0, "rmsnorm: hidden size too large: ", cols);
+  const int64_t rows = x.numel() / cols;
+  MP_CHECK(rows <= INT32_MAX, "rmsnorm: too many rows");
+  MP_CHECK(gamma.numel() == cols, "rmsnorm: gamma size mismatch");
+  check_same(x, gamma, "x", "gamma");
+  if (res.has_value()) {
+    check_cuda(*res, "residual");
+    check_same(x, *res, "x", "residual");
+    MP_CHECK(res->numel() == x.numel(), "rmsnorm: residual shape mismatch");
+  }
+  MP_CHECK(p >= 0.0 && p < 1.0, "dropout p must be in [0, 1)");
+  at::hip::HIPGuardMasqueradingAsCUDA guard(x.device());
+  auto y = at::empty_like(x);
+  std::optional<Tensor> z;
+  if (save_z) z = at::empty_like(x);
+  auto rstd = at::empty({rows}, x.options().dtype(at::kFloat));
+  uint64_t seed = 0, offset = 0;
+  if (p > 0.0) std::tie(seed, offset) = philox_draw(x.device(), 4);
+  auto s = cur_stream(x);
+  if (rows == 0) return {y, z, rstd, (int64_t)seed, (int64_t)offset};
+  dispatch_fb(x, "rmsnorm_fwd", [&](auto* tag) {
+    using T = std::remove_pointer_t<decltype(tag)>;
+    RmsArgs<T> a;
+    a.x = cptr<T>(x); a.res = optr<T>(res); a.gamma = cptr<T>(gamma);
+    a.y = ptr<T>(y); a.z = z ? ptr<T>(*z) : nullptr; a.rstd = ptr<float>(rstd);
+    a.rows = (int)rows; a.cols = (int)cols; a.eps = (float)eps; a.p = (float)p; a.seed = seed; a.offset = offset;
+    rmsnorm_fwd<T>(a, s);
+  });
+  return {y, z, rstd, (int64_t)seed, (int64_t)offset};
+}
+
+// With acc_gamma (a fp32 main_grad view) dgamma is accumulated there and None is returned for it.
+std::tuple<Tensor, std::optional<Tensor>, std::optional<Tensor>> py_rmsnorm_bwd(
+    Tensor dy, Tensor z, Tensor rstd, Tensor gamma, double p, int64_t seed, int64_t offset,
+    std::optional<Tensor> acc_gamma, std::optional<Tensor> addend) {
+  check_cuda(dy, "dy");
+  check_cuda(z, "z");
+  check_cuda(gamma, "gamma");
+  check_cuda(rstd, "rstd");
+  check_same(dy, z, "dy", "z");
+  check_same(dy, gamma, "dy", "gamma");
+  MP_CHECK(dy.dim() >= 1, "rmsnorm_bwd: dy needs a hidden dimension");
+  const int64_t cols = dy.size(-1);
+  MP_CHECK(cols > 0 && cols % 8 == 0 && rms_max_vec((int)std::min<int64_t>(cols, 1 << 20)) > 0,
+           "rmsnorm_bwd: bad hidden size ", cols);
+  const int64_t rows = dy.numel() / cols;
+  MP_CHECK(rows <= INT32_MAX, "rmsnorm_bwd: too many rows");
+  MP_CHECK(z.numel() == dy.numel(), "rmsnorm_bwd: shape mismatch");
+  MP_CHECK(gamma.numel() == cols, "rmsnorm_bwd: gamma size mismatch");
+  MP_CHECK(rstd.numel() == rows && rstd.scalar_type() == at::kFloat && rstd.device() == dy.device(),
+           "rmsnorm_bwd: rstd must be fp32 [rows] on dy's device");
+  MP_CHECK(p >= 0.0 && p < 1.0, "dropout p must be in [0, 1)");
+  if (addend) {
+    check_same(dy, *addend, "dy", "addend");
+    MP_CHECK(addend->numel() == dy.numel() && addend->is_contiguous(), "rmsnorm_bwd: addend must match dy");
+  }
+  const bool acc = acc_gamma.has_value();
+  if (acc) {
+    MP_CHECK(acc_gamma->is_cuda() && acc_gamma->device() == dy.device() && acc_gamma->is_contiguous() &&
+                 acc_gamma->scalar_type() == at::kFloat && acc_gamma->numel() == cols,
+             "rmsnorm_bwd: the accumulation target must be contiguous fp32 [cols] on dy's device");
+  }
+  at::hip::HIPGuardMasqueradingAsCUDA guard(dy.device());
+  auto dz = at::empty_like(dy);
+  std::optional<Tensor> dx;
+  if (p > 0.0) dx = at::empty_like(dy);
+  Tensor dgamma = acc ? *acc_gamma : at::empty_like(gamma);
+  std::optional<Tensor> rg;
+  if (!acc) rg = dgamma;
+  if (rows == 0) {
+    if (!acc) dgamma.zero_();
+    return {dz, dx, rg};
+  }
+  const int nparts = std::max(1, rms_bwd_parts((int)rows, (int)cols));
+  auto part = at::empty({nparts, cols}, dy.options().dtype(at::kFloat));
+  auto s = cur_stream(dy);
+  dispatch_fb(dy, "rmsnorm_bwd", [&](auto* tag) {
+    using T = std::remove_pointer_t<decltype(tag)>;
+    RmsBwdArgs<T> a;
+    a.dy = cptr<T>(dy); a.z = cptr<T>(z); a.rstd = cptr<float>(rstd); a.gamma = cptr<T>(gamma);
+    a.dz = ptr<T>(dz); a.dx = dx ? ptr<T>(*dx) : nullptr; a.addend = addend ? cptr<T>(*addend) : nullptr;
+    a.dgamma_part = ptr<float>(part); a.dgamma = dgamma.data_ptr();
+    a.out_f32 = dgamma.scalar_type() == at::kFloat; a.accumulate = acc;
+    a.rows = (int)rows; a.cols = (int)cols; a.nparts = nparts; a.p = (float)p;
+    a.seed = (uint64_t)seed; a.offset = (uint64_t)offset;
+    rmsnorm_bwd<T>(a, s);
+  });
+  return {dz, dx, rg};
+}
+
+// ------------------------------------------------------------------ SwiGLU / RoPE
+Tensor py_swiglu_fwd(Tensor gu) {
+  check_cuda(gu, "gu");
+  MP_CHECK(gu.dim() >= 1, "swiglu: gu needs a feature dimension");
+  const int64_t two_f = gu.size(-1);
+  MP_CHECK(two_f > 0 && two_f % 16 == 0, "swiglu: the last dim is 2F with F a multiple of 8, got ", two_f);
+  MP_CHECK(two_f / 2 <= INT32_MAX / 4, "swiglu: F too large");
+  const int64_t F = two_f / 2, rows = gu.numel() / two_f;
+  at::hip::HIPGuardMasqueradingAsCUDA guard(gu.device());
+  auto shape = gu.sizes().vec();
+  shape.back() = F;
+  auto h = at::empty(shape, gu.options());
+  auto s = cur_stream(gu);
+  dispatch_fb(gu, "swiglu_fwd", [&](auto* tag) {
+    using T = std::remove_pointer_t<decltype(tag)>;
+    swiglu_fwd<T>(cptr<T>(gu), ptr<T>(h), rows, (int)F, s);
+  });
+  return h;
+}
+
+Tensor py_swiglu_bwd(Tensor dh, Tensor gu) {
+  check_cuda(dh, "dh");
+  check_cuda(gu, "gu");
+  check_same(dh, gu, "dh", "gu");
+  MP_CHECK(gu.dim() >= 1 && dh.dim() >= 1, "swiglu_bwd: tensors need a feature dimension");
+  const int64_t two_f = gu.size(-1);
+  MP_CHECK(two_f > 0 && two_f % 16 == 0, "swiglu_bwd: the last dim of gu is 2F with F a multiple of 8, got ", two_f);
+  MP_CHECK(two_f / 2 <= INT32_MAX / 4, "swiglu_bwd: F too large");
+  const int64_t F = two_f / 2, rows = gu.numel() / two_f;
+  MP_CHECK(dh.size(-1) == F && dh.numel() == rows * F, "swiglu_bwd: dh must be [rows, F]");
+  at::hip::HIPGuardMasqueradingAsCUDA guard(gu.device());
+  auto dgu = at::empty_like(gu);
+  auto s = cur_stream(gu);
+  dispatch_fb(gu, "swiglu_bwd", [&](auto* tag) {
+    using T = std::remove_pointer_t<decltype(tag)>;
+    swiglu_bwd<T>(cptr<T>(dh), cptr<T>(gu), ptr<T>(dgu), rows, (int)F, s);
+  });
+  return dgu;
+}
+
+// out: None (a fresh tensor, V copied) or a tensor of qkv's layout; out being qkv itself rotates in place.
+Tensor py_rope_packed(Tensor qkv, Tensor cos, Tensor sin, std::optional<Tensor> out, int64_t pos0, bool inverse) {
+  check_cuda(qkv, "qkv");
+  check_cuda(cos, "cos");
+  check_cuda(sin, "sin");
+  MP_CHECK(qkv.dim() == 5 && qkv.size(2) == 3, "rope_packed: qkv must be [B, S, 3, H, D]");
+  const int64_t B = qkv.size(0), S = qkv.size(1), H = qkv.size(3), D = qkv.size(4);
+  MP_CHECK(D > 0 && D % 16 == 0, "rope_packed: head dim must be a multiple of 16, got ", D);
+  MP_CHECK(S <= INT32_MAX / 2 && H * D <= INT32_MAX / 8, "rope_packed: shape too large");
+  MP_CHECK(pos0 >= 0 && pos0 <= INT32_MAX / 2, "rope_packed: bad pos0 ", pos0);
+  for (auto* t : {&cos, &sin}) {
+    MP_CHECK(t->scalar_type() == at::kFloat && t->dim() == 2 && t->size(1) == D / 2 && t->size(0) >= pos0 + S &&
+                 t->device() == qkv.device(),
+             "rope_packed: cos / sin must be fp32 [>= pos0 + S, D / 2] on qkv's device");
+  }
+  at::hip::HIPGuardMasqueradingAsCUDA guard(qkv.device());
+  Tensor o;
+  if (out.has_value()) {
+    o = *out;
+    check_cuda(o, "out");
+    check_same(qkv, o, "qkv", "out");
+    MP_CHECK(o.sizes() == qkv.sizes(), "rope_packed: out must have qkv's shape");
+    // the same tensor or a disjoint one: a partial overlap would race
+    if (o.data_ptr() != qkv.data_ptr()) {
+      const char* a = static_cast<const char*>(qkv.data_ptr());
+      const char* b = static_cast<const char*>(o.data_ptr());
+      const int64_t n = (int64_t)qkv.nbytes();
+      MP_CHECK(b + n <= a || a + n <= b, "rope_packed: out partly overlaps qkv");
+    }
+  } else {
+    o = at::empty_like(qkv);
+  }
+  auto s = cur_stream(qkv);
+  dispatch_fb(qkv, "rope_packed", [&](auto* tag) {
+    using T = std::remove_pointer_t<decltype(tag)>;
+    rope_packed<T>(cptr<T>(qkv), cptr<float>(cos), cptr<float>(sin), ptr<T>(o), B, (int)S, (int)H, (int)D, (int)pos0,
+                   inverse, s);
+  });
+  return o;
+}
+
 std::tuple<Tensor, int64_t, int64_t> py_bias_act_fwd(Tensor x, std::optional<Tensor> bias, int64_t act, double p) {
   check_cuda(x, "x");
   const int64_t cols = x.size(-1);
@@ -1235,6 +1414,14 @@ PYBIND11_MODULE(_C, m) {
   m.def("layernorm_bwd", &py_layernorm_bwd, py::arg("dy"), py::arg("z"), py::arg("mean"), py::arg("rstd"),
         py::arg("gamma"), py::arg("p"), py::arg("seed"), py::arg("offset"), py::arg("acc_gamma") = py::none(),
         py::arg("acc_beta") = py::none(), py::arg("addend") = py::none());
+  m.def("rmsnorm_fwd", &py_rmsnorm_fwd, py::arg("x"), py::arg("res"), py::arg("gamma"), py::arg("eps"), py::arg("p"),
+        py::arg("save_z"));
+  m.def("rmsnorm_bwd", &py_rmsnorm_bwd, py::arg("dy"), py::arg("z"), py::arg("rstd"), py::arg("gamma"), py::arg("p"),
+        py::arg("seed"), py::arg("offset"), py::arg("acc_gamma") = py::none(), py::arg("addend") = py::none());
+  m.def("swiglu_fwd", &py_swiglu_fwd);
+  m.def("swiglu_bwd", &py_swiglu_bwd);
+  m.def("rope_packed", &py_rope_packed, py::arg("qkv"), py::arg("cos"), py::arg("sin"), py::arg("out") = py::none(),
+        py::arg("pos0") = 0, py::arg("inverse") = false);
   m.def("bias_act_fwd", &py_bias_act_fwd);
   m.def("bias_act_bwd", &py_bias_act_bwd, py::arg("dy"), py::arg("saved"), py::arg("bias"), py::arg("act"),
         py::arg("p"), py::arg("seed"), py::arg("offset"), py::arg("need_dbias"), py::arg("dbias_acc") = py::none());

@@ -59,6 +59,62 @@ int ln_bwd_parts(int rows, int cols);
 template <typename T> void layernorm_fwd(const LnArgs<T>& a, hipStream_t s);
 template <typename T> void layernorm_bwd(const LnBwdArgs<T>& a, hipStream_t s);
 
+// ------------------------------------------------------------------ RMSNorm
+// y = z * rsqrt(mean(z^2) + eps) * gamma with z = res + dropout(x): LnArgs
+// without mean and beta (rmsnorm.hip).
+template <typename T>
+struct RmsArgs {
+  const T* x = nullptr;      // branch input (dropout applies here)
+  const T* res = nullptr;    // residual input (optional)
+  const T* gamma = nullptr;
+  T* y = nullptr;
+  T* z = nullptr;            // optional: saved pre-norm sum for backward
+  float* rstd = nullptr;
+  int rows = 0, cols = 0;
+  float eps = 1e-5f;
+  float p = 0.f;
+  uint64_t seed = 0, offset = 0;
+};
+
+template <typename T>
+struct RmsBwdArgs {
+  const T* dy = nullptr;
+  const T* z = nullptr;
+  const float* rstd = nullptr;
+  const T* gamma = nullptr;
+  T* dz = nullptr;           // grad of z (= grad of the residual input)
+  const T* addend = nullptr; // optional extra gradient of z, added to dz (fan-out fusion)
+  T* dx = nullptr;           // grad of the dropout branch (nullptr if p == 0)
+  float* dgamma_part = nullptr;  // [nparts, cols] workspace
+  void* dgamma = nullptr;        // T (store) or fp32 (main_grad, may accumulate)
+  bool out_f32 = false;
+  bool accumulate = false;
+  int rows = 0, cols = 0, nparts = 0;
+  float p = 0.f;
+  uint64_t seed = 0, offset = 0;
+};
+
+// Vectors per thread of the one-row-per-group kernels (2, 4, 8), -1: width not supported
+// (cols % 8 != 0 or cols > 16384).
+int rms_max_vec(int cols);
+int rms_bwd_parts(int rows, int cols);
+template <typename T> void rmsnorm_fwd(const RmsArgs<T>& a, hipStream_t s);
+template <typename T> void rmsnorm_bwd(const RmsBwdArgs<T>& a, hipStream_t s);
+
+// ------------------------------------------------------------------ SwiGLU / RoPE (llama.hip)
+// gu [rows, 2F] = [gate | up] per row, F % 8 == 0: h [rows, F] = silu(gate) * up.
+template <typename T>
+void swiglu_fwd(const T* gu, T* h, int64_t rows, int F, hipStream_t s);
+// dgu [rows, 2F] = [dgate | dup] from dh [rows, F] and the forward's gu.
+template <typename T>
+void swiglu_bwd(const T* dh, const T* gu, T* dgu, int64_t rows, int F, hipStream_t s);
+// Rotates Q and K of qkv [B, S, 3, H, D] (contiguous, D % 16 == 0) at positions pos0 + s, pairs
+// (i, i + D/2); cos / sin: fp32 [>= pos0 + S, D/2].  out == qkv rotates in place (V untouched),
+// otherwise V is copied.  inverse negates sin (the backward, on dqkv).
+template <typename T>
+void rope_packed(const T* qkv, const float* cos_t, const float* sin_t, T* out, int64_t B, int S, int H, int D, int pos0,
+                 bool inverse, hipStream_t s);
+
 // ------------------------------------------------------------------ elementwise
 enum Activation : int { kActNone = 0, kActRelu = 1, kActGelu = 2 };
 // Backward-only activation code: the saved tensor IS act'(pre) (a GELU forward

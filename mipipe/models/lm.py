@@ -46,21 +46,31 @@ def sinusoidal_positions(max_len: int, d_model: int) -> Tensor:
 class Encoder(nn.Module):
     """Token embedding x sqrt(E) + positional encoding + dropout: ``[B, S] -> [B, S, E]``.
 
-    ``learned_positions=True`` gives GPT-2's learned position embedding instead
-    of the sinusoidal table.
+    ``positions`` picks the position signal added to the embedding:
+    ``"sinusoidal"`` (the reference's table), ``"learned"`` (GPT-2's learned
+    position embedding; ``learned_positions=True`` says the same) or ``"none"``
+    (rotary models: the positions enter in the attention blocks).
     """
 
     def __init__(self, ntoken: int, d_model: int, dropout: float = 0.5, max_len: int = 5000, *,
-                 learned_positions: bool = False, scale_embedding: bool = True, device=None, dtype=None) -> None:
+                 learned_positions: bool = False, scale_embedding: bool = True, positions: Optional[str] = None,
+                 device=None, dtype=None) -> None:
         super().__init__()
         fk = {"device": device, "dtype": dtype}
+        if positions is None:
+            positions = "learned" if learned_positions else "sinusoidal"
+        if positions not in ("sinusoidal", "learned", "none"):
+            raise ValueError(f"positions must be 'sinusoidal', 'learned' or 'none', got {positions!r}")
+        if learned_positions and positions != "learned":
+            raise ValueError(f"learned_positions=True contradicts positions={positions!r}")
         self.ntoken, self.d_model, self.dropout = ntoken, d_model, dropout
         self.scale = math.sqrt(d_model) if scale_embedding else 1.0
         self.weight = nn.Parameter(torch.empty(ntoken, d_model, **fk))
-        self.learned_positions = learned_positions
-        if learned_positions:
+        self.positions = positions
+        self.learned_positions = positions == "learned"
+        if positions == "learned":
             self.pos_weight = nn.Parameter(torch.empty(max_len, d_model, device=device, dtype=torch.float32))
-        else:
+        elif positions == "sinusoidal":
             self.register_buffer("pe", sinusoidal_positions(max_len, d_model).to(device), persistent=False)
         self.max_len = max_len
         self.reset_parameters()
@@ -69,13 +79,16 @@ class Encoder(nn.Module):
         nn.init.uniform_(self.weight, -0.1, 0.1)  # main.py:32-34
         if self.learned_positions:
             nn.init.normal_(self.pos_weight, std=0.01)
-        elif self.pe.device.type != "meta":
+        elif self.positions == "sinusoidal" and self.pe.device.type != "meta":
             with torch.no_grad():
                 self.pe.copy_(sinusoidal_positions(self.max_len, self.d_model))
 
     def forward(self, tokens: Tensor) -> Tensor:
         # learned positions: the fused kernels add them and accumulate their gradient
-        pe = self.pos_weight if self.learned_positions else self.pe
+        if self.positions == "none":
+            pe = None
+        else:
+            pe = self.pos_weight if self.learned_positions else self.pe
         return ops.embed_scale_posenc_dropout(tokens, self.weight, pe, self.scale, self.dropout, self.training)
 
     def flops_per_token(self, seq_len: int) -> float:
@@ -141,19 +154,26 @@ class Decoder(nn.Module):
 
 
 class FinalNorm(nn.Module):
-    """Pre-norm models' final LayerNorm (GPT-2's ln_f)."""
+    """Pre-norm models' final norm: LayerNorm (GPT-2's ln_f) or, with ``norm="rms"``, RMSNorm (no bias)."""
 
-    def __init__(self, d_model: int, eps: float = 1e-5, *, device=None, dtype=None) -> None:
+    def __init__(self, d_model: int, eps: float = 1e-5, *, norm: str = "layer", device=None, dtype=None) -> None:
         super().__init__()
+        if norm not in ("layer", "rms"):
+            raise ValueError(f"norm must be 'layer' or 'rms', got {norm!r}")
+        self.norm = norm
         self.weight = nn.Parameter(torch.ones(d_model, device=device, dtype=dtype))
-        self.bias = nn.Parameter(torch.zeros(d_model, device=device, dtype=dtype))
+        if norm == "layer":
+            self.bias = nn.Parameter(torch.zeros(d_model, device=device, dtype=dtype))
         self.eps = eps
 
     def reset_parameters(self) -> None:
         nn.init.ones_(self.weight)
-        nn.init.zeros_(self.bias)
+        if self.norm == "layer":
+            nn.init.zeros_(self.bias)
 
     def forward(self, x: Tensor) -> Tensor:
+        if self.norm == "rms":
+            return ops.add_dropout_rms_norm(x, None, self.weight, self.eps, 0.0, self.training)
         return ops.add_dropout_layer_norm(x, None, self.weight, self.bias, self.eps, 0.0, self.training)
 
     def flops_per_token(self, seq_len: int) -> float:
@@ -180,11 +200,30 @@ class LMConfig:
     # (c_fc -> gelu -> c_proj -> resid dropout)
     act_dropout: Optional[float] = None
     notes: str = ""
+    # LLaMA-style block options (defaults: the blocks above)
+    norm: str = "layer"            # "layer" | "rms" (no norm bias)
+    bias: bool = True              # False: no bias in the attention and MLP linears
+    rope: bool = False             # rotary position embeddings on Q and K
+    rope_base: float = 10000.0
+    positions: Optional[str] = None  # Encoder positions; None: "learned" if learned_positions else "sinusoidal"
+
+    def encoder_positions(self) -> str:
+        return self.positions if self.positions is not None else ("learned" if self.learned_positions else "sinusoidal")
 
     def params(self) -> int:
+        """Parameter count of the model :func:`build_lm_blocks` builds, without the zero rows that
+        pad the decoder's vocabulary to a multiple of 256 (an implementation detail of its GEMM)."""
         e, f, v = self.d_model, self.dim_feedforward, self.vocab
-        layer = 4 * e * e + 4 * e + 2 * e * f + f + e + 4 * e
-        return self.num_layers * layer + v * e + (v * e + v)
+        f1 = 2 * f if self.activation == "swiglu" else f   # the gated first GEMM
+        nb = 1 if self.bias else 0
+        norm = e * (2 if self.norm == "layer" else 1)
+        layer = 4 * e * e + 2 * norm + f1 * e + e * f + nb * (4 * e + f1 + e)
+        total = self.num_layers * layer + v * e
+        if self.encoder_positions() == "learned":
+            total += max(self.seq_len, 1024) * e
+        if self.norm_first:
+            total += norm
+        return total + (v * e + v)
 
 
 CONFIGS = {
@@ -203,6 +242,15 @@ CONFIGS = {
                         notes="GPT-2's block: attention / residual / embedding dropout 0.1, none after the GELU"),
     # Tiny config for smoke tests.
     "tiny": LMConfig("tiny", 2, 256, 4, 512, 1000, 64, dropout=0.1),
+    # LLaMA-style block: pre-norm RMSNorm, SwiGLU MLP, rotary positions, no biases, causal.
+    "llama_tiny": LMConfig("llama_tiny", 2, 256, 4, 512, 1000, 64, dropout=0.0, activation="swiglu",
+                           norm_first=True, causal=True, scale_embedding=False, act_dropout=0.0, norm="rms",
+                           bias=False, rope=True, positions="none", notes="tiny LLaMA-style model for tests"),
+    # LLaMA-2 7B: full multi-head attention (32 query = 32 key/value heads), so no GQA is needed.
+    "llama2_7b": LMConfig("llama2_7b", 32, 4096, 32, 11008, 32000, 4096, dropout=0.0, activation="swiglu",
+                          norm_first=True, causal=True, scale_embedding=False, act_dropout=0.0, norm="rms",
+                          bias=False, rope=True, positions="none",
+                          notes="LLaMA-2 7B's block; the decoder keeps its (zero-initialised) bias"),
 }
 
 
@@ -210,18 +258,19 @@ def build_lm_blocks(cfg: LMConfig, *, device=None, dtype=None) -> List[nn.Module
     """``[Encoder, attn0, mlp0, attn1, mlp1, ..., (FinalNorm), Decoder]``."""
     blocks: List[nn.Module] = [
         Encoder(cfg.vocab, cfg.d_model, cfg.dropout, max_len=max(cfg.seq_len, 1024),
-                learned_positions=cfg.learned_positions, scale_embedding=cfg.scale_embedding,
+                positions=cfg.encoder_positions(), scale_embedding=cfg.scale_embedding,
                 device=device, dtype=dtype)
     ]
     blocks += transformer_blocks(cfg.num_layers, cfg.d_model, cfg.nhead, cfg.dim_feedforward, cfg.dropout,
-                                 cfg.activation, norm_first=cfg.norm_first, causal=cfg.causal,
+                                 cfg.activation, norm_first=cfg.norm_first, causal=cfg.causal, norm=cfg.norm,
+                                 bias=cfg.bias, rope=cfg.rope, rope_base=cfg.rope_base,
                                  device=device, dtype=dtype)
     if cfg.act_dropout is not None:
         for b in blocks:
             if isinstance(b, FeedForwardBlock):
                 b.fc_in.dropout = cfg.act_dropout
     if cfg.norm_first:
-        blocks.append(FinalNorm(cfg.d_model, device=device, dtype=dtype))
+        blocks.append(FinalNorm(cfg.d_model, norm=cfg.norm, device=device, dtype=dtype))
     blocks.append(Decoder(cfg.vocab, cfg.d_model, device=device, dtype=dtype))
     return blocks
 

@@ -18,6 +18,13 @@ Hot path per block: MFMA GEMMs with fused bias/activation/dropout epilogues,
 flash attention, fused dropout+residual+LayerNorm -- see ``mipipe.ops``.
 ``from_torch`` copies weights from an ``nn.TransformerEncoderLayer`` so the
 blocks can be checked against PyTorch.
+
+Keyword options turn the same halves into a LLaMA-style block (all default to
+the behaviour above): ``norm="rms"`` (RMSNorm, no norm bias), ``bias=False`` (no
+bias parameters; the linears get ``None``), ``rope=True`` (rotary positions on
+Q and K) and ``activation="swiglu"`` (``linear1_weight`` is ``[2F, E]``: rows
+``[0, F)`` the gate projection, rows ``[F, 2F)`` the up projection; the halves
+still exchange an ``F``-wide ``h``).
 """
 from __future__ import annotations
 
@@ -58,6 +65,38 @@ def _folds(fc_in, training: bool) -> bool:
         return False
     return act != "gelu" or not (training and fc_in.dropout > 0.0)
 
+
+NORMS = ("layer", "rms")
+
+
+def _init_norm(mod: nn.Module, d_model: int, norm: str, fk: dict) -> None:
+    """``mod.norm_weight`` (and ``mod.norm_bias`` for LayerNorm: RMSNorm has none)."""
+    if norm not in NORMS:
+        raise ValueError(f"norm must be one of {NORMS}, got {norm!r}")
+    mod.norm_weight = nn.Parameter(torch.empty(d_model, **fk))
+    if norm == "layer":
+        mod.norm_bias = nn.Parameter(torch.empty(d_model, **fk))
+
+
+def _reset_norm(mod: nn.Module) -> None:
+    nn.init.ones_(mod.norm_weight)
+    if mod.norm == "layer":
+        nn.init.zeros_(mod.norm_bias)
+
+
+def _norm(mod: nn.Module, x: Tensor, residual: Optional[Tensor], p: float) -> Tensor:
+    """``norm(residual + dropout(x, p))`` with ``mod``'s norm kind and parameters."""
+    if mod.norm == "rms":
+        return ops.add_dropout_rms_norm(x, residual, mod.norm_weight, mod.eps, p, mod.training)
+    return ops.add_dropout_layer_norm(x, residual, mod.norm_weight, mod.norm_bias, mod.eps, p, mod.training)
+
+
+def _norm_fanout(mod: nn.Module, x: Tensor):
+    if mod.norm == "rms":
+        return ops.rms_norm_fanout(x, mod.norm_weight, mod.eps)
+    return ops.layer_norm_fanout(x, mod.norm_weight, mod.norm_bias, mod.eps)
+
+
 __all__ = [
     "AttentionCore",
     "AttentionOutput",
@@ -82,25 +121,41 @@ class AttentionCore(nn.Module):
     """
 
     def __init__(self, d_model: int, nhead: int, dropout: float, *, norm_first: bool, causal: bool,
-                 layer_norm_eps: float, device=None, dtype=None) -> None:
+                 layer_norm_eps: float, norm: str = "layer", bias: bool = True, rope: bool = False,
+                 rope_base: float = 10000.0, device=None, dtype=None) -> None:
         super().__init__()
         fk = {"device": device, "dtype": dtype}
         self.d_model, self.nhead, self.head_dim = d_model, nhead, d_model // nhead
         self.dropout, self.norm_first, self.causal, self.eps = dropout, norm_first, causal, layer_norm_eps
+        self.norm, self.rope, self.rope_base = norm, rope, rope_base
+        if rope and self.head_dim % 2 != 0:  # (the HIP kernel wants a multiple of 16 and says so itself)
+            raise ValueError(f"rope needs an even head dim, got {self.head_dim}")
         self.in_proj_weight = mark_gemm_weight(nn.Parameter(torch.empty(3 * d_model, d_model, **fk)))
-        self.in_proj_bias = nn.Parameter(torch.empty(3 * d_model, **fk))
+        self.in_proj_bias = nn.Parameter(torch.empty(3 * d_model, **fk)) if bias else None
         if norm_first:
-            self.norm_weight = nn.Parameter(torch.empty(d_model, **fk))
-            self.norm_bias = nn.Parameter(torch.empty(d_model, **fk))
+            _init_norm(self, d_model, norm, fk)
+        if rope:
+            # cos / sin tables [positions, head_dim / 2], fp32: sized to the sequence, grown on demand
+            empty = torch.empty(0, self.head_dim // 2, device=device, dtype=torch.float32)
+            self.register_buffer("rope_cos", empty, persistent=False)
+            self.register_buffer("rope_sin", empty.clone(), persistent=False)
         self.reset_parameters()
 
     def reset_parameters(self) -> None:
         # nn.MultiheadAttention's init: xavier on in_proj, zero biases.
         nn.init.xavier_uniform_(self.in_proj_weight)
-        nn.init.zeros_(self.in_proj_bias)
+        if self.in_proj_bias is not None:
+            nn.init.zeros_(self.in_proj_bias)
         if self.norm_first:
-            nn.init.ones_(self.norm_weight)
-            nn.init.zeros_(self.norm_bias)
+            _reset_norm(self)
+
+    def _rope_tables(self, seq_len: int, device):
+        # rebuilt when too short, on another device, or cast by a module-wide .to(dtype): the kernel reads fp32
+        if (self.rope_cos.shape[0] < seq_len or self.rope_cos.device != device
+                or self.rope_cos.dtype != torch.float32):
+            cos, sin = ops.rope_tables(seq_len, self.head_dim, self.rope_base, device=device)
+            self.rope_cos, self.rope_sin = cos, sin
+        return self.rope_cos, self.rope_sin
 
     def forward(self, x: Tensor) -> Tensor:
         return self.forward_fanout(x, fanout=False)[0]
@@ -115,10 +170,9 @@ class AttentionCore(nn.Module):
         xr = x
         if self.norm_first:
             if fanout:
-                x, xr = ops.layer_norm_fanout(x, self.norm_weight, self.norm_bias, self.eps)
+                x, xr = _norm_fanout(self, x)
             else:
-                x = ops.add_dropout_layer_norm(x, None, self.norm_weight, self.norm_bias, self.eps, 0.0,
-                                               self.training)
+                x = _norm(self, x, None, 0.0)
             qkv = ops.linear(x, self.in_proj_weight, self.in_proj_bias)
         elif fanout:
             qkv, xr = ops.linear_fanout(x, self.in_proj_weight, self.in_proj_bias)
@@ -126,8 +180,13 @@ class AttentionCore(nn.Module):
             qkv = ops.linear(x, self.in_proj_weight, self.in_proj_bias)
         # The projection output viewed as [B, S, 3, H, D] feeds the kernel in
         # place; its output [B, S, H, D] is already [B, S, E] -- no transposes.
-        o = ops.attention_packed(qkv.view(B, S, 3, H, D), causal=self.causal, dropout_p=self.dropout,
-                                 training=self.training)
+        if self.rope:
+            # Q and K rotated: in the projection's own output where no graph is recorded, else into a new tensor
+            cos, sin = self._rope_tables(S, qkv.device)
+            qkv5 = ops.rope_projection(qkv, cos, sin, H)
+        else:
+            qkv5 = qkv.view(B, S, 3, H, D)
+        o = ops.attention_packed(qkv5, causal=self.causal, dropout_p=self.dropout, training=self.training)
         return o.reshape(B, S, E), xr
 
     def flops_per_token(self, seq_len: int) -> float:
@@ -139,31 +198,31 @@ class AttentionOutput(nn.Module):
     """``out_proj`` + dropout + residual (+ LayerNorm for post-norm): ``(x, o) -> y``."""
 
     def __init__(self, d_model: int, dropout: float, *, norm_first: bool, layer_norm_eps: float,
-                 device=None, dtype=None) -> None:
+                 norm: str = "layer", bias: bool = True, device=None, dtype=None) -> None:
         super().__init__()
         fk = {"device": device, "dtype": dtype}
         self.d_model, self.dropout, self.norm_first, self.eps = d_model, dropout, norm_first, layer_norm_eps
+        self.norm = norm
         self.out_proj_weight = mark_gemm_weight(nn.Parameter(torch.empty(d_model, d_model, **fk)))
-        self.out_proj_bias = nn.Parameter(torch.empty(d_model, **fk))
+        self.out_proj_bias = nn.Parameter(torch.empty(d_model, **fk)) if bias else None
         if not norm_first:
-            self.norm_weight = nn.Parameter(torch.empty(d_model, **fk))
-            self.norm_bias = nn.Parameter(torch.empty(d_model, **fk))
+            _init_norm(self, d_model, norm, fk)
         self.reset_parameters()
 
     def reset_parameters(self) -> None:
         bound = 1.0 / math.sqrt(self.d_model)
         nn.init.uniform_(self.out_proj_weight, -bound, bound)
-        nn.init.zeros_(self.out_proj_bias)
+        if self.out_proj_bias is not None:
+            nn.init.zeros_(self.out_proj_bias)
         if not self.norm_first:
-            nn.init.ones_(self.norm_weight)
-            nn.init.zeros_(self.norm_bias)
+            _reset_norm(self)
 
     def forward(self, x: Tensor, o: Tensor) -> Tensor:
         p = self.dropout if self.training else 0.0
         if self.norm_first:
             return ops.linear_residual(o, self.out_proj_weight, self.out_proj_bias, x, p, self.training)
         a = ops.linear(o, self.out_proj_weight, self.out_proj_bias)
-        return ops.add_dropout_layer_norm(a, x, self.norm_weight, self.norm_bias, self.eps, p, self.training)
+        return _norm(self, a, x, p)
 
     def flops_per_token(self, seq_len: int) -> float:
         return 2 * self.d_model * self.d_model
@@ -177,14 +236,16 @@ class SelfAttentionBlock(nn.Module):
     """
 
     def __init__(self, d_model: int, nhead: int, dropout: float = 0.1, *, norm_first: bool = False,
-                 causal: bool = False, layer_norm_eps: float = 1e-5, device=None, dtype=None) -> None:
+                 causal: bool = False, layer_norm_eps: float = 1e-5, norm: str = "layer", bias: bool = True,
+                 rope: bool = False, rope_base: float = 10000.0, device=None, dtype=None) -> None:
         super().__init__()
         if d_model % nhead != 0:
             raise ValueError("d_model must be divisible by nhead")
         self.core = AttentionCore(d_model, nhead, dropout, norm_first=norm_first, causal=causal,
-                                  layer_norm_eps=layer_norm_eps, device=device, dtype=dtype)
+                                  layer_norm_eps=layer_norm_eps, norm=norm, bias=bias, rope=rope,
+                                  rope_base=rope_base, device=device, dtype=dtype)
         self.out = AttentionOutput(d_model, dropout, norm_first=norm_first, layer_norm_eps=layer_norm_eps,
-                                   device=device, dtype=dtype)
+                                   norm=norm, bias=bias, device=device, dtype=dtype)
 
     def reset_parameters(self) -> None:
         self.core.reset_parameters()
@@ -274,25 +335,27 @@ class FeedForwardIn(nn.Module):
     """First half of the MLP: ``h = drop(act(W1 x + b1))`` (pre-norm: of ``LN2(x)``)."""
 
     def __init__(self, d_model: int, dim_feedforward: int, dropout: float, activation: str, *, norm_first: bool,
-                 layer_norm_eps: float, device=None, dtype=None) -> None:
+                 layer_norm_eps: float, norm: str = "layer", bias: bool = True, device=None, dtype=None) -> None:
         super().__init__()
         fk = {"device": device, "dtype": dtype}
         self.d_model, self.dim_feedforward = d_model, dim_feedforward
         self.dropout, self.activation, self.norm_first, self.eps = dropout, activation, norm_first, layer_norm_eps
-        self.linear1_weight = mark_gemm_weight(nn.Parameter(torch.empty(dim_feedforward, d_model, **fk)))
-        self.linear1_bias = nn.Parameter(torch.empty(dim_feedforward, **fk))
+        self.norm = norm
+        # "swiglu": the gate projection (rows [0, F)) and the up projection (rows [F, 2F)) in ONE weight
+        width = 2 * dim_feedforward if activation == "swiglu" else dim_feedforward
+        self.linear1_weight = mark_gemm_weight(nn.Parameter(torch.empty(width, d_model, **fk)))
+        self.linear1_bias = nn.Parameter(torch.empty(width, **fk)) if bias else None
         if norm_first:
-            self.norm_weight = nn.Parameter(torch.empty(d_model, **fk))
-            self.norm_bias = nn.Parameter(torch.empty(d_model, **fk))
+            _init_norm(self, d_model, norm, fk)
         self.reset_parameters()
 
     def reset_parameters(self) -> None:
         nn.init.kaiming_uniform_(self.linear1_weight, a=math.sqrt(5))
-        bound = 1.0 / math.sqrt(self.linear1_weight.shape[1])
-        nn.init.uniform_(self.linear1_bias, -bound, bound)
+        if self.linear1_bias is not None:
+            bound = 1.0 / math.sqrt(self.linear1_weight.shape[1])
+            nn.init.uniform_(self.linear1_bias, -bound, bound)
         if self.norm_first:
-            nn.init.ones_(self.norm_weight)
-            nn.init.zeros_(self.norm_bias)
+            _reset_norm(self)
 
     def forward(self, x: Tensor) -> Tensor:
         return self.forward_fanout(x, fanout=False)[0]
@@ -302,44 +365,52 @@ class FeedForwardIn(nn.Module):
         only consumer applies the activation backward (:class:`ActFold`)."""
         p = self.dropout if self.training else 0.0
         w, b, act = self.linear1_weight, self.linear1_bias, self.activation
+        if act == "swiglu":
+            if p > 0.0:
+                raise ValueError("activation='swiglu' has no dropout between the gate and linear2: set "
+                                 "act_dropout=0.0 (FeedForwardIn.dropout)")
+            if self.norm_first:
+                xn, xr = _norm_fanout(self, x) if fanout else (_norm(self, x, None, 0.0), x)
+                return ops.swiglu(ops.linear(xn, w, b)), xr
+            gu, xr = ops.linear_fanout(x, w, b) if fanout else (ops.linear(x, w, b), x)
+            return ops.swiglu(gu), xr
         if self.norm_first:
             if fanout:
-                xn, xr = ops.layer_norm_fanout(x, self.norm_weight, self.norm_bias, self.eps)
+                xn, xr = _norm_fanout(self, x)
             else:
-                xn, xr = ops.add_dropout_layer_norm(x, None, self.norm_weight, self.norm_bias, self.eps, 0.0,
-                                                    self.training), x
+                xn, xr = _norm(self, x, None, 0.0), x
             return ops.linear(xn, w, b, act, p, self.training, act_fold_out=fold), xr
         if fanout:
             return ops.linear_fanout(x, w, b, act, p, self.training, act_fold_out=fold)
         return ops.linear(x, w, b, act, p, self.training, act_fold_out=fold), x
 
     def flops_per_token(self, seq_len: int) -> float:
-        return 2 * self.d_model * self.dim_feedforward
+        return 2 * self.d_model * self.linear1_weight.shape[0]  # the gated first GEMM is 2F wide
 
 
 class FeedForwardOut(nn.Module):
     """Second half: ``LN2(x + drop(W2 h + b2))`` (pre-norm: ``x + drop(W2 h + b2)``)."""
 
     def __init__(self, d_model: int, dim_feedforward: int, dropout: float, *, norm_first: bool, layer_norm_eps: float,
-                 device=None, dtype=None) -> None:
+                 norm: str = "layer", bias: bool = True, device=None, dtype=None) -> None:
         super().__init__()
         fk = {"device": device, "dtype": dtype}
         self.d_model, self.dim_feedforward = d_model, dim_feedforward
         self.dropout, self.norm_first, self.eps = dropout, norm_first, layer_norm_eps
+        self.norm = norm
         self.linear2_weight = mark_gemm_weight(nn.Parameter(torch.empty(d_model, dim_feedforward, **fk)))
-        self.linear2_bias = nn.Parameter(torch.empty(d_model, **fk))
+        self.linear2_bias = nn.Parameter(torch.empty(d_model, **fk)) if bias else None
         if not norm_first:
-            self.norm_weight = nn.Parameter(torch.empty(d_model, **fk))
-            self.norm_bias = nn.Parameter(torch.empty(d_model, **fk))
+            _init_norm(self, d_model, norm, fk)
         self.reset_parameters()
 
     def reset_parameters(self) -> None:
         nn.init.kaiming_uniform_(self.linear2_weight, a=math.sqrt(5))
-        bound = 1.0 / math.sqrt(self.linear2_weight.shape[1])
-        nn.init.uniform_(self.linear2_bias, -bound, bound)
+        if self.linear2_bias is not None:
+            bound = 1.0 / math.sqrt(self.linear2_weight.shape[1])
+            nn.init.uniform_(self.linear2_bias, -bound, bound)
         if not self.norm_first:
-            nn.init.ones_(self.norm_weight)
-            nn.init.zeros_(self.norm_bias)
+            _reset_norm(self)
 
     def forward(self, x: Tensor, h: Tensor, fold: Optional[ActFold] = None) -> Tensor:
         p = self.dropout if self.training else 0.0
@@ -347,7 +418,7 @@ class FeedForwardOut(nn.Module):
             return ops.linear_residual(h, self.linear2_weight, self.linear2_bias, x, p, self.training,
                                        act_fold_in=fold)
         h = ops.linear(h, self.linear2_weight, self.linear2_bias, act_fold_in=fold)
-        return ops.add_dropout_layer_norm(h, x, self.norm_weight, self.norm_bias, self.eps, p, self.training)
+        return _norm(self, h, x, p)
 
     def flops_per_token(self, seq_len: int) -> float:
         return 2 * self.d_model * self.dim_feedforward
@@ -366,6 +437,8 @@ class FeedForwardBlock(nn.Module):
         *,
         norm_first: bool = False,
         layer_norm_eps: float = 1e-5,
+        norm: str = "layer",
+        bias: bool = True,
         device=None,
         dtype=None,
     ) -> None:
@@ -373,9 +446,10 @@ class FeedForwardBlock(nn.Module):
         self.d_model, self.dim_feedforward = d_model, dim_feedforward
         self.norm_first = norm_first
         self.fc_in = FeedForwardIn(d_model, dim_feedforward, dropout, activation, norm_first=norm_first,
-                                   layer_norm_eps=layer_norm_eps, device=device, dtype=dtype)
+                                   layer_norm_eps=layer_norm_eps, norm=norm, bias=bias, device=device, dtype=dtype)
         self.fc_out = FeedForwardOut(d_model, dim_feedforward, dropout, norm_first=norm_first,
-                                     layer_norm_eps=layer_norm_eps, device=device, dtype=dtype)
+                                     layer_norm_eps=layer_norm_eps, norm=norm, bias=bias, device=device,
+                                     dtype=dtype)
 
     def reset_parameters(self) -> None:
         self.fc_in.reset_parameters()
@@ -391,7 +465,7 @@ class FeedForwardBlock(nn.Module):
         return out
 
     def flops_per_token(self, seq_len: int) -> float:
-        return 2 * 2 * self.d_model * self.dim_feedforward
+        return self.fc_in.flops_per_token(seq_len) + self.fc_out.flops_per_token(seq_len)
 
 
 class PackedFeedForwardIn(nn.Module):
@@ -447,12 +521,18 @@ class TransformerEncoderLayer(nn.Sequential):
         causal: bool = False,
         device=None,
         dtype=None,
+        *,
+        norm: str = "layer",
+        bias: bool = True,
+        rope: bool = False,
+        rope_base: float = 10000.0,
     ) -> None:
         super().__init__(
             SelfAttentionBlock(d_model, nhead, dropout, norm_first=norm_first, causal=causal,
-                               layer_norm_eps=layer_norm_eps, device=device, dtype=dtype),
+                               layer_norm_eps=layer_norm_eps, norm=norm, bias=bias, rope=rope, rope_base=rope_base,
+                               device=device, dtype=dtype),
             FeedForwardBlock(d_model, dim_feedforward, dropout, activation, norm_first=norm_first,
-                             layer_norm_eps=layer_norm_eps, device=device, dtype=dtype),
+                             layer_norm_eps=layer_norm_eps, norm=norm, bias=bias, device=device, dtype=dtype),
         )
 
     @torch.no_grad()
@@ -486,6 +566,10 @@ def transformer_blocks(
     *,
     norm_first: bool = False,
     causal: bool = False,
+    norm: str = "layer",
+    bias: bool = True,
+    rope: bool = False,
+    rope_base: float = 10000.0,
     device=None,
     dtype=None,
 ) -> List[nn.Module]:
@@ -493,7 +577,8 @@ def transformer_blocks(
     blocks: List[nn.Module] = []
     for _ in range(num_layers):
         layer = TransformerEncoderLayer(d_model, nhead, dim_feedforward, dropout, activation,
-                                        norm_first=norm_first, causal=causal, device=device, dtype=dtype)
+                                        norm_first=norm_first, causal=causal, norm=norm, bias=bias, rope=rope,
+                                        rope_base=rope_base, device=device, dtype=dtype)
         blocks.extend(layer.children())
     return blocks
 

@@ -6,9 +6,12 @@ CPU tensors (plumbing tests).  GPU tensors never fall back to eager PyTorch:
 a missing extension raises (``mipipe._native_loader.kernels``).
 """
 from .layernorm import add_dropout_layer_norm, layer_norm_fanout, layer_norm_reference
+from .rmsnorm import add_dropout_rms_norm, rms_norm_fanout, rms_norm_reference
 from .linear import deferred_wgrad, flush_wgrad, linear, linear_fanout, linear_residual
 from .attention import attention, attention_packed, attention_reference
 from .activation import bias_act_dropout
+from .swiglu import swiglu, swiglu_reference
+from .rope import rope_packed, rope_projection, rope_reference, rope_tables
 from .loss import cross_entropy
 from .embedding import embed_scale_posenc_dropout
 
@@ -16,6 +19,9 @@ __all__ = [
     "add_dropout_layer_norm",
     "layer_norm_fanout",
     "layer_norm_reference",
+    "add_dropout_rms_norm",
+    "rms_norm_fanout",
+    "rms_norm_reference",
     "linear",
     "linear_fanout",
     "linear_residual",
@@ -25,6 +31,12 @@ __all__ = [
     "attention_packed",
     "attention_reference",
     "bias_act_dropout",
+    "swiglu",
+    "swiglu_reference",
+    "rope_tables",
+    "rope_packed",
+    "rope_projection",
+    "rope_reference",
     "cross_entropy",
     "embed_scale_posenc_dropout",
 ]

@@ -65,7 +65,10 @@ def block_costs(cfg: LMConfig, split_decoder: bool = False) -> List[float]:
     causal = 0.5 if cfg.causal else 1.0
     core = 3.0 * (2 * 3 * e * e + 4 * s * e * causal) + 3.0 * 10 * e
     out = 3.0 * (2 * e * e) + 3.0 * 10 * e  # + LN/dropout traffic
-    mlp_in = 3.0 * (2 * e * f) + 3.0 * 5 * f
+    if cfg.activation == "swiglu":  # the gated first GEMM is 2F wide, and the gate is a pass of its own
+        mlp_in = 3.0 * (2 * e * 2 * f) + 3.0 * 10 * f
+    else:
+        mlp_in = 3.0 * (2 * e * f) + 3.0 * 5 * f
     mlp_out = 3.0 * (2 * e * f) + 3.0 * 10 * e
     enc = 3.0 * 40 * e  # gather + scatter-add traffic, expressed in FLOP-equivalents
     dec = 3.0 * (2 * e * v) + 3.0 * 4 * v  # GEMM + cross-entropy passes
