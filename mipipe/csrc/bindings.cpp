@@ -353,45 +353,93 @@ Tensor py_swiglu_bwd(Tensor dh, Tensor gu) {
   return dgu;
 }
 
-// out: None (a fresh tensor, V copied) or a tensor of qkv's layout; out being qkv itself rotates in place.
-Tensor py_rope_packed(Tensor qkv, Tensor cos, Tensor sin, std::optional<Tensor> out, int64_t pos0, bool inverse) {
-  check_cuda(qkv, "qkv");
+// x [B, S, heads, D] with the first n_rot heads of a token rotated and the rest passed through.
+// out: None (a fresh tensor, the rest copied) or a tensor of x's layout; out being x itself rotates in place.
+Tensor rope_impl(Tensor x, Tensor cos, Tensor sin, std::optional<Tensor> out, int64_t n_rot, int64_t pos0, bool inverse,
+                 const char* name) {
+  check_cuda(x, "qkv");
   check_cuda(cos, "cos");
   check_cuda(sin, "sin");
-  MP_CHECK(qkv.dim() == 5 && qkv.size(2) == 3, "rope_packed: qkv must be [B, S, 3, H, D]");
-  const int64_t B = qkv.size(0), S = qkv.size(1), H = qkv.size(3), D = qkv.size(4);
-  MP_CHECK(D > 0 && D % 16 == 0, "rope_packed: head dim must be a multiple of 16, got ", D);
-  MP_CHECK(S <= INT32_MAX / 2 && H * D <= INT32_MAX / 8, "rope_packed: shape too large");
-  MP_CHECK(pos0 >= 0 && pos0 <= INT32_MAX / 2, "rope_packed: bad pos0 ", pos0);
+  const int64_t B = x.size(0), S = x.size(1), heads = x.size(2), D = x.size(3);
+  MP_CHECK(n_rot >= 0 && n_rot <= heads, name, ": n_rot must be in [0, heads], got ", n_rot);
+  MP_CHECK(D > 0 && D % 16 == 0, name, ": head dim must be a multiple of 16, got ", D);
+  MP_CHECK(S <= INT32_MAX / 2 && heads * D <= INT32_MAX / 8 * 3, name, ": shape too large");
+  MP_CHECK(pos0 >= 0 && pos0 <= INT32_MAX / 2, name, ": bad pos0 ", pos0);
   for (auto* t : {&cos, &sin}) {
     MP_CHECK(t->scalar_type() == at::kFloat && t->dim() == 2 && t->size(1) == D / 2 && t->size(0) >= pos0 + S &&
-                 t->device() == qkv.device(),
-             "rope_packed: cos / sin must be fp32 [>= pos0 + S, D / 2] on qkv's device");
+                 t->device() == x.device(),
+             name, ": cos / sin must be fp32 [>= pos0 + S, D / 2] on qkv's device");
   }
-  at::hip::HIPGuardMasqueradingAsCUDA guard(qkv.device());
+  at::hip::HIPGuardMasqueradingAsCUDA guard(x.device());
   Tensor o;
   if (out.has_value()) {
     o = *out;
     check_cuda(o, "out");
-    check_same(qkv, o, "qkv", "out");
-    MP_CHECK(o.sizes() == qkv.sizes(), "rope_packed: out must have qkv's shape");
+    check_same(x, o, "qkv", "out");
+    MP_CHECK(o.sizes() == x.sizes(), name, ": out must have qkv's shape");
     // the same tensor or a disjoint one: a partial overlap would race
-    if (o.data_ptr() != qkv.data_ptr()) {
-      const char* a = static_cast<const char*>(qkv.data_ptr());
+    if (o.data_ptr() != x.data_ptr()) {
+      const char* a = static_cast<const char*>(x.data_ptr());
       const char* b = static_cast<const char*>(o.data_ptr());
-      const int64_t n = (int64_t)qkv.nbytes();
-      MP_CHECK(b + n <= a || a + n <= b, "rope_packed: out partly overlaps qkv");
+      const int64_t n = (int64_t)x.nbytes();
+      MP_CHECK(b + n <= a || a + n <= b, name, ": out partly overlaps qkv");
     }
   } else {
-    o = at::empty_like(qkv);
+    o = at::empty_like(x);
   }
-  auto s = cur_stream(qkv);
-  dispatch_fb(qkv, "rope_packed", [&](auto* tag) {
+  auto s = cur_stream(x);
+  dispatch_fb(x, name, [&](auto* tag) {
     using T = std::remove_pointer_t<decltype(tag)>;
-    rope_packed<T>(cptr<T>(qkv), cptr<float>(cos), cptr<float>(sin), ptr<T>(o), B, (int)S, (int)H, (int)D, (int)pos0,
-                   inverse, s);
+    rope_heads<T>(cptr<T>(x), cptr<float>(cos), cptr<float>(sin), ptr<T>(o), B, (int)S, (int)n_rot,
+                  (int)(heads - n_rot), (int)D, (int)pos0, inverse, s);
   });
   return o;
+}
+
+// qkv [B, S, 3, H, D]: Q and K rotated, V passed through.
+Tensor py_rope_packed(Tensor qkv, Tensor cos, Tensor sin, std::optional<Tensor> out, int64_t pos0, bool inverse) {
+  MP_CHECK(qkv.dim() == 5 && qkv.size(2) == 3, "rope_packed: qkv must be [B, S, 3, H, D]");
+  const int64_t H = qkv.size(3);
+  const std::vector<int64_t> shape4 = {qkv.size(0), qkv.size(1), 3 * H, qkv.size(4)};
+  MP_CHECK(qkv.is_contiguous(), "rope_packed: qkv must be contiguous");
+  std::optional<Tensor> out4;
+  if (out.has_value()) {
+    MP_CHECK(out->sizes() == qkv.sizes() && out->is_contiguous(), "rope_packed: out must have qkv's shape and layout");
+    out4 = out->view(shape4);
+  }
+  Tensor o = rope_impl(qkv.view(shape4), cos, sin, out4, 2 * H, pos0, inverse, "rope_packed");
+  return out.has_value() ? *out : o.view(qkv.sizes());
+}
+
+// x [B, S, heads, D] (the grouped-query projection [B, S, H + 2 Hkv, D] with n_rot = H + Hkv).
+Tensor py_rope_heads(Tensor x, Tensor cos, Tensor sin, std::optional<Tensor> out, int64_t n_rot, int64_t pos0,
+                     bool inverse) {
+  MP_CHECK(x.dim() == 4 && x.is_contiguous() && (!out.has_value() || out->is_contiguous()),
+           "rope_heads: x (and out) must be contiguous [B, S, heads, D]");
+  return rope_impl(x, cos, sin, out, n_rot, pos0, inverse, "rope_heads");
+}
+
+// dkv [B, S, 2, H, D] (per-query-head dK / dV partials) summed per group into the K and V heads of
+// dqkv [B, S, H + 2 Hkv, D]; the Q heads of dqkv are not touched.
+void py_gqa_reduce_dkv(Tensor dkv, Tensor dqkv, int64_t H, int64_t Hkv) {
+  check_cuda(dkv, "dkv");
+  check_cuda(dqkv, "dqkv");
+  check_same(dkv, dqkv, "dkv", "dqkv");
+  MP_CHECK(H > 0 && Hkv > 0 && H % Hkv == 0, "gqa_reduce_dkv: H must be a positive multiple of Hkv, got ", H, " / ", Hkv);
+  MP_CHECK(dkv.dim() == 5 && dkv.size(2) == 2 && dkv.size(3) == H, "gqa_reduce_dkv: dkv must be [B, S, 2, H, D]");
+  const int64_t B = dkv.size(0), S = dkv.size(1), D = dkv.size(4);
+  MP_CHECK(D > 0 && D % 8 == 0, "gqa_reduce_dkv: head dim must be a multiple of 8, got ", D);
+  MP_CHECK(dqkv.dim() == 4 && dqkv.size(0) == B && dqkv.size(1) == S && dqkv.size(2) == H + 2 * Hkv &&
+               dqkv.size(3) == D,
+           "gqa_reduce_dkv: dqkv must be [B, S, H + 2 Hkv, D] = [", B, ", ", S, ", ", H + 2 * Hkv, ", ", D, "]");
+  MP_CHECK(dkv.is_contiguous() && dqkv.is_contiguous(), "gqa_reduce_dkv: dkv and dqkv must be contiguous");
+  MP_CHECK(H * D <= INT32_MAX / 8, "gqa_reduce_dkv: shape too large");
+  at::hip::HIPGuardMasqueradingAsCUDA guard(dkv.device());
+  auto s = cur_stream(dkv);
+  dispatch_fb(dkv, "gqa_reduce_dkv", [&](auto* tag) {
+    using T = std::remove_pointer_t<decltype(tag)>;
+    gqa_reduce_dkv<T>(cptr<T>(dkv), ptr<T>(dqkv), B * S, (int)H, (int)Hkv, (int)D, s);
+  });
 }
 
 std::tuple<Tensor, int64_t, int64_t> py_bias_act_fwd(Tensor x, std::optional<Tensor> bias, int64_t act, double p) {
@@ -1140,16 +1188,27 @@ bool attn_ok(at::ScalarType t, int S, int D) {
   return t == at::kFloat ? attention_f32_supported(S, D) : attention_supported(S, D);
 }
 
+// k and v may hold fewer heads than q (grouped-query attention: query head h reads K / V head
+// h / group, group = H / Hkv) but share q's batch, token and head strides -- views of one packed
+// projection.
 void fill_qkv(AttnArgs& a, const Tensor& q, const Tensor& k, const Tensor& v) {
   check_bshd(q, "q");
   check_bshd(k, "k");
   check_bshd(v, "v");
-  MP_CHECK(q.sizes() == k.sizes() && q.sizes() == v.sizes(), "attention: q, k, v shapes differ");
+  MP_CHECK(k.sizes() == v.sizes(), "attention: k, v shapes differ");
+  MP_CHECK(q.size(0) == k.size(0) && q.size(1) == k.size(1) && q.size(3) == k.size(3) && k.size(2) > 0 &&
+               q.size(2) % k.size(2) == 0,
+           "attention: k, v must have q's batch, length and head dim and a head count dividing q's");
   MP_CHECK(q.strides() == k.strides() && q.strides() == v.strides(), "attention: q, k, v strides differ");
   MP_CHECK(q.scalar_type() == k.scalar_type() && q.scalar_type() == v.scalar_type(), "attention: q, k, v dtypes differ");
   a.q = q.data_ptr(); a.k = k.data_ptr(); a.v = v.data_ptr();
   a.B = (int)q.size(0); a.S = (int)q.size(1); a.H = (int)q.size(2); a.D = (int)q.size(3);
+  a.group = (int)(q.size(2) / k.size(2));
   a.sb_qkv = q.stride(0); a.ld_qkv = q.stride(1); a.sh_qkv = q.stride(2);
+  MP_CHECK(a.group == 1 || q.scalar_type() == at::kBFloat16,
+           "attention: fewer K/V heads than query heads run on the bf16 kernels only (repeat the K/V heads for ",
+           q.scalar_type(), ")");
+  MP_CHECK(attn_group_ok(a.H, a.group), "attention: H=", a.H, " query heads over ", k.size(2), " K/V heads is too large");
   MP_CHECK(attn_ok(q.scalar_type(), a.S, a.D), "attention: unsupported S=", a.S, " D=", a.D, " for ",
            q.scalar_type(), " (bf16: S % 64 == 0, D in {64,128,256}; fp32: S % 32 == 0, D in {64,128})");
 }
@@ -1223,12 +1282,33 @@ void py_attention_bwd(Tensor dout, Tensor q, Tensor k, Tensor v, Tensor o, Tenso
                dq.scalar_type() == q.scalar_type(), "attention_bwd: dtypes differ");
   MP_CHECK(dq.strides() == q.strides() && dk.strides() == q.strides() && dv.strides() == q.strides(),
            "attention_bwd: gradient buffers must share q's layout");
+  MP_CHECK(dq.sizes() == q.sizes() && dk.sizes() == k.sizes() && dv.sizes() == k.sizes() &&
+               dk.scalar_type() == q.scalar_type() && dv.scalar_type() == q.scalar_type(),
+           "attention_bwd: gradient buffers must have q's / k's / v's shapes and dtype");
   MP_CHECK(lse.scalar_type() == at::kFloat && lse.numel() == (int64_t)a.B * a.H * a.S, "attention_bwd: bad lse");
   at::hip::HIPGuardMasqueradingAsCUDA guard(q.device());
   auto delta = at::empty({a.B, a.H, a.S}, q.options().dtype(at::kFloat));
   a.o = o.data_ptr(); a.dout = dout.data_ptr();
   a.sb_o = o.stride(0); a.ld_o = o.stride(1); a.sh_o = o.stride(2);
   a.dq = dq.data_ptr(); a.dk = dk.data_ptr(); a.dv = dv.data_ptr();
+  // Grouped-query attention: the dK / dV kernels keep one block per QUERY head and write its partial into a
+  // scratch [B, S, 2, H, D]; gqa_reduce_dkv then sums each group into dk / dv, which must be the K and V head
+  // slots of one packed contiguous dqkv [B, S, H + 2 Hkv, D] whose first H heads are dq.
+  Tensor dkv;
+  const int64_t Hkv = a.H / a.group, es = (int64_t)q.element_size();
+  if (a.group > 1) {
+    const int64_t ld = (a.H + 2 * Hkv) * (int64_t)a.D;
+    const char* base = static_cast<const char*>(dq.data_ptr());
+    MP_CHECK(dq.stride(2) == a.D && dq.stride(1) == ld && dq.stride(0) == ld * a.S &&
+                 static_cast<const char*>(dk.data_ptr()) == base + (int64_t)a.H * a.D * es &&
+                 static_cast<const char*>(dv.data_ptr()) == base + (a.H + Hkv) * a.D * es,
+             "attention_bwd: with fewer K/V heads dq, dk, dv must be the head slices of one packed contiguous "
+             "[B, S, H + 2 Hkv, D] gradient");
+    dkv = at::empty({a.B, a.S, 2, a.H, a.D}, q.options());
+    a.dk = dkv.data_ptr();
+    a.dv = static_cast<char*>(dkv.data_ptr()) + (int64_t)a.H * a.D * es;
+    a.sb_dkv = dkv.stride(0); a.ld_dkv = dkv.stride(1); a.sh_dkv = dkv.stride(3);
+  }
   a.lse = ptr<float>(lse); a.delta = ptr<float>(delta);
   a.scale = (float)scale; a.p = (float)p; a.seed = (uint64_t)seed; a.offset = (uint64_t)offset; a.causal = causal;
   if (q.scalar_type() == at::kFloat) {
@@ -1243,6 +1323,10 @@ void py_attention_bwd(Tensor dout, Tensor q, Tensor k, Tensor v, Tensor o, Tenso
     attention_long_bwd(a, cur_stream(q));
   } else {
     attention_bwd(a, cur_stream(q));
+  }
+  if (a.group > 1) {
+    gqa_reduce_dkv<bf16_t>(cptr<bf16_t>(dkv), static_cast<bf16_t*>(dq.data_ptr()), (int64_t)a.B * a.S, a.H, (int)Hkv,
+                           a.D, cur_stream(q));
   }
 }
 
@@ -1422,6 +1506,12 @@ PYBIND11_MODULE(_C, m) {
   m.def("swiglu_bwd", &py_swiglu_bwd);
   m.def("rope_packed", &py_rope_packed, py::arg("qkv"), py::arg("cos"), py::arg("sin"), py::arg("out") = py::none(),
         py::arg("pos0") = 0, py::arg("inverse") = false);
+  m.def("rope_heads", &py_rope_heads, py::arg("x"), py::arg("cos"), py::arg("sin"), py::arg("out") = py::none(),
+        py::arg("n_rot"), py::arg("pos0") = 0, py::arg("inverse") = false,
+        "x [B, S, heads, D]: the first n_rot heads of every token rotated, the rest passed through");
+  m.def("gqa_reduce_dkv", &py_gqa_reduce_dkv, py::arg("dkv"), py::arg("dqkv"), py::arg("H"), py::arg("Hkv"),
+        "dkv [B, S, 2, H, D] per-query-head dK / dV partials -> group sums in the K / V heads of dqkv "
+        "[B, S, H + 2 Hkv, D]");
   m.def("bias_act_fwd", &py_bias_act_fwd);
   m.def("bias_act_bwd", &py_bias_act_bwd, py::arg("dy"), py::arg("saved"), py::arg("bias"), py::arg("act"),
         py::arg("p"), py::arg("seed"), py::arg("offset"), py::arg("need_dbias"), py::arg("dbias_acc") = py::none());

@@ -206,8 +206,8 @@ __global__ void __launch_bounds__(kThreads, D == 256 ? 1 : 2) attn_fwd_kernel(At
   bf16_t* scr = scr_all + wave * 16 * kScrStride;
 
   const bf16_t* Q = reinterpret_cast<const bf16_t*>(a.q) + (int64_t)b * a.sb_qkv + (int64_t)h * a.sh_qkv;
-  const bf16_t* K = reinterpret_cast<const bf16_t*>(a.k) + (int64_t)b * a.sb_qkv + (int64_t)h * a.sh_qkv;
-  const bf16_t* V = reinterpret_cast<const bf16_t*>(a.v) + (int64_t)b * a.sb_qkv + (int64_t)h * a.sh_qkv;
+  const bf16_t* K = reinterpret_cast<const bf16_t*>(a.k) + (int64_t)b * a.sb_qkv + (int64_t)kv_head(a, h) * a.sh_qkv;
+  const bf16_t* V = reinterpret_cast<const bf16_t*>(a.v) + (int64_t)b * a.sb_qkv + (int64_t)kv_head(a, h) * a.sh_qkv;
 
   // Q fragments of this wave's 16 rows (A operand), kept in registers.
   constexpr int NS = D / 32;
@@ -380,8 +380,8 @@ __global__ void __launch_bounds__(kThreads, 2) attn_fwd_wide_kernel(AttnArgs a) 
   const int wrow0 = q0 + wave * 32;  // this wave's rows wrow0 .. wrow0 + 31
 
   const bf16_t* Q = reinterpret_cast<const bf16_t*>(a.q) + (int64_t)b * a.sb_qkv + (int64_t)h * a.sh_qkv;
-  const bf16_t* K = reinterpret_cast<const bf16_t*>(a.k) + (int64_t)b * a.sb_qkv + (int64_t)h * a.sh_qkv;
-  const bf16_t* V = reinterpret_cast<const bf16_t*>(a.v) + (int64_t)b * a.sb_qkv + (int64_t)h * a.sh_qkv;
+  const bf16_t* K = reinterpret_cast<const bf16_t*>(a.k) + (int64_t)b * a.sb_qkv + (int64_t)kv_head(a, h) * a.sh_qkv;
+  const bf16_t* V = reinterpret_cast<const bf16_t*>(a.v) + (int64_t)b * a.sb_qkv + (int64_t)kv_head(a, h) * a.sh_qkv;
 
   bf16x8 qf[RB][NS];
 #pragma unroll
@@ -564,9 +564,10 @@ __global__ void __launch_bounds__(kThreads, D == 256 ? 1 : 2) attn_dq_kernel(Att
   const int q0 = qt * kRows;
   bf16_t* scr = scr_all + wave * 16 * kScrStride;
   const int64_t boff = (int64_t)b * a.sb_qkv + (int64_t)h * a.sh_qkv;
+  const int64_t koff = (int64_t)b * a.sb_qkv + (int64_t)kv_head(a, h) * a.sh_qkv;  // K / V: the group's head
   const bf16_t* Q = reinterpret_cast<const bf16_t*>(a.q) + boff;
-  const bf16_t* K = reinterpret_cast<const bf16_t*>(a.k) + boff;
-  const bf16_t* V = reinterpret_cast<const bf16_t*>(a.v) + boff;
+  const bf16_t* K = reinterpret_cast<const bf16_t*>(a.k) + koff;
+  const bf16_t* V = reinterpret_cast<const bf16_t*>(a.v) + koff;
   const bf16_t* dO = reinterpret_cast<const bf16_t*>(a.dout) + (int64_t)b * a.sb_o + (int64_t)h * a.sh_o;
 
   constexpr int NS = D / 32, ND = D / 16;
@@ -677,9 +678,10 @@ __global__ void __launch_bounds__(kThreads, 2) attn_dq_wide_kernel(AttnArgs a) {
   const int q0 = qt * kWideRows;
   const int wrow0 = q0 + wave * 32;
   const int64_t boff = (int64_t)b * a.sb_qkv + (int64_t)h * a.sh_qkv;
+  const int64_t koff = (int64_t)b * a.sb_qkv + (int64_t)kv_head(a, h) * a.sh_qkv;  // K / V: the group's head
   const bf16_t* Q = reinterpret_cast<const bf16_t*>(a.q) + boff;
-  const bf16_t* K = reinterpret_cast<const bf16_t*>(a.k) + boff;
-  const bf16_t* V = reinterpret_cast<const bf16_t*>(a.v) + boff;
+  const bf16_t* K = reinterpret_cast<const bf16_t*>(a.k) + koff;
+  const bf16_t* V = reinterpret_cast<const bf16_t*>(a.v) + koff;
   const bf16_t* dO = reinterpret_cast<const bf16_t*>(a.dout) + (int64_t)b * a.sb_o + (int64_t)h * a.sh_o;
 
   bf16x8 qf[RB][NS], df[RB][NS];
@@ -807,9 +809,10 @@ __global__ void __launch_bounds__(kThreads, D >= 128 ? 1 : 2) attn_dkdv_kernel(A
   const int k0 = kt * kRows;
   bf16_t* scr = scr_all + wave * 16 * kScrStride;
   const int64_t boff = (int64_t)b * a.sb_qkv + (int64_t)h * a.sh_qkv;
+  const int64_t koff = (int64_t)b * a.sb_qkv + (int64_t)kv_head(a, h) * a.sh_qkv;  // K / V: the group's head
   const bf16_t* Q = reinterpret_cast<const bf16_t*>(a.q) + boff;
-  const bf16_t* K = reinterpret_cast<const bf16_t*>(a.k) + boff;
-  const bf16_t* V = reinterpret_cast<const bf16_t*>(a.v) + boff;
+  const bf16_t* K = reinterpret_cast<const bf16_t*>(a.k) + koff;
+  const bf16_t* V = reinterpret_cast<const bf16_t*>(a.v) + koff;
   const bf16_t* dO = reinterpret_cast<const bf16_t*>(a.dout) + (int64_t)b * a.sb_o + (int64_t)h * a.sh_o;
 
   constexpr int NS = D / 32, ND = D / 16;
@@ -929,13 +932,14 @@ __global__ void __launch_bounds__(kThreads, D >= 128 ? 1 : 2) attn_dkdv_kernel(A
       dk[t2] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(f1, frag_cols<D>(qimg, 16 * t2, 1, lane), dk[t2], 0, 0, 0);
     }
   }
-  bf16_t* dK = reinterpret_cast<bf16_t*>(a.dk) + boff;
-  bf16_t* dV = reinterpret_cast<bf16_t*>(a.dv) + boff;
+  const DkvDst dst = dkv_dst<0>(blockIdx.y);  // 0: AttnArgs is this kernel's first (only) parameter
+  bf16_t* dK = dst.dk;
+  bf16_t* dV = dst.dv;
 #pragma unroll
   for (int t2 = 0; t2 < ND; ++t2)
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-      const int64_t o = (int64_t)(key0 + r) * a.ld_qkv + 16 * t2 + (lane & 15);
+      const int64_t o = (int64_t)(key0 + r) * dst.ld + 16 * t2 + (lane & 15);
       dK[o] = f2bf(dk[t2][r] * a.scale);
       dV[o] = f2bf(dv[t2][r]);
     }
@@ -1027,9 +1031,10 @@ __global__ void __launch_bounds__(kThreads, 1) attn_bwd_s128_kernel(AttnArgs a) 
   const int bh = blockIdx.x;
   const int b = bh / a.H, h = bh % a.H;
   const int64_t boff = (int64_t)b * a.sb_qkv + (int64_t)h * a.sh_qkv;
+  const int64_t koff = (int64_t)b * a.sb_qkv + (int64_t)kv_head(a, h) * a.sh_qkv;  // K / V: the group's head
   const bf16_t* Q = reinterpret_cast<const bf16_t*>(a.q) + boff;
-  const bf16_t* K = reinterpret_cast<const bf16_t*>(a.k) + boff;
-  const bf16_t* V = reinterpret_cast<const bf16_t*>(a.v) + boff;
+  const bf16_t* K = reinterpret_cast<const bf16_t*>(a.k) + koff;
+  const bf16_t* V = reinterpret_cast<const bf16_t*>(a.v) + koff;
   const bf16_t* dO = reinterpret_cast<const bf16_t*>(a.dout) + (int64_t)b * a.sb_o + (int64_t)h * a.sh_o;
   constexpr int NC = D / kChunk;
 
@@ -1129,9 +1134,6 @@ __global__ void __launch_bounds__(kThreads, 1) attn_bwd_s128_kernel(AttnArgs a) 
   char* kimg = smem;
   char* qimg = smem + kChunkImg;
   char* dimg = smem + 2 * kChunkImg;
-  bf16_t* dQ = reinterpret_cast<bf16_t*>(a.dq) + boff;
-  bf16_t* dK = reinterpret_cast<bf16_t*>(a.dk) + boff;
-  bf16_t* dV = reinterpret_cast<bf16_t*>(a.dv) + boff;
   const int r0 = wave * 16;  // output rows (queries for dQ, keys for dK / dV)
   // The next chunk's K / Q / dO are loaded into registers while this chunk's
   // MFMAs run; results leave through the (then free) chunk images as 16-byte
@@ -1184,14 +1186,20 @@ __global__ void __launch_bounds__(kThreads, 1) attn_bwd_s128_kernel(AttnArgs a) 
     __syncthreads();
     {
       const int r = tid >> 3, cc = tid & 7;  // pieces tid and tid + 512: rows r and r + 64
+      // <0>: AttnArgs is this kernel's first (only) parameter
+      const DkvDst dst = dkv_dst<0>(blockIdx.x);
+      bf16_t* dK = dst.dk;
+      bf16_t* dV = dst.dv;
+      bf16_t* dQ = dq_dst<0>(blockIdx.x);
 #pragma unroll
       for (int h2 = 0; h2 < 2; ++h2) {
         const int row = r + 64 * h2;
         const int off = coff(row, cc);
         const int64_t g = (int64_t)row * a.ld_qkv + d0 + 8 * cc;
+        const int64_t gk = (int64_t)row * dst.ld + d0 + 8 * cc;
         *reinterpret_cast<uint4*>(dQ + g) = *reinterpret_cast<const uint4*>(kimg + off);
-        *reinterpret_cast<uint4*>(dK + g) = *reinterpret_cast<const uint4*>(qimg + off);
-        *reinterpret_cast<uint4*>(dV + g) = *reinterpret_cast<const uint4*>(dimg + off);
+        *reinterpret_cast<uint4*>(dK + gk) = *reinterpret_cast<const uint4*>(qimg + off);
+        *reinterpret_cast<uint4*>(dV + gk) = *reinterpret_cast<const uint4*>(dimg + off);
       }
     }
   }
@@ -1208,9 +1216,10 @@ __global__ void __launch_bounds__(kThreads, 2) attn_fwd_s128_kernel(AttnArgs a) 
   const int bh = blockIdx.x;
   const int b = bh / a.H, h = bh % a.H;
   const int64_t boff = (int64_t)b * a.sb_qkv + (int64_t)h * a.sh_qkv;
+  const int64_t koff = (int64_t)b * a.sb_qkv + (int64_t)kv_head(a, h) * a.sh_qkv;  // K / V: the group's head
   const bf16_t* Q = reinterpret_cast<const bf16_t*>(a.q) + boff;
-  const bf16_t* K = reinterpret_cast<const bf16_t*>(a.k) + boff;
-  const bf16_t* V = reinterpret_cast<const bf16_t*>(a.v) + boff;
+  const bf16_t* K = reinterpret_cast<const bf16_t*>(a.k) + koff;
+  const bf16_t* V = reinterpret_cast<const bf16_t*>(a.v) + koff;
   constexpr int NC = D / kChunk;
 
   f32x4 sacc[8];
@@ -1407,7 +1416,7 @@ void attention_set_fused_bwd(int on) { g_attn_fused_bwd = on; }
 bool attention_supported(int S, int D) { return S > 0 && S % kRows == 0 && (D == 64 || D == 128 || D == 256); }
 
 void attention_fwd(const AttnArgs& ai, hipStream_t s) {
-  AttnArgs a = ai;
+  AttnArgs a = attn_resolved(ai);
   a.threshold = dropout_threshold(a.p);
   if (a.causal) {
     if (a.D == 64) run_fwd<64, true>(a, s);
@@ -1421,7 +1430,7 @@ void attention_fwd(const AttnArgs& ai, hipStream_t s) {
 }
 
 void attention_bwd(const AttnArgs& ai, hipStream_t s) {
-  AttnArgs a = ai;
+  AttnArgs a = attn_resolved(ai);
   a.threshold = dropout_threshold(a.p);
   if (a.causal) {
     if (a.D == 64) run_bwd<64, true>(a, s);

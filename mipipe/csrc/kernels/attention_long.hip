@@ -199,9 +199,10 @@ __global__ void __launch_bounds__(kThreads, 2) attn_long_fwd_kernel(AttnArgs a) 
   const int q0w = qt * kBlockRows + wave * kWaveRows;  // this wave's queries q0w .. q0w + 63
   const bool active = q0w < a.S;
   const int64_t hoff = (int64_t)b * a.sb_qkv + (int64_t)hh * a.sh_qkv;
+  const int64_t koff = (int64_t)b * a.sb_qkv + (int64_t)kv_head(a, hh) * a.sh_qkv;  // K / V: the group's head
   const bf16_t* Q = reinterpret_cast<const bf16_t*>(a.q) + hoff;
-  const bf16_t* K = reinterpret_cast<const bf16_t*>(a.k) + hoff;
-  const bf16_t* V = reinterpret_cast<const bf16_t*>(a.v) + hoff;
+  const bf16_t* K = reinterpret_cast<const bf16_t*>(a.k) + koff;
+  const bf16_t* V = reinterpret_cast<const bf16_t*>(a.v) + koff;
   constexpr bool drop = DM != 0;
   const float pscale = drop ? 1.f / (1.f - a.p) : 1.f;
   const float sl2 = a.scale * kLog2e;
@@ -401,6 +402,7 @@ __global__ void __launch_bounds__(kThreads, 1) attn_long_dkdv_kernel(AttnArgs a)
   const int k0w = kt * kBlockRows + wave * kWaveRows;  // this wave's keys
   const bool active = k0w < a.S;
   const int64_t hoff = (int64_t)b * a.sb_qkv + (int64_t)hh * a.sh_qkv;
+  const int64_t koff = (int64_t)b * a.sb_qkv + (int64_t)kv_head(a, hh) * a.sh_qkv;  // K / V: the group's head
   const int64_t ooff = (int64_t)b * a.sb_o + (int64_t)hh * a.sh_o;
   const bf16_t* Q = reinterpret_cast<const bf16_t*>(a.q) + hoff;
   const bf16_t* dO = reinterpret_cast<const bf16_t*>(a.dout) + ooff;
@@ -417,8 +419,8 @@ __global__ void __launch_bounds__(kThreads, 1) attn_long_dkdv_kernel(AttnArgs a)
   char* vimg_w = kimg_w + kImg;
   {
     const int key = min(k0w + lane, a.S - 1);
-    const bf16_t* kr = reinterpret_cast<const bf16_t*>(a.k) + hoff + (int64_t)key * a.ld_qkv;
-    const bf16_t* vr = reinterpret_cast<const bf16_t*>(a.v) + hoff + (int64_t)key * a.ld_qkv;
+    const bf16_t* kr = reinterpret_cast<const bf16_t*>(a.k) + koff + (int64_t)key * a.ld_qkv;
+    const bf16_t* vr = reinterpret_cast<const bf16_t*>(a.v) + koff + (int64_t)key * a.ld_qkv;
 #pragma unroll
     for (int c = 0; c < 8; ++c) {
       *reinterpret_cast<u32x4*>(kimg_w + ioff(lane, c)) = *reinterpret_cast<const u32x4*>(kr + 8 * c);
@@ -551,11 +553,12 @@ __global__ void __launch_bounds__(kThreads, 1) attn_long_dkdv_kernel(AttnArgs a)
   }
   if (!active) return;
   // dK^T / dV^T tiles: register r = d (32 dt + arow(r, h)), lane = key -> 4 consecutive d per 8-byte store
+  const int64_t doff = (int64_t)b * a.sb_dkv + (int64_t)hh * a.sh_dkv;  // this QUERY head's slot
 #pragma unroll
   for (int kb = 0; kb < 2; ++kb) {
     const int key = k0w + 32 * kb + li;
-    bf16_t* dK = reinterpret_cast<bf16_t*>(a.dk) + hoff + (int64_t)key * a.ld_qkv;
-    bf16_t* dV = reinterpret_cast<bf16_t*>(a.dv) + hoff + (int64_t)key * a.ld_qkv;
+    bf16_t* dK = reinterpret_cast<bf16_t*>(a.dk) + doff + (int64_t)key * a.ld_dkv;
+    bf16_t* dV = reinterpret_cast<bf16_t*>(a.dv) + doff + (int64_t)key * a.ld_dkv;
 #pragma unroll
     for (int dt = 0; dt < 2; ++dt)
 #pragma unroll
@@ -594,6 +597,7 @@ __global__ void __launch_bounds__(kThreads8, 2) attn_long_dkdv8_kernel(AttnArgs 
   const int k0w = kt * kBlockRows + wave * 32;  // this wave's keys k0w .. k0w + 31
   const bool active = k0w < a.S;
   const int64_t hoff = (int64_t)b * a.sb_qkv + (int64_t)hh * a.sh_qkv;
+  const int64_t koff = (int64_t)b * a.sb_qkv + (int64_t)kv_head(a, hh) * a.sh_qkv;  // K / V: the group's head
   const int64_t ooff = (int64_t)b * a.sb_o + (int64_t)hh * a.sh_o;
   const bf16_t* Q = reinterpret_cast<const bf16_t*>(a.q) + hoff;
   const bf16_t* dO = reinterpret_cast<const bf16_t*>(a.dout) + ooff;
@@ -605,8 +609,8 @@ __global__ void __launch_bounds__(kThreads8, 2) attn_long_dkdv8_kernel(AttnArgs 
   char* vimg_w = kimg_w + kImg32;
   {
     const int key = min(k0w + li, a.S - 1);
-    const bf16_t* kr = reinterpret_cast<const bf16_t*>(a.k) + hoff + (int64_t)key * a.ld_qkv;
-    const bf16_t* vr = reinterpret_cast<const bf16_t*>(a.v) + hoff + (int64_t)key * a.ld_qkv;
+    const bf16_t* kr = reinterpret_cast<const bf16_t*>(a.k) + koff + (int64_t)key * a.ld_qkv;
+    const bf16_t* vr = reinterpret_cast<const bf16_t*>(a.v) + koff + (int64_t)key * a.ld_qkv;
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       const int c = 4 * h + j;
@@ -714,8 +718,9 @@ __global__ void __launch_bounds__(kThreads8, 2) attn_long_dkdv8_kernel(AttnArgs 
   if (!active) return;
   const int key = k0w + li;
   if (key >= a.S) return;
-  bf16_t* dK = reinterpret_cast<bf16_t*>(a.dk) + hoff + (int64_t)key * a.ld_qkv;
-  bf16_t* dV = reinterpret_cast<bf16_t*>(a.dv) + hoff + (int64_t)key * a.ld_qkv;
+  const int64_t doff = (int64_t)b * a.sb_dkv + (int64_t)hh * a.sh_dkv;  // this QUERY head's slot
+  bf16_t* dK = reinterpret_cast<bf16_t*>(a.dk) + doff + (int64_t)key * a.ld_dkv;
+  bf16_t* dV = reinterpret_cast<bf16_t*>(a.dv) + doff + (int64_t)key * a.ld_dkv;
 #pragma unroll
   for (int dt = 0; dt < 2; ++dt)
 #pragma unroll
@@ -747,9 +752,10 @@ __global__ void __launch_bounds__(kThreads, 2) attn_long_dq_kernel(AttnArgs a) {
   const int q0w = qt * kBlockRows + wave * kWaveRows;
   const bool active = q0w < a.S;
   const int64_t hoff = (int64_t)b * a.sb_qkv + (int64_t)hh * a.sh_qkv;
+  const int64_t koff = (int64_t)b * a.sb_qkv + (int64_t)kv_head(a, hh) * a.sh_qkv;  // K / V: the group's head
   const int64_t ooff = (int64_t)b * a.sb_o + (int64_t)hh * a.sh_o;
-  const bf16_t* K = reinterpret_cast<const bf16_t*>(a.k) + hoff;
-  const bf16_t* V = reinterpret_cast<const bf16_t*>(a.v) + hoff;
+  const bf16_t* K = reinterpret_cast<const bf16_t*>(a.k) + koff;
+  const bf16_t* V = reinterpret_cast<const bf16_t*>(a.v) + koff;
   constexpr bool drop = DROP;
   const float pscale = drop ? 1.f / (1.f - a.p) : 1.f;
   const float sl2 = a.scale * kLog2e;
@@ -918,14 +924,14 @@ void attention_long_set_fused_rng(bool on) { g_fused_rng = on; }
 bool attention_long_supported(int S, int Dh) { return Dh == D && S >= kBlockRows && S % kTile == 0; }
 
 void attention_long_fwd(const AttnArgs& ai, hipStream_t s) {
-  AttnArgs a = ai;
+  AttnArgs a = attn_resolved(ai);
   a.threshold = dropout_threshold(a.p);
   if (a.causal) run_fwd<true>(a, s);
   else run_fwd<false>(a, s);
 }
 
 void attention_long_fwd_words(const AttnArgs& ai, hipStream_t s) {
-  AttnArgs a = ai;
+  AttnArgs a = attn_resolved(ai);
   a.threshold = dropout_threshold(a.p);
   const dim3 grid(a.B * a.H, (a.S + kBlockRows - 1) / kBlockRows);
   if (a.causal) hipLaunchKernelGGL((attn_long_fwd_kernel<true, 1>), grid, dim3(kThreads), 0, s, a);
@@ -933,7 +939,7 @@ void attention_long_fwd_words(const AttnArgs& ai, hipStream_t s) {
 }
 
 void attention_long_bwd(const AttnArgs& ai, hipStream_t s) {
-  AttnArgs a = ai;
+  AttnArgs a = attn_resolved(ai);
   a.threshold = dropout_threshold(a.p);
   if (a.causal) run_bwd<true>(a, s);
   else run_bwd<false>(a, s);

@@ -114,6 +114,18 @@ void swiglu_bwd(const T* dh, const T* gu, T* dgu, int64_t rows, int F, hipStream
 template <typename T>
 void rope_packed(const T* qkv, const float* cos_t, const float* sin_t, T* out, int64_t B, int S, int H, int D, int pos0,
                  bool inverse, hipStream_t s);
+// The same on x [B, S, n_rot + n_copy, D]: the first n_rot heads of a token are rotated, the last n_copy
+// pass through (copied, or untouched when out == x).  rope_packed is (2 H, H); a grouped-query projection
+// [B, S, H + 2 Hkv, D] is (H + Hkv, Hkv).
+template <typename T>
+void rope_heads(const T* x, const float* cos_t, const float* sin_t, T* out, int64_t B, int S, int n_rot, int n_copy,
+                int D, int pos0, bool inverse, hipStream_t s);
+// Grouped-query attention backward: dkv [B, S, 2, H, D] (contiguous) holds one dK and one dV partial per
+// QUERY head; each group of H / Hkv consecutive heads is summed in fp32, rounded once and stored into the
+// K (heads [H, H + Hkv)) and V (heads [H + Hkv, H + 2 Hkv)) slots of dqkv [B, S, H + 2 Hkv, D]
+// (contiguous); the Q slots are not touched.  D % 8 == 0 (fp32: % 4), 16-byte aligned pointers.
+template <typename T>
+void gqa_reduce_dkv(const T* dkv, T* dqkv, int64_t tokens, int H, int Hkv, int D, hipStream_t s);
 
 // ------------------------------------------------------------------ elementwise
 enum Activation : int { kActNone = 0, kActRelu = 1, kActGelu = 2 };
@@ -285,7 +297,75 @@ struct AttnArgs {
   // long-sequence kernels with dropout: keep bits, one uint32 per (b*h, 32-query
   // block, key) written by the forward and read by the backward
   uint32_t* dmask = nullptr;
+  // Grouped-query attention: query head h reads K and V of head h / group (k and v hold H / group heads
+  // with q's strides).  Everything on the query side -- q, o, dout, dq, lse, delta, the Philox counters,
+  // dmask -- keeps query-head indexing.  The dK / dV kernels keep one block per QUERY head and store its
+  // partial at dk / dv + b*sb_dkv + s*ld_dkv + h*sh_dkv; 0 (group == 1) means q's strides, so dk / dv are
+  // then the gradients themselves.  With group > 1 the caller points dk / dv at a scratch of H heads and
+  // sums each group afterwards (gqa_reduce_dkv).
+  int group = 1;
+  uint32_t group_rcp = 1u << 20;  // ceil(2^20 / group): set by attn_resolved (kv_head)
+  int64_t ld_dkv = 0, sb_dkv = 0, sh_dkv = 0;
 };
+// K / V head of query head h: h / group as a scalar multiply by ceil(2^20 / group) and a shift instead of a
+// division.  Exact for every h when group == 1 (the 64-bit product is h * 2^20) and while h * group < 2^20
+// otherwise, which attn_group_ok checks for the callers (H <= 1024 always passes).
+inline bool attn_group_ok(int64_t H, int64_t group) {
+  return group >= 1 && H % group == 0 && (group == 1 || H * group < (int64_t(1) << 20));
+}
+#if defined(__HIPCC__)
+__device__ __forceinline__ int kv_head(const AttnArgs& a, int h) {
+  return (int)(((uint64_t)(uint32_t)h * a.group_rcp) >> 20);
+}
+// Where the dK / dV epilogue of block (batch * H + head) = bh stores: the two head bases and the token
+// stride.  The dK / dV kernels of attention.hip are at their scalar-register limit through the main loop
+// (100-106 SGPRs, the S = 128 backward with spills), so the epilogue reads what only it needs (dk, dv, the
+// store strides, H) from the kernel-argument segment when the loop is over instead of holding it from the
+// start.  (attention_long.hip's dK / dV kernels use 48-58 SGPRs and read a.sb_dkv ... in the plain way.)
+//
+// kArgOffset is the byte offset of the kernel's by-value AttnArgs parameter in its kernel-argument segment
+// and must be given at every call: 0 for a kernel whose FIRST parameter is the AttnArgs (explicit arguments
+// start the segment, in declaration order).  A kernel with anything before its AttnArgs must pass that
+// parameter's offset, or these helpers read another argument's bytes.
+struct DkvDst {
+  bf16_t* dk;
+  bf16_t* dv;
+  int64_t ld;
+};
+template <int kArgOffset>
+__device__ __forceinline__ const __attribute__((address_space(4))) AttnArgs* attn_args_late() {
+  static_assert(kArgOffset >= 0 && kArgOffset % alignof(AttnArgs) == 0, "offset of an AttnArgs kernel parameter");
+  typedef const __attribute__((address_space(4))) char* BytePtr;
+  typedef const __attribute__((address_space(4))) AttnArgs* ArgPtr;
+  ArgPtr ap = (ArgPtr)((BytePtr)__builtin_amdgcn_kernarg_segment_ptr() + kArgOffset);
+  asm volatile("" : "+s"(ap));  // opaque from here on: loads through ap cannot move above this point
+  return ap;
+}
+template <int kArgOffset>
+__device__ __forceinline__ DkvDst dkv_dst(int bh) {
+  const auto* ap = attn_args_late<kArgOffset>();
+  const int H = ap->H, b = bh / H, h = bh - b * H;
+  const int64_t off = (int64_t)b * ap->sb_dkv + (int64_t)h * ap->sh_dkv;
+  return DkvDst{reinterpret_cast<bf16_t*>(ap->dk) + off, reinterpret_cast<bf16_t*>(ap->dv) + off, ap->ld_dkv};
+}
+// The dQ base of block bh, read late in the same way.
+template <int kArgOffset>
+__device__ __forceinline__ bf16_t* dq_dst(int bh) {
+  const auto* ap = attn_args_late<kArgOffset>();
+  const int H = ap->H, b = bh / H, h = bh - b * H;
+  return reinterpret_cast<bf16_t*>(ap->dq) + (int64_t)b * ap->sb_qkv + (int64_t)h * ap->sh_qkv;
+}
+#endif
+// Resolves the dK / dV store strides' default (q's) and checks the group; every attention launcher calls it.
+inline AttnArgs attn_resolved(const AttnArgs& ai) {
+  AttnArgs a = ai;
+  if (a.group < 1) a.group = 1;
+  a.group_rcp = ((1u << 20) + (uint32_t)a.group - 1) / (uint32_t)a.group;
+  if (a.ld_dkv == 0 && a.sb_dkv == 0 && a.sh_dkv == 0) {
+    a.ld_dkv = a.ld_qkv; a.sb_dkv = a.sb_qkv; a.sh_dkv = a.sh_qkv;
+  }
+  return a;
+}
 bool attention_supported(int S, int D);
 // S == 128 backward: fused one-pass kernel (1, default) or delta + dK/dV + dQ kernels (0).
 void attention_set_fused_bwd(int on);

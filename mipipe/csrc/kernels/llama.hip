@@ -12,7 +12,12 @@
 //          qkv [B, S, 3, H, D] at position pos0 + s; cos / sin come from fp32
 //          host-built tables [>= pos0 + S, D/2] (no device trigonometry); V is
 //          copied, or untouched when out aliases qkv.  The backward is the
-//          same kernel with sin negated (`inverse`) on dqkv.
+//          same kernel with sin negated (`inverse`) on dqkv.  The kernel takes
+//          "rotate the first n_rot heads of a token, pass the last n_copy
+//          through": (2H, H) is the layout above, (H + Hkv, Hkv) the
+//          grouped-query projection [B, S, H + 2 Hkv, D].
+//   GQA dK/dV reduce:  sums the per-query-head partials of each K/V head's
+//          group into the packed dqkv (gqa_reduce_dkv_kernel).
 #include "common.h"
 #include "kernels.h"
 
@@ -88,27 +93,26 @@ __global__ void __launch_bounds__(kThreads) swiglu_kernel(const T* __restrict__ 
   }
 }
 
-// Items per token: H * D / 16 rotations of Q, as many of K (8 pairs each:
-// elements i .. i + 7 and i + D/2 .. i + D/2 + 7 of one head), then -- only
-// when V is copied -- H * D / 8 vectors of V.
+// Items per token: n_rot * D / 16 rotations (8 pairs each: elements i .. i + 7
+// and i + D/2 .. i + D/2 + 7 of one of the first n_rot heads), then -- only when
+// the rest is copied -- n_copy * D / 8 vectors of the last n_copy heads.
 template <typename T>
 __global__ void __launch_bounds__(kThreads) rope_kernel(const T* qkv, const float* __restrict__ cos_t,
                                                         const float* __restrict__ sin_t, T* out, int64_t tokens, int S,
-                                                        int H, int D, int pos0, float sign, int copy_v) {
+                                                        int n_rot, int n_copy, int D, int pos0, float sign, int copy_v) {
   const int half = D >> 1;
   const int hvec = half >> 3;        // rotation items per head
-  const int rot = H * hvec;          // per Q (and per K) of one token
-  const int per_tok = 2 * rot * (copy_v ? 2 : 1);
+  const int rot = n_rot * hvec;      // rotation items per token
+  const int per_tok = rot + (copy_v ? n_copy * (D >> 3) : 0);
   const int64_t nitems = tokens * per_tok;
   const int64_t stride = (int64_t)gridDim.x * kThreads;
-  const int64_t tok_elems = (int64_t)3 * H * D;
+  const int64_t tok_elems = (int64_t)(n_rot + n_copy) * D;
   for (int64_t t = blockIdx.x * (int64_t)kThreads + threadIdx.x; t < nitems; t += stride) {
     const int64_t tok = t / per_tok;
     const int j = (int)(t - tok * per_tok);
-    if (j < 2 * rot) {
-      const int which = j / rot, r = j - which * rot;
-      const int h = r / hvec, i = (r - h * hvec) * 8;
-      const int64_t e = tok * tok_elems + ((int64_t)which * H + h) * D + i;
+    if (j < rot) {
+      const int h = j / hvec, i = (j - h * hvec) * 8;
+      const int64_t e = tok * tok_elems + (int64_t)h * D + i;
       const int64_t te = (int64_t)(pos0 + (int)(tok % S)) * half + i;
       float a[8], b[8], c[8], s[8], oa[8], ob[8];
       Io<T>::load8(qkv + e, a);
@@ -124,7 +128,7 @@ __global__ void __launch_bounds__(kThreads) rope_kernel(const T* qkv, const floa
       Io<T>::store8(out + e, oa);
       Io<T>::store8(out + e + half, ob);
     } else {
-      const int64_t e = tok * tok_elems + (int64_t)2 * H * D + (int64_t)(j - 2 * rot) * 8;
+      const int64_t e = tok * tok_elems + (int64_t)n_rot * D + (int64_t)(j - rot) * 8;
       if (sizeof(T) == 2) {
         *reinterpret_cast<u16x8*>(out + e) = *reinterpret_cast<const u16x8*>(qkv + e);
       } else {
@@ -135,6 +139,45 @@ __global__ void __launch_bounds__(kThreads) rope_kernel(const T* qkv, const floa
         o[1] = v1;
       }
     }
+  }
+}
+
+// Grouped-query attention: the dK / dV kernels leave one partial per QUERY head
+// in dkv [tokens, 2, H, D]; item (token, which, kv head, 8 features) adds the
+// G = H / Hkv partials of its group in fp32 (in head order), rounds once and
+// stores into head H + which * Hkv + kv of dqkv [tokens, H + 2 Hkv, D].  The Q
+// heads of dqkv (the dQ kernel's output) are not touched.  Two partials are in
+// flight per thread; 64-bit item and element indices.
+template <typename T>
+__global__ void __launch_bounds__(kThreads) gqa_reduce_dkv_kernel(const T* __restrict__ dkv, T* __restrict__ dqkv,
+                                                                  int64_t tokens, int H, int Hkv, int D) {
+  const int G = H / Hkv;
+  const int dvec = D >> 3;
+  const int per_tok = 2 * Hkv * dvec;
+  const int64_t nitems = tokens * per_tok;
+  const int64_t stride = (int64_t)gridDim.x * kThreads;
+  const int64_t src_tok = (int64_t)2 * H * D, dst_tok = (int64_t)(H + 2 * Hkv) * D;
+  for (int64_t t = blockIdx.x * (int64_t)kThreads + threadIdx.x; t < nitems; t += stride) {
+    const int64_t tok = t / per_tok;
+    const int j = (int)(t - tok * per_tok);
+    const int hk = j / dvec, i = (j - hk * dvec) * 8;  // hk = which * Hkv + kv head
+    const int which = hk / Hkv, kv = hk - which * Hkv;
+    const T* src = dkv + tok * src_tok + ((int64_t)which * H + (int64_t)kv * G) * D + i;
+    float acc[8], x[8], y[8];
+    Io<T>::load8(src, acc);
+    int g = 1;
+    for (; g + 1 < G; g += 2) {
+      Io<T>::load8(src + (int64_t)g * D, x);
+      Io<T>::load8(src + (int64_t)(g + 1) * D, y);
+#pragma unroll
+      for (int k = 0; k < 8; ++k) acc[k] = (acc[k] + x[k]) + y[k];
+    }
+    if (g < G) {
+      Io<T>::load8(src + (int64_t)g * D, x);
+#pragma unroll
+      for (int k = 0; k < 8; ++k) acc[k] += x[k];
+    }
+    Io<T>::store8(dqkv + tok * dst_tok + (int64_t)(H + hk) * D + i, acc);
   }
 }
 
@@ -157,13 +200,27 @@ void swiglu_bwd(const T* dh, const T* gu, T* dgu, int64_t rows, int F, hipStream
 }
 
 template <typename T>
+void rope_heads(const T* x, const float* cos_t, const float* sin_t, T* out, int64_t B, int S, int n_rot, int n_copy,
+                int D, int pos0, bool inverse, hipStream_t s) {
+  const bool copy_v = out != x;
+  const int64_t nitems = B * S * ((int64_t)n_rot * (D / 16) + (copy_v ? (int64_t)n_copy * (D / 8) : 0));
+  if (nitems == 0) return;
+  hipLaunchKernelGGL((rope_kernel<T>), dim3((unsigned)grid_for(nitems)), dim3(kThreads), 0, s, x, cos_t, sin_t, out,
+                     B * S, S, n_rot, n_copy, D, pos0, inverse ? -1.f : 1.f, copy_v ? 1 : 0);
+}
+
+template <typename T>
 void rope_packed(const T* qkv, const float* cos_t, const float* sin_t, T* out, int64_t B, int S, int H, int D, int pos0,
                  bool inverse, hipStream_t s) {
-  const bool copy_v = out != qkv;
-  const int64_t nitems = B * S * (int64_t)(2 * H * (D / 16)) * (copy_v ? 2 : 1);
+  rope_heads<T>(qkv, cos_t, sin_t, out, B, S, 2 * H, H, D, pos0, inverse, s);
+}
+
+template <typename T>
+void gqa_reduce_dkv(const T* dkv, T* dqkv, int64_t tokens, int H, int Hkv, int D, hipStream_t s) {
+  const int64_t nitems = tokens * 2 * Hkv * (D / 8);
   if (nitems == 0) return;
-  hipLaunchKernelGGL((rope_kernel<T>), dim3((unsigned)grid_for(nitems)), dim3(kThreads), 0, s, qkv, cos_t, sin_t, out,
-                     B * S, S, H, D, pos0, inverse ? -1.f : 1.f, copy_v ? 1 : 0);
+  hipLaunchKernelGGL((gqa_reduce_dkv_kernel<T>), dim3((unsigned)grid_for(nitems)), dim3(kThreads), 0, s, dkv, dqkv,
+                     tokens, H, Hkv, D);
 }
 
 template void swiglu_fwd<float>(const float*, float*, int64_t, int, hipStream_t);
@@ -172,5 +229,9 @@ template void swiglu_bwd<float>(const float*, const float*, float*, int64_t, int
 template void swiglu_bwd<bf16_t>(const bf16_t*, const bf16_t*, bf16_t*, int64_t, int, hipStream_t);
 template void rope_packed<float>(const float*, const float*, const float*, float*, int64_t, int, int, int, int, bool, hipStream_t);
 template void rope_packed<bf16_t>(const bf16_t*, const float*, const float*, bf16_t*, int64_t, int, int, int, int, bool, hipStream_t);
+template void rope_heads<float>(const float*, const float*, const float*, float*, int64_t, int, int, int, int, int, bool, hipStream_t);
+template void rope_heads<bf16_t>(const bf16_t*, const float*, const float*, bf16_t*, int64_t, int, int, int, int, int, bool, hipStream_t);
+template void gqa_reduce_dkv<float>(const float*, float*, int64_t, int, int, int, hipStream_t);
+template void gqa_reduce_dkv<bf16_t>(const bf16_t*, bf16_t*, int64_t, int, int, int, hipStream_t);
 
 }  // namespace mipipe

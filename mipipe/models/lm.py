@@ -206,6 +206,12 @@ class LMConfig:
     rope: bool = False             # rotary position embeddings on Q and K
     rope_base: float = 10000.0
     positions: Optional[str] = None  # Encoder positions; None: "learned" if learned_positions else "sinusoidal"
+    n_kv_heads: Optional[int] = None  # grouped-query attention: K/V heads (a divisor of nhead); None = nhead
+
+    def qkv_dim(self) -> int:
+        """Width of the QKV projection: ``(H + 2 Hkv) D`` (``3 d_model`` without grouped-query attention)."""
+        hkv = self.nhead if self.n_kv_heads is None else self.n_kv_heads
+        return (self.nhead + 2 * hkv) * (self.d_model // self.nhead)
 
     def encoder_positions(self) -> str:
         return self.positions if self.positions is not None else ("learned" if self.learned_positions else "sinusoidal")
@@ -217,7 +223,8 @@ class LMConfig:
         f1 = 2 * f if self.activation == "swiglu" else f   # the gated first GEMM
         nb = 1 if self.bias else 0
         norm = e * (2 if self.norm == "layer" else 1)
-        layer = 4 * e * e + 2 * norm + f1 * e + e * f + nb * (4 * e + f1 + e)
+        qkv = self.qkv_dim()
+        layer = (qkv + e) * e + 2 * norm + f1 * e + e * f + nb * (qkv + e + f1 + e)
         total = self.num_layers * layer + v * e
         if self.encoder_positions() == "learned":
             total += max(self.seq_len, 1024) * e
@@ -246,11 +253,21 @@ CONFIGS = {
     "llama_tiny": LMConfig("llama_tiny", 2, 256, 4, 512, 1000, 64, dropout=0.0, activation="swiglu",
                            norm_first=True, causal=True, scale_embedding=False, act_dropout=0.0, norm="rms",
                            bias=False, rope=True, positions="none", notes="tiny LLaMA-style model for tests"),
-    # LLaMA-2 7B: full multi-head attention (32 query = 32 key/value heads), so no GQA is needed.
+    # llama_tiny with grouped-query attention: 4 query heads share 2 K/V heads (head dim 64).
+    "llama_gqa_tiny": LMConfig("llama_gqa_tiny", 2, 256, 4, 512, 1000, 64, dropout=0.0, activation="swiglu",
+                               norm_first=True, causal=True, scale_embedding=False, act_dropout=0.0, norm="rms",
+                               bias=False, rope=True, positions="none", n_kv_heads=2,
+                               notes="tiny LLaMA-style model with grouped-query attention for tests"),
+    # LLaMA-2 7B: full multi-head attention (32 query = 32 key/value heads).
     "llama2_7b": LMConfig("llama2_7b", 32, 4096, 32, 11008, 32000, 4096, dropout=0.0, activation="swiglu",
                           norm_first=True, causal=True, scale_embedding=False, act_dropout=0.0, norm="rms",
                           bias=False, rope=True, positions="none",
                           notes="LLaMA-2 7B's block; the decoder keeps its (zero-initialised) bias"),
+    # LLaMA-3 8B: 32 query heads over 8 K/V heads (groups of 4), a 128,256-token vocabulary, rope base 500,000.
+    "llama3_8b": LMConfig("llama3_8b", 32, 4096, 32, 14336, 128256, 8192, dropout=0.0, activation="swiglu",
+                          norm_first=True, causal=True, scale_embedding=False, act_dropout=0.0, norm="rms",
+                          bias=False, rope=True, rope_base=500000.0, positions="none", n_kv_heads=8,
+                          notes="LLaMA-3 8B's block; the decoder is untied and keeps its (zero-initialised) bias"),
 }
 
 
@@ -263,7 +280,7 @@ def build_lm_blocks(cfg: LMConfig, *, device=None, dtype=None) -> List[nn.Module
     ]
     blocks += transformer_blocks(cfg.num_layers, cfg.d_model, cfg.nhead, cfg.dim_feedforward, cfg.dropout,
                                  cfg.activation, norm_first=cfg.norm_first, causal=cfg.causal, norm=cfg.norm,
-                                 bias=cfg.bias, rope=cfg.rope, rope_base=cfg.rope_base,
+                                 bias=cfg.bias, rope=cfg.rope, rope_base=cfg.rope_base, n_kv_heads=cfg.n_kv_heads,
                                  device=device, dtype=dtype)
     if cfg.act_dropout is not None:
         for b in blocks:

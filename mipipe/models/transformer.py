@@ -24,7 +24,11 @@ the behaviour above): ``norm="rms"`` (RMSNorm, no norm bias), ``bias=False`` (no
 bias parameters; the linears get ``None``), ``rope=True`` (rotary positions on
 Q and K) and ``activation="swiglu"`` (``linear1_weight`` is ``[2F, E]``: rows
 ``[0, F)`` the gate projection, rows ``[F, 2F)`` the up projection; the halves
-still exchange an ``F``-wide ``h``).
+still exchange an ``F``-wide ``h``).  ``n_kv_heads=Hkv`` (a divisor of ``nhead``;
+``None`` means ``nhead``) is grouped-query attention: ``in_proj_weight`` is
+``[(H + 2 Hkv) D, E]`` -- rows of the ``H`` Q heads, then of the ``Hkv`` K heads,
+then of the ``Hkv`` V heads -- and query head ``h`` attends with K/V head
+``h // (H / Hkv)`` (``ops.attention_gqa_packed``).
 """
 from __future__ import annotations
 
@@ -122,16 +126,21 @@ class AttentionCore(nn.Module):
 
     def __init__(self, d_model: int, nhead: int, dropout: float, *, norm_first: bool, causal: bool,
                  layer_norm_eps: float, norm: str = "layer", bias: bool = True, rope: bool = False,
-                 rope_base: float = 10000.0, device=None, dtype=None) -> None:
+                 rope_base: float = 10000.0, n_kv_heads: Optional[int] = None, device=None, dtype=None) -> None:
         super().__init__()
         fk = {"device": device, "dtype": dtype}
         self.d_model, self.nhead, self.head_dim = d_model, nhead, d_model // nhead
+        self.n_kv_heads = nhead if n_kv_heads is None else int(n_kv_heads)
+        if self.n_kv_heads <= 0 or nhead % self.n_kv_heads != 0:
+            raise ValueError(f"n_kv_heads must divide nhead, got nhead={nhead}, n_kv_heads={n_kv_heads}")
+        # width of the QKV projection: H Q heads, then Hkv K heads, then Hkv V heads (3 * d_model for Hkv == H)
+        self.qkv_dim = (nhead + 2 * self.n_kv_heads) * self.head_dim
         self.dropout, self.norm_first, self.causal, self.eps = dropout, norm_first, causal, layer_norm_eps
         self.norm, self.rope, self.rope_base = norm, rope, rope_base
         if rope and self.head_dim % 2 != 0:  # (the HIP kernel wants a multiple of 16 and says so itself)
             raise ValueError(f"rope needs an even head dim, got {self.head_dim}")
-        self.in_proj_weight = mark_gemm_weight(nn.Parameter(torch.empty(3 * d_model, d_model, **fk)))
-        self.in_proj_bias = nn.Parameter(torch.empty(3 * d_model, **fk)) if bias else None
+        self.in_proj_weight = mark_gemm_weight(nn.Parameter(torch.empty(self.qkv_dim, d_model, **fk)))
+        self.in_proj_bias = nn.Parameter(torch.empty(self.qkv_dim, **fk)) if bias else None
         if norm_first:
             _init_norm(self, d_model, norm, fk)
         if rope:
@@ -180,6 +189,18 @@ class AttentionCore(nn.Module):
             qkv = ops.linear(x, self.in_proj_weight, self.in_proj_bias)
         # The projection output viewed as [B, S, 3, H, D] feeds the kernel in
         # place; its output [B, S, H, D] is already [B, S, E] -- no transposes.
+        Hkv = self.n_kv_heads
+        if Hkv != H:
+            # grouped-query attention: [B, S, H + 2 Hkv, D], the K/V heads read in place by every query head
+            # of their group
+            if self.rope:
+                cos, sin = self._rope_tables(S, qkv.device)
+                qkv4 = ops.rope_projection(qkv, cos, sin, H, n_kv_heads=Hkv)
+            else:
+                qkv4 = qkv.view(B, S, H + 2 * Hkv, D)
+            o = ops.attention_gqa_packed(qkv4, Hkv, causal=self.causal, dropout_p=self.dropout,
+                                         training=self.training)
+            return o.reshape(B, S, E), xr
         if self.rope:
             # Q and K rotated: in the projection's own output where no graph is recorded, else into a new tensor
             cos, sin = self._rope_tables(S, qkv.device)
@@ -191,7 +212,7 @@ class AttentionCore(nn.Module):
 
     def flops_per_token(self, seq_len: int) -> float:
         e = self.d_model
-        return 2 * 3 * e * e + 4 * seq_len * e * (0.5 if self.causal else 1.0)
+        return 2 * self.qkv_dim * e + 4 * seq_len * e * (0.5 if self.causal else 1.0)
 
 
 class AttentionOutput(nn.Module):
@@ -237,13 +258,14 @@ class SelfAttentionBlock(nn.Module):
 
     def __init__(self, d_model: int, nhead: int, dropout: float = 0.1, *, norm_first: bool = False,
                  causal: bool = False, layer_norm_eps: float = 1e-5, norm: str = "layer", bias: bool = True,
-                 rope: bool = False, rope_base: float = 10000.0, device=None, dtype=None) -> None:
+                 rope: bool = False, rope_base: float = 10000.0, n_kv_heads: Optional[int] = None,
+                 device=None, dtype=None) -> None:
         super().__init__()
         if d_model % nhead != 0:
             raise ValueError("d_model must be divisible by nhead")
         self.core = AttentionCore(d_model, nhead, dropout, norm_first=norm_first, causal=causal,
                                   layer_norm_eps=layer_norm_eps, norm=norm, bias=bias, rope=rope,
-                                  rope_base=rope_base, device=device, dtype=dtype)
+                                  rope_base=rope_base, n_kv_heads=n_kv_heads, device=device, dtype=dtype)
         self.out = AttentionOutput(d_model, dropout, norm_first=norm_first, layer_norm_eps=layer_norm_eps,
                                    norm=norm, bias=bias, device=device, dtype=dtype)
 
@@ -526,11 +548,12 @@ class TransformerEncoderLayer(nn.Sequential):
         bias: bool = True,
         rope: bool = False,
         rope_base: float = 10000.0,
+        n_kv_heads: Optional[int] = None,
     ) -> None:
         super().__init__(
             SelfAttentionBlock(d_model, nhead, dropout, norm_first=norm_first, causal=causal,
                                layer_norm_eps=layer_norm_eps, norm=norm, bias=bias, rope=rope, rope_base=rope_base,
-                               device=device, dtype=dtype),
+                               n_kv_heads=n_kv_heads, device=device, dtype=dtype),
             FeedForwardBlock(d_model, dim_feedforward, dropout, activation, norm_first=norm_first,
                              layer_norm_eps=layer_norm_eps, norm=norm, bias=bias, device=device, dtype=dtype),
         )
@@ -539,6 +562,9 @@ class TransformerEncoderLayer(nn.Sequential):
     def load_from_torch(self, layer: nn.TransformerEncoderLayer) -> "TransformerEncoderLayer":
         """Copies weights from ``nn.TransformerEncoderLayer``."""
         attn, ff = self[0], self[1]
+        if attn.core.n_kv_heads != attn.core.nhead:
+            raise ValueError("load_from_torch: nn.TransformerEncoderLayer has no grouped-query attention "
+                             f"(this layer has {attn.core.n_kv_heads} K/V heads for {attn.core.nhead} query heads)")
         attn.core.in_proj_weight.copy_(layer.self_attn.in_proj_weight)
         attn.core.in_proj_bias.copy_(layer.self_attn.in_proj_bias)
         attn.out.out_proj_weight.copy_(layer.self_attn.out_proj.weight)
@@ -570,6 +596,7 @@ def transformer_blocks(
     bias: bool = True,
     rope: bool = False,
     rope_base: float = 10000.0,
+    n_kv_heads: Optional[int] = None,
     device=None,
     dtype=None,
 ) -> List[nn.Module]:
@@ -578,7 +605,7 @@ def transformer_blocks(
     for _ in range(num_layers):
         layer = TransformerEncoderLayer(d_model, nhead, dim_feedforward, dropout, activation,
                                         norm_first=norm_first, causal=causal, norm=norm, bias=bias, rope=rope,
-                                        rope_base=rope_base, device=device, dtype=dtype)
+                                        rope_base=rope_base, n_kv_heads=n_kv_heads, device=device, dtype=dtype)
         blocks.extend(layer.children())
     return blocks
 

@@ -8,10 +8,10 @@ a missing extension raises (``mipipe._native_loader.kernels``).
 from .layernorm import add_dropout_layer_norm, layer_norm_fanout, layer_norm_reference
 from .rmsnorm import add_dropout_rms_norm, rms_norm_fanout, rms_norm_reference
 from .linear import deferred_wgrad, flush_wgrad, linear, linear_fanout, linear_residual
-from .attention import attention, attention_packed, attention_reference
+from .attention import attention, attention_gqa_packed, attention_packed, attention_reference
 from .activation import bias_act_dropout
 from .swiglu import swiglu, swiglu_reference
-from .rope import rope_packed, rope_projection, rope_reference, rope_tables
+from .rope import rope_heads, rope_packed, rope_projection, rope_reference, rope_tables
 from .loss import cross_entropy
 from .embedding import embed_scale_posenc_dropout
 
@@ -29,6 +29,7 @@ __all__ = [
     "flush_wgrad",
     "attention",
     "attention_packed",
+    "attention_gqa_packed",
     "attention_reference",
     "bias_act_dropout",
     "swiglu",
@@ -36,6 +37,7 @@ __all__ = [
     "rope_tables",
     "rope_packed",
     "rope_projection",
+    "rope_heads",
     "rope_reference",
     "cross_entropy",
     "embed_scale_posenc_dropout",

@@ -1,13 +1,22 @@
 """Scaled dot-product attention on the HIP flash-attention kernels
 (csrc/kernels/attention.hip).
 
-Two entry points:
+Three entry points:
 
 * :func:`attention_packed` -- ``qkv [B, S, 3, H, D]`` (the QKV projection output
   viewed in place) -> ``o [B, S, H, D]``.  No transposes: the kernels read Q, K
   and V with strides and the backward writes one packed ``dqkv`` gradient.
+* :func:`attention_gqa_packed` -- grouped-query attention on ``qkv [B, S, H +
+  2 Hkv, D]``: heads ``[0, H)`` are Q, ``[H, H + Hkv)`` K and ``[H + Hkv, H + 2
+  Hkv)`` V; query head ``h`` attends with K/V head ``h // (H / Hkv)``.  With
+  ``Hkv == H`` this is ``attention_packed``'s layout byte for byte.  On the
+  bf16 kernels the K/V heads are read in place (no repeated copy) and the
+  backward sums each group's dK / dV partials in one extra kernel; everything
+  else (fp32, the CPU, the padded shapes of ``_run_shape``) repeats the K/V
+  heads into ``[B, S, 3, H, D]`` and calls :func:`attention_packed`, autograd
+  summing the group.
 * :func:`attention` -- the usual ``q, k, v [B, H, S, D]`` API (views are
-  permuted, not copied).
+  permuted, not copied); ``k`` and ``v`` may have ``Hkv | H`` heads (repeated).
 
 Causal masking and attention dropout are supported; the dropout mask is
 regenerated from Philox (seed, offset) in backward, so checkpoint recompute
@@ -41,7 +50,7 @@ from torch import Tensor
 from ..checkpoint import is_recomputing, recompute_expected
 from ._util import kernels_for
 
-__all__ = ["attention", "attention_packed", "attention_reference", "clear_keep_words"]
+__all__ = ["attention", "attention_packed", "attention_gqa_packed", "attention_reference", "clear_keep_words"]
 
 
 def attention_reference(q: Tensor, k: Tensor, v: Tensor, causal: bool, p: float, scale: Optional[float] = None) -> Tensor:
@@ -172,6 +181,36 @@ class _Attention(torch.autograd.Function):
         return dq, dk, dv, None, None, None, None
 
 
+class _AttentionGqaPacked(torch.autograd.Function):
+    """``qkv [B, S, H + 2 Hkv, D]`` (contiguous, bf16) in, ``o [B, S, H, D]`` out.  Q, K and V are head
+    slices of the one buffer (same strides, fewer K/V heads); the backward writes dQ and the group-summed
+    dK / dV into one packed ``dqkv`` of the same layout (the binding owns the per-query-head scratch)."""
+
+    @staticmethod
+    def forward(ctx, qkv, n_kv, causal, p, scale):  # type: ignore[override]
+        kern = kernels_for(qkv)
+        H = qkv.shape[2] - 2 * n_kv
+        q, k, v = qkv[:, :, :H], qkv[:, :, H:H + n_kv], qkv[:, :, H + n_kv:]
+        o, lse, seed, offset, bits = _attention_fwd(kern, q, k, v, causal, p, scale, 0)
+        ctx.save_for_backward(qkv, o, lse, bits)
+        ctx.n_kv, ctx.causal, ctx.p, ctx.scale, ctx.seed, ctx.offset = n_kv, causal, p, scale, seed, offset
+        return o
+
+    @staticmethod
+    def backward(ctx, do):  # type: ignore[override]
+        qkv, o, lse, bits = ctx.saved_tensors
+        kern = kernels_for(do)
+        if do.stride() != o.stride():
+            do = do.contiguous()
+        n_kv = ctx.n_kv
+        H = qkv.shape[2] - 2 * n_kv
+        dqkv = torch.empty_like(qkv)
+        kern.attention_bwd(do, qkv[:, :, :H], qkv[:, :, H:H + n_kv], qkv[:, :, H + n_kv:], o, lse, ctx.causal, ctx.p,
+                           ctx.scale, ctx.seed, ctx.offset, dqkv[:, :, :H], dqkv[:, :, H:H + n_kv],
+                           dqkv[:, :, H + n_kv:], bits if bits.numel() else None, 0)
+        return dqkv, None, None, None, None
+
+
 _noted = set()
 
 
@@ -266,11 +305,50 @@ def attention_packed(qkv: Tensor, causal: bool = False, dropout_p: float = 0.0, 
     return o.transpose(1, 2)
 
 
+def _expand_kv(qkv: Tensor, n_kv: int) -> Tensor:
+    """``[B, S, H + 2 Hkv, D]`` -> ``[B, S, 3, H, D]`` with every K/V head repeated over its group
+    (differentiable: the backward sums the group)."""
+    B, S, heads, D = qkv.shape
+    H = heads - 2 * n_kv
+    g = H // n_kv
+    q = qkv[:, :, :H]
+    k = qkv[:, :, H:H + n_kv].repeat_interleave(g, dim=2)
+    v = qkv[:, :, H + n_kv:].repeat_interleave(g, dim=2)
+    return torch.stack((q, k, v), dim=2)
+
+
+def attention_gqa_packed(qkv: Tensor, n_kv_heads: int, causal: bool = False, dropout_p: float = 0.0,
+                         training: bool = True, scale: Optional[float] = None) -> Tensor:
+    """``qkv [B, S, H + 2 Hkv, D]`` -> ``o [B, S, H, D]`` (grouped-query attention, ``Hkv = n_kv_heads``)."""
+    if qkv.dim() != 4:
+        raise ValueError(f"attention_gqa_packed: qkv must be [B, S, H + 2 Hkv, D], got {tuple(qkv.shape)}")
+    B, S, heads, D = qkv.shape
+    n_kv = int(n_kv_heads)
+    H = heads - 2 * n_kv
+    if n_kv <= 0 or H <= 0 or H % n_kv != 0:
+        raise ValueError(f"attention_gqa_packed: {heads} packed heads do not split into H + 2 * {n_kv} with "
+                         f"{n_kv} dividing H")
+    if n_kv == H:  # plain multi-head attention: the same bytes as [B, S, 3, H, D]
+        return attention_packed(qkv.reshape(B, S, 3, H, D), causal, dropout_p, training, scale)
+    if qkv.is_cuda and qkv.dtype == torch.bfloat16 and _gpu_ok(qkv, S, D):
+        p = float(dropout_p) if training else 0.0
+        scale = float(scale) if scale is not None else 1.0 / math.sqrt(D)
+        return _AttentionGqaPacked.apply(qkv.contiguous(), n_kv, bool(causal), p, scale)
+    return attention_packed(_expand_kv(qkv, n_kv), causal, dropout_p, training, scale)
+
+
 def attention(
     q: Tensor, k: Tensor, v: Tensor, causal: bool = False, dropout_p: float = 0.0, training: bool = True,
     scale: Optional[float] = None,
 ) -> Tensor:
-    """``q, k, v [B, H, S, D]`` -> ``[B, H, S, D]``."""
+    """``q, k, v [B, H, S, D]`` -> ``[B, H, S, D]``.  ``k`` and ``v`` may have fewer heads, ``Hkv | H``
+    (grouped-query attention): separate tensors do not share q's strides, so their heads are repeated
+    (autograd sums each group's gradient)."""
+    if k.shape[1] != q.shape[1]:
+        if k.shape[1] != v.shape[1] or k.shape[1] <= 0 or q.shape[1] % k.shape[1] != 0:
+            raise ValueError(f"attention: {k.shape[1]} / {v.shape[1]} K/V heads do not divide {q.shape[1]} query heads")
+        g = q.shape[1] // k.shape[1]
+        k, v = k.repeat_interleave(g, dim=1), v.repeat_interleave(g, dim=1)
     p = float(dropout_p) if training else 0.0
     scale = float(scale) if scale is not None else 1.0 / math.sqrt(q.shape[-1])
     if not q.is_cuda:

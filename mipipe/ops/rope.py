@@ -11,17 +11,23 @@ are built once on the host in fp64 and stored in fp32 (:func:`rope_tables`);
 the kernel does no trigonometry.  A rotation is orthogonal, so the backward is
 the inverse rotation (``sin`` negated) of the incoming gradient -- the same
 kernel.
+
+The kernel itself takes "rotate the first ``n_rot`` heads of a token, pass the
+last ``n_copy`` through" on ``[B, S, n_rot + n_copy, D]``: the layout above is
+``(2H, H)``, and a grouped-query projection ``[B, S, H + 2 Hkv, D]`` (Q heads,
+then ``Hkv`` K heads, then ``Hkv`` V heads) is ``(H + Hkv, Hkv)``
+(:func:`rope_heads`, ``rope_projection(..., n_kv_heads=Hkv)``).
 """
 from __future__ import annotations
 
-from typing import Tuple
+from typing import Optional, Tuple
 
 import torch
 from torch import Tensor
 
 from ._util import kernels_for
 
-__all__ = ["rope_tables", "rope_packed", "rope_reference"]
+__all__ = ["rope_tables", "rope_packed", "rope_heads", "rope_projection", "rope_reference"]
 
 
 def rope_tables(max_len: int, head_dim: int, base: float = 10000.0, device=None) -> Tuple[Tensor, Tensor]:
@@ -49,6 +55,46 @@ def rope_reference(qkv: Tensor, cos: Tensor, sin: Tensor, pos0: int = 0, inverse
     a, b = qk[..., :half], qk[..., half:]
     rot = torch.cat((a * c - b * s, b * c + a * s), dim=-1).to(qkv.dtype)
     return torch.cat((rot, qkv[:, :, 2:]), dim=2)
+
+
+def rope_heads_reference(x: Tensor, cos: Tensor, sin: Tensor, n_rot: int, pos0: int = 0,
+                         inverse: bool = False) -> Tensor:
+    """Eager rotation of the first ``n_rot`` heads of ``x [B, S, heads, D]`` (CPU path and test oracle);
+    the arithmetic runs in the wider of x's and the tables' dtypes."""
+    B, S, heads, D = x.shape
+    half = D // 2
+    wide = torch.promote_types(x.dtype, cos.dtype)
+    c = cos[pos0:pos0 + S].to(wide).view(1, S, 1, half)
+    s = sin[pos0:pos0 + S].to(wide).view(1, S, 1, half)
+    if inverse:
+        s = -s
+    r = x[:, :, :n_rot].to(wide)
+    a, b = r[..., :half], r[..., half:]
+    rot = torch.cat((a * c - b * s, b * c + a * s), dim=-1).to(x.dtype)
+    return torch.cat((rot, x[:, :, n_rot:]), dim=2)
+
+
+class _RopeHeads(torch.autograd.Function):
+    """:class:`_RopePacked` on ``[B, S, heads, D]`` = shape4 with the first ``n_rot`` heads rotated."""
+
+    @staticmethod
+    def forward(ctx, x, cos, sin, pos0, inplace, shape4, n_rot):  # type: ignore[override]
+        k = kernels_for(x)
+        ctx.save_for_backward(cos, sin)
+        ctx.pos0, ctx.shape4, ctx.n_rot = pos0, shape4, n_rot
+        x4 = x.view(shape4)
+        if inplace:
+            ctx.mark_dirty(x)
+            k.rope_heads(x4, cos, sin, x4, n_rot, pos0, False)
+            return x
+        return k.rope_heads(x4, cos, sin, None, n_rot, pos0, False).view(x.shape)
+
+    @staticmethod
+    def backward(ctx, dout):  # type: ignore[override]
+        cos, sin = ctx.saved_tensors
+        d4 = dout.contiguous().view(ctx.shape4)  # out of place: the incoming gradient belongs to autograd
+        dx = kernels_for(dout).rope_heads(d4, cos, sin, None, ctx.n_rot, ctx.pos0, True)
+        return dx.view(dout.shape), None, None, None, None, None, None
 
 
 class _RopePacked(torch.autograd.Function):
@@ -101,7 +147,23 @@ def rope_packed(qkv: Tensor, cos: Tensor, sin: Tensor, pos0: int = 0, *, inplace
     return _RopePacked.apply(qkv, cos, sin, int(pos0), bool(inplace), tuple(qkv.shape))
 
 
-def rope_projection(proj: Tensor, cos: Tensor, sin: Tensor, nhead: int, pos0: int = 0) -> Tensor:
+def rope_heads(x: Tensor, cos: Tensor, sin: Tensor, n_rot: int, pos0: int = 0, *, inplace: bool = False) -> Tensor:
+    """Rotates the first ``n_rot`` heads of ``x [B, S, heads, D]`` for positions ``pos0 .. pos0 + S - 1``; the
+    other heads pass through.  The in-place / out-of-place rules are :func:`rope_packed`'s."""
+    if x.dim() != 4 or not 0 <= n_rot <= x.shape[2]:
+        raise ValueError(f"rope_heads: x must be [B, S, heads, D] with 0 <= n_rot <= heads, got {tuple(x.shape)}, "
+                         f"n_rot={n_rot}")
+    if not x.is_cuda:
+        return rope_heads_reference(x, cos, sin, n_rot, pos0)
+    if not x.is_contiguous():
+        x, inplace = x.contiguous(), False
+    if inplace and x.is_leaf and x.requires_grad:
+        inplace = False  # autograd forbids writing into a leaf that requires grad
+    return _RopeHeads.apply(x, cos, sin, int(pos0), bool(inplace), tuple(x.shape), int(n_rot))
+
+
+def rope_projection(proj: Tensor, cos: Tensor, sin: Tensor, nhead: int, pos0: int = 0,
+                    n_kv_heads: Optional[int] = None) -> Tensor:
     """:func:`rope_packed` for the models: ``proj [B, S, 3 E]`` is the QKV
     projection's own output (fresh, read by nothing else), returned rotated
     and viewed as ``[B, S, 3, H, D]``.
@@ -112,7 +174,20 @@ def rope_projection(proj: Tensor, cos: Tensor, sin: Tensor, nhead: int, pos0: in
     view made inside it, and autograd forbids modifying such a view in place
     (its own view + in-place logic would replace the Function's backward).
     The two give the same bits, so a checkpoint's recompute matches its first
-    forward."""
+    forward.
+
+    ``n_kv_heads`` (``None`` or ``nhead``: the above) selects the grouped-query
+    projection: ``proj [B, S, (H + 2 Hkv) D]``, returned as ``[B, S, H + 2 Hkv,
+    D]`` with the ``H`` Q heads and the ``Hkv`` K heads rotated."""
+    if n_kv_heads is not None and n_kv_heads != nhead:
+        B, S, W = proj.shape
+        heads = nhead + 2 * n_kv_heads
+        shape4 = (B, S, heads, W // heads)
+        n_rot = nhead + n_kv_heads
+        if not proj.is_cuda:
+            return rope_heads_reference(proj.view(shape4), cos, sin, n_rot, pos0)
+        inplace = proj.is_contiguous() and not (torch.is_grad_enabled() and proj.requires_grad)
+        return _RopeHeads.apply(proj.contiguous(), cos, sin, int(pos0), inplace, shape4, n_rot).view(shape4)
     B, S, E3 = proj.shape
     shape5 = (B, S, 3, nhead, E3 // (3 * nhead))
     if not proj.is_cuda:

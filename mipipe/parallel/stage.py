@@ -63,7 +63,9 @@ def block_costs(cfg: LMConfig, split_decoder: bool = False) -> List[float]:
     (see ``mipipe.models.transformer.pipeline_units``)."""
     e, f, s, v = cfg.d_model, cfg.dim_feedforward, cfg.seq_len, cfg.vocab
     causal = 0.5 if cfg.causal else 1.0
-    core = 3.0 * (2 * 3 * e * e + 4 * s * e * causal) + 3.0 * 10 * e
+    # the QKV projection is (H + 2 Hkv) D wide: 3 e without grouped-query attention
+    qkv = cfg.qkv_dim()
+    core = 3.0 * (2 * qkv * e + 4 * s * e * causal) + 3.0 * 10 * e
     out = 3.0 * (2 * e * e) + 3.0 * 10 * e  # + LN/dropout traffic
     if cfg.activation == "swiglu":  # the gated first GEMM is 2F wide, and the gate is a pass of its own
         mlp_in = 3.0 * (2 * e * 2 * f) + 3.0 * 10 * f
