@@ -357,25 +357,76 @@ __device__ __forceinline__ void vmcnt_keep() {
   asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
 }
 
-template <bool KC, int W>
-__device__ __forceinline__ void stage_fast(const bf16_t* base, int64_t ld, int k0, const uint32_t (&off)[W / 64],
-                                           char* tile, int wave) {
+// s_waitcnt lgkmcnt(0) as the builtin's immediate (gfx9 encoding: vmcnt 63 in
+// bits 15:14 and 3:0, expcnt 7 in 6:4 = no wait; lgkmcnt in 11:8 = 0).
+constexpr int kWaitLgkm0 = 0xC07F;
+
+// `base`: the operand's byte address at the tile's first K-row / K-column (a
+// scalar the caller keeps and advances; no per-tile multiply here).
+template <int W>
+__device__ __forceinline__ void stage_fast(const char* base, const uint32_t (&off)[W / 64], char* tile, int wave) {
   constexpr int NU = W / 64;
-  const char* b = reinterpret_cast<const char*>(base) + (KC ? (int64_t)k0 * 2 : (int64_t)k0 * ld * 2);
 #pragma unroll
-  for (int u = 0; u < NU; ++u) glds16_saddr(b, off[u], tile + (wave * NU + u) * 1024);
+  for (int u = 0; u < NU; ++u) glds16_saddr(base, off[u], tile + (wave * NU + u) * 1024);
 }
 
-// Operand base and local k of K-tile k0 (K-segmented operands, GemmArgs::seg_k).
-__device__ __forceinline__ const bf16_t* seg_base(const GemmArgs& g, bool is_a, int k0, int& kl) {
-  if (g.seg_k == 0) {
-    kl = k0;
-    return reinterpret_cast<const bf16_t*>(is_a ? g.A : g.B);
+// K position of the tile a wave group stages next, as running scalars: the
+// A / B byte addresses of the tile (`a`, `b`), and for K-segmented operands
+// (GemmArgs::seg_k) the segment, the local k in it and the NEXT segment's
+// pointers.  init() is the only place that divides (a split-K block may start
+// mid-segment); next() adds the loop-invariant byte steps and, where the local
+// k reaches seg_k, switches to the pointers loaded when the segment before
+// was entered -- so the straight path of the K loop has no scalar load and
+// no wait for one, and the loop reads nothing else from the kernel arguments
+// (the crossing block itself, taken once per seg_k / BK tiles, still waits
+// for the two loads it issues: the compiler loads into spare registers).
+// (seg_base(), which this replaces, re-read GemmArgs::A / a_seg[s] after every
+// LDS-DMA -- the DMA asm clobbers memory -- and its s_waitcnt lgkmcnt(0)
+// drained the fragment reads twice per K-tile, with a division each.)
+struct KCursor {
+  const char *a, *b;    // tile bases
+  const char *na, *nb;  // segment seg + 1 (clamped to the array)
+  int64_t step_a, step_b;
+  int seg_k, kl, seg;
+
+  __device__ __forceinline__ void load_next(const GemmArgs& g) {
+    const int nx = min(seg + 1, GemmArgs::kMaxSegs - 1);
+    na = reinterpret_cast<const char*>(g.a_seg[nx]);
+    nb = reinterpret_cast<const char*>(g.b_seg[nx]);
   }
-  const int s = k0 / g.seg_k;
-  kl = k0 - s * g.seg_k;
-  return reinterpret_cast<const bf16_t*>(is_a ? g.a_seg[s] : g.b_seg[s]);
-}
+  template <bool A_KC, bool B_KC>
+  __device__ __forceinline__ void init(const GemmArgs& g, int kt) {
+    const int64_t lda = g.lda, ldb = g.ldb;
+    step_a = A_KC ? BK * 2 : BK * lda * 2;
+    step_b = B_KC ? BK * 2 : BK * ldb * 2;
+    seg_k = g.seg_k;
+    kl = kt * BK;
+    seg = 0;
+    a = na = reinterpret_cast<const char*>(g.A);
+    b = nb = reinterpret_cast<const char*>(g.B);
+    if (seg_k > 0) {
+      seg = kl / seg_k;
+      kl -= seg * seg_k;
+      a = reinterpret_cast<const char*>(g.a_seg[seg]);
+      b = reinterpret_cast<const char*>(g.b_seg[seg]);
+      load_next(g);
+    }
+    a += A_KC ? (int64_t)kl * 2 : (int64_t)kl * lda * 2;
+    b += B_KC ? (int64_t)kl * 2 : (int64_t)kl * ldb * 2;
+  }
+  __device__ __forceinline__ void next(const GemmArgs& g) {
+    a += step_a;
+    b += step_b;
+    kl += BK;
+    if (__builtin_expect(kl == seg_k, 0)) {  // never with seg_k == 0
+      kl = 0;
+      ++seg;
+      a = na;
+      b = nb;
+      load_next(g);
+    }
+  }
+};
 
 template <bool KC, int W>
 __device__ __forceinline__ bf16x8 frag(const char* tile, int ib, int s, int lane) {
@@ -769,14 +820,27 @@ __global__ void __launch_bounds__(kThreads, 1) gemm256_kernel(GemmArgs g) {
   // [16 tn + 4 (t & 3), +4) of K-row t >> 2 of every A tile (I-contiguous image)
   const bool rsum = g.rowsum != nullptr && tn < 16 && !A_KC;
   float rs[4] = {0.f, 0.f, 0.f, 0.f};
-  auto rowsum_step = [&](const char* tile) {
+  // The fold is split into its LDS read and its adds: the PP == 4 loop issues
+  // the read with the fragment reads and adds after the DMA issue, behind the
+  // interval's own lgkmcnt(0) (adding right after the read put a second drain
+  // of all the fragment reads in front of the DMA issue).
+  auto rowsum_read = [&](const char* tile, s16x4& v) {
     if (rsum && wm == 0) {
       const int r = tid >> 2, c8 = 4 * tn + (tid & 3);
-      const s16x4 v = *reinterpret_cast<const s16x4*>(
+      v = *reinterpret_cast<const s16x4*>(
           AH ? tile + (tn >> 3) * (kTileBytes / 2) + ic_off_w<128>(r, c8 & 31) : tile + ic_off_w<256>(r, c8));
+    }
+  };
+  auto rowsum_add = [&](const s16x4& v) {
+    if (rsum && wm == 0) {
 #pragma unroll
       for (int e = 0; e < 4; ++e) rs[e] += __uint_as_float((uint32_t)(uint16_t)v[e] << 16);
     }
+  };
+  auto rowsum_step = [&](const char* tile) {
+    s16x4 v;
+    rowsum_read(tile, v);
+    rowsum_add(v);
   };
   // fused bias gradient on the B side (GemmArgs::colsum): the tile column is cut
   // into slices of 16 cm columns spread over its tile rows -- block tm, wave
@@ -792,6 +856,11 @@ __global__ void __launch_bounds__(kThreads, 1) gemm256_kernel(GemmArgs g) {
   const int csl = tm + tiles_m * wm;  // this group's slice
   const bool csum = X == kXColsum && !B_KC && g.colsum != nullptr && csl < (W / 16 >> cm_log);
   float cs[4] = {0.f, 0.f, 0.f, 0.f};
+  // Unlike the row fold this one is not split into read and adds: holding its
+  // value across the DMA issue cost the X = kXColsum kernels 2-6 VGPRs more
+  // than they had (254 -> 256, 168 -> 172).  The PP == 4 loop runs the whole
+  // step below the DMA issue instead -- the B tile read is not restaged before
+  // the interval's barrier -- so its wait is the interval's own drain.
   auto colsum_step = [&](const char* btile) {
     if (csum) {
       const int t = tid & 255;
@@ -825,11 +894,15 @@ __global__ void __launch_bounds__(kThreads, 1) gemm256_kernel(GemmArgs g) {
     a = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(atile + lo));
     b = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(atile + hi));
   };
+  // (GemmArgs fields as locals: read through `g` inside the K loop they are
+  // re-loaded after every LDS-DMA, see KCursor)
+  bf16_t* const at_out = X == kXEmit ? reinterpret_cast<bf16_t*>(g.at) : nullptr;
+  const int64_t ldat = X == kXEmit ? g.ldat : 0;
+  const int M = g.M;
   auto emit_store = [&](int kt, int j, const s16x4& a, const s16x4& b) {
     const int rb = 4 * wave + j;
-    bf16_t* at = reinterpret_cast<bf16_t*>(g.at) + (int64_t)(kt * BK + 16 * (lane >> 4) + (lane & 15)) * g.ldat + m0 +
-                 8 * rb;
-    if (m0 + 8 * rb < g.M) *reinterpret_cast<s16x8*>(at) = __builtin_shufflevector(a, b, 0, 1, 2, 3, 4, 5, 6, 7);
+    bf16_t* at = at_out + (int64_t)(kt * BK + 16 * (lane >> 4) + (lane & 15)) * ldat + m0 + 8 * rb;
+    if (m0 + 8 * rb < M) *reinterpret_cast<s16x8*>(at) = __builtin_shufflevector(a, b, 0, 1, 2, 3, 4, 5, 6, 7);
   };
   int kt0 = 0, nk = g.K / BK;
   if (g.k_splits > 1) {  // this block's share of the K-tiles
@@ -860,25 +933,31 @@ __global__ void __launch_bounds__(kThreads, 1) gemm256_kernel(GemmArgs g) {
   constexpr bool LEADB = PP == 2 || PP == 3 || PP == 4;
   constexpr int NB = W / 64;  // B DMAs per wave per K-tile
   constexpr int NA = 4;       // A DMAs per wave per K-tile
+  // PP == 4: `kc` runs ahead of the loop, always at the tile this wave group
+  // stages next (tile u + 1 for group 0, u + 2 for group 1).  The A/B-only
+  // schedules stage A and B at different leads and take their bases from
+  // tile_at(), a KCursor initialised per use (a division and kernel-argument
+  // reads per tile: not for the product loop).
+  KCursor kc;
+  kc.init<A_KC, B_KC>(g, kt0);
+  auto tile_at = [&](int kt) {
+    KCursor c;
+    c.init<A_KC, B_KC>(g, kt0 + kt);
+    return c;
+  };
   {
-    int kl;
-    const bf16_t* A = seg_base(g, true, kt0 * BK, kl);
-    stage_fast<A_KC, 256>(A, g.lda, kl, offA, smem, shA);
-    const bf16_t* B = seg_base(g, false, kt0 * BK, kl);
-    stage_fast<B_KC, W>(B, g.ldb, kl, offB, smem + kTileBytes, shB);
-    if ((PP == 2 || PP == 3) && nk > 1) {
-      B = seg_base(g, false, (kt0 + 1) * BK, kl);
-      stage_fast<B_KC, W>(B, g.ldb, kl, offB, smem + kBuf + kTileBytes, wave);
-    }
-    if (PP == 3 && wm == 1 && nk > 1) {  // group 1 stages its A share one tile earlier (below)
-      A = seg_base(g, true, (kt0 + 1) * BK, kl);
-      stage_fast<A_KC, 256>(A, g.lda, kl, offA, smem + kBuf, wave);
-    }
-    if (PP == 4 && wm == 1 && nk > 1) {  // group 1 stages whole tiles one tile earlier (below)
-      A = seg_base(g, true, (kt0 + 1) * BK, kl);
-      stage_fast<A_KC, 256>(A, g.lda, kl, offA, smem + kBuf, shA);
-      B = seg_base(g, false, (kt0 + 1) * BK, kl);
-      stage_fast<B_KC, W>(B, g.ldb, kl, offB, smem + kBuf + kTileBytes, shB);
+    stage_fast<256>(kc.a, offA, smem, shA);
+    stage_fast<W>(kc.b, offB, smem + kTileBytes, shB);
+    if ((PP == 2 || PP == 3) && nk > 1) stage_fast<W>(tile_at(1).b, offB, smem + kBuf + kTileBytes, wave);
+    if (PP == 3 && wm == 1 && nk > 1)  // group 1 stages its A share one tile earlier (below)
+      stage_fast<256>(tile_at(1).a, offA, smem + kBuf, wave);
+    if constexpr (PP == 4) {
+      kc.next(g);
+      if (wm == 1 && nk > 1) {  // group 1 stages whole tiles one tile earlier (below)
+        stage_fast<256>(kc.a, offA, smem + kBuf, shA);
+        stage_fast<W>(kc.b, offB, smem + kBuf + kTileBytes, shB);
+        kc.next(g);
+      }
     }
   }
 
@@ -902,6 +981,10 @@ __global__ void __launch_bounds__(kThreads, 1) gemm256_kernel(GemmArgs g) {
     // have landed by the barrier ending 2u+1: group 0 drains after its MFMAs
     // (vmcnt(0)), group 1 in its load interval 2u+1 after staging tile u+2
     // (vmcnt(NA + NB)).
+    // The load interval reads no kernel argument: the operand addresses of
+    // the tile a group stages come from its KCursor `kc`, advanced once per
+    // staged tile, and it has ONE LDS drain, the lgkmcnt(0) before its
+    // barrier (static counts and timings: profiles/gemm_loop_scalar.txt).
     if (wm == 1 && nk > 1) vmcnt_keep<NA + NB>();
     else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
@@ -950,22 +1033,25 @@ __global__ void __launch_bounds__(kThreads, 1) gemm256_kernel(GemmArgs g) {
       for (int j = 0; j < NJ; ++j)
 #pragma unroll
         for (int s = 0; s < 2; ++s) bq[j][s] = frag<B_KC, W>(bcur, wn * WN + 16 * j, s, lane);
-      rowsum_step(cur);
-      colsum_step(bcur);
+      // row fold: read here, added below the DMA issue (the column fold runs there whole)
+      s16x4 rv;
+      rowsum_read(cur, rv);
       if (X == kXEmit && A_KC && ej >= 0) emit_store(kt0 + u, ej, ea, eb);
       ekt = ekt + 1 == ntn ? 0 : ekt + 1;
+      // The DMA issue needs nothing but scalars already in registers (kc: no
+      // kernel-argument load, no division, no wait), so it goes out while the
+      // fragment reads above are still in flight.
       const int ahead = wm == 0 ? 1 : 2;  // the tile this group stages now
       if (u + ahead < nk) {
-        int kl;
         char* dst = wm == 0 ? nxt : cur;
-        const bf16_t* A = seg_base(g, true, (kt0 + u + ahead) * BK, kl);
-        stage_fast<A_KC, 256>(A, g.lda, kl, offA, dst, shA);
-        const bf16_t* B = seg_base(g, false, (kt0 + u + ahead) * BK, kl);
+        stage_fast<256>(kc.a, offA, dst, shA);
         int bn = bs + ahead;
         if (bn >= 3) bn -= 3;
-        stage_fast<B_KC, W>(B, g.ldb, kl, offB, B3 ? bslot(bn) : dst + kTileBytes, shB);
+        stage_fast<W>(kc.b, offB, B3 ? bslot(bn) : dst + kTileBytes, shB);
+        kc.next(g);  // a segment crossing loads the pointers of the segment after: retired by the wait below
       }
       bs = bs == 2 ? 0 : bs + 1;
+      colsum_step(bcur);
       if (wm == 1) {
         if (u + 2 < nk) vmcnt_keep<NA + NB>();
         else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -977,7 +1063,11 @@ __global__ void __launch_bounds__(kThreads, 1) gemm256_kernel(GemmArgs g) {
       // wrong accumulator (tools/gemm_round_screen.py caught it: ~1 launch in
       // 3 of one shape).  Guide rule: restage one phase after a read only when
       // an lgkmcnt before the reading phase's barrier retired it.
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      // The wait is the builtin, not asm, so that the compiler's own counting
+      // sees it: the fold adds below and the MFMAs after the barrier then need
+      // no further lgkmcnt wait, and this is the interval's only one.
+      __builtin_amdgcn_s_waitcnt(kWaitLgkm0);
+      rowsum_add(rv);
       __builtin_amdgcn_sched_barrier(0);
       __builtin_amdgcn_s_barrier();
       __builtin_amdgcn_sched_barrier(0);
@@ -1044,18 +1134,13 @@ __global__ void __launch_bounds__(kThreads, 1) gemm256_kernel(GemmArgs g) {
 #pragma unroll
             for (int s = 0; s < 2; ++s) bq[j][s] = frag<B_KC, W>(cur + kTileBytes, wn * WN + 16 * j, s, lane);
           if (wm == 0 && more) {
-            int kl;
-            const bf16_t* A = seg_base(g, true, (kt0 + u + 1) * BK, kl);
-            stage_fast<A_KC, 256>(A, g.lda, kl, offA, nxt, wave);
+            stage_fast<256>(tile_at(u + 1).a, offA, nxt, wave);
           }
         } else if (lead) {
-          int kl;
           if (wm == 1) {
-            const bf16_t* A = seg_base(g, true, (kt0 + u + 2) * BK, kl);
-            stage_fast<A_KC, 256>(A, g.lda, kl, offA, cur, wave);
+            stage_fast<256>(tile_at(u + 2).a, offA, cur, wave);
           }
-          const bf16_t* B = seg_base(g, false, (kt0 + u + 2) * BK, kl);
-          stage_fast<B_KC, W>(B, g.ldb, kl, offB, cur + kTileBytes, wave);
+          stage_fast<W>(tile_at(u + 2).b, offB, cur + kTileBytes, wave);
         }
         if (ph == 1 && wm == 1) {
           if (lead) vmcnt_keep<NA + NB>();
@@ -1115,20 +1200,14 @@ __global__ void __launch_bounds__(kThreads, 1) gemm256_kernel(GemmArgs g) {
               bf[qn][jj][s] = frag<B_KC, W>(cur + kTileBytes, wn * WN + qn * (WN / 2) + 16 * jj, s, lane);
         }
         if (ph == 0 && more) {
-          int kl;
-          const bf16_t* A = seg_base(g, true, (kt0 + u + 1) * BK, kl);
-          stage_fast<A_KC, 256>(A, g.lda, kl, offA, nxt, wave);
+          stage_fast<256>(tile_at(u + 1).a, offA, nxt, wave);
         }
         if (!LEADB && ph == 1 && more) {
-          int kl;
-          const bf16_t* B = seg_base(g, false, (kt0 + u + 1) * BK, kl);
-          stage_fast<B_KC, W>(B, g.ldb, kl, offB, nxt + kTileBytes, wave);
+          stage_fast<W>(tile_at(u + 1).b, offB, nxt + kTileBytes, wave);
         }
         const bool lead = LEADB && u + 2 < nk;  // a B DMA two tiles ahead is issued this tile
         if (ph == 3 && lead) {
-          int kl;
-          const bf16_t* B = seg_base(g, false, (kt0 + u + 2) * BK, kl);
-          stage_fast<B_KC, W>(B, g.ldb, kl, offB, const_cast<char*>(cur) + kTileBytes, wave);
+          stage_fast<W>(tile_at(u + 2).b, offB, const_cast<char*>(cur) + kTileBytes, wave);
         }
         if (ph == 3 && wm == 1) {
           if (lead) vmcnt_keep<NB>();
@@ -1167,11 +1246,8 @@ __global__ void __launch_bounds__(kThreads, 1) gemm256_kernel(GemmArgs g) {
     __syncthreads();
     if (kt + 1 < nk) {
       char* nxt = smem + ((kt + 1) & 1) * kBuf;
-      int kl;
-      const bf16_t* A = seg_base(g, true, (kt0 + kt + 1) * BK, kl);
-      stage_fast<A_KC, 256>(A, g.lda, kl, offA, nxt, wave);
-      const bf16_t* B = seg_base(g, false, (kt0 + kt + 1) * BK, kl);
-      stage_fast<B_KC, W>(B, g.ldb, kl, offB, nxt + kTileBytes, wave);
+      stage_fast<256>(tile_at(kt + 1).a, offA, nxt, wave);
+      stage_fast<W>(tile_at(kt + 1).b, offB, nxt + kTileBytes, wave);
     }
     const char* cur = smem + (kt & 1) * kBuf;
     rowsum_step(cur);
