@@ -274,12 +274,12 @@ constexpr int kThreads = 512;
 constexpr int kTileBytes = BM * BK * 2;      // 32 KiB per operand tile
 constexpr int kSmemBytes = 128 * 260 * 4;    // 130 KiB: 2 x 64 KiB operand buffers, reused by the epilogue
 
-// The PP == 4 loop keeps an I-contiguous B operand in THREE buffers (A in two;
+// The main loop keeps an I-contiguous B operand in THREE buffers (A in two;
 // see the loop): 2 (A + B) + B = 160 KiB at W = 256, all of the CU's LDS.
-template <bool B_KC, int PP, int W>
+template <bool B_KC, int W>
 constexpr int smem_bytes() {
   constexpr int b3 = 2 * (kTileBytes + W * BK * 2) + W * BK * 2;
-  return PP == 4 && !B_KC && b3 > kSmemBytes ? b3 : kSmemBytes;
+  return !B_KC && b3 > kSmemBytes ? b3 : kSmemBytes;
 }
 
 // I-contiguous image with 2W-byte rows (W = 256 or 128 i values; the B tile of
@@ -318,7 +318,7 @@ __device__ __forceinline__ void stage_offsets(int64_t ld, int i0, int lim, int w
   }
 }
 
-// The I-contiguous A tile of the PP == 4 loop is kept as two 128-wide halves
+// The I-contiguous A tile of the main loop is kept as two 128-wide halves
 // (i 0-127, then 128-255; 16 KiB each, the W = 128 image), so each half is read
 // by one wave group only.  Share s (0-7) stages rows 16 (s & 3) .. +16 of half
 // s >> 2 -- the same LDS pieces stage_fast gives share s (4 KiB at 4 s KiB).
@@ -502,31 +502,18 @@ __device__ __forceinline__ void epi_rows(const EpiParams ep, f32x4 (&acc)[8][NJ]
 // per store (+ the bf16 addend `res`, read as 16-byte row chunks), fp32
 // read-modify-write (kEpiAccumF32) or fp32 stores.  Starts with the LDS free,
 // ends with a barrier (so it can run twice: aux, then the output).
-// NJ: 16-wide accumulator tiles per wave (W / 64 for the 8-wave kernel, whose
-// wave tile is 128 x W/4; 8 for the 4-wave kernel's 128 x 128), kT: threads.
-// ROWSPLIT (the 4-wave kernel): pass p stages accumulator rows i = 4p..4p+3 of
-// EVERY wave (all waves share the LDS writes) instead of all rows of the waves
-// with wm == p; image row R is then tile row 128 (R >> 6) + 64 p + (R & 63).
-template <int EPI, int W, int NJ = W / 64, int kT = 512, bool ROWSPLIT = false>
-__device__ __forceinline__ void staged_store(char* smem, const f32x4 (&acc)[8][NJ], int wm, int wn, int lane,
+template <int EPI, int W>
+__device__ __forceinline__ void staged_store(char* smem, const f32x4 (&acc)[8][W / 64], int wm, int wn, int lane,
                                              int tid, int m0, int n0, int M, int N, int64_t ldc, void* out,
                                              const bf16_t* res, int64_t ldr = 0, const bf16_t* dact_in = nullptr,
                                              int64_t ldd = 0, int dact = 0, float dact_scale = 1.f,
                                              bool trans = false, bool dgelu = false) {
-  constexpr int WN = 16 * NJ, kStride = W + 4;
+  constexpr int NJ = W / 64, WN = 16 * NJ, kStride = W + 4;  // NJ: 16-wide accumulator tiles per wave
   const int quad = lane >> 4, col_in = lane & 15;
   float* stg = reinterpret_cast<float*>(smem);
 #pragma unroll
   for (int pass = 0; pass < 2; ++pass) {
-    if (ROWSPLIT) {
-#pragma unroll
-      for (int ii = 0; ii < 4; ++ii)
-#pragma unroll
-        for (int j = 0; j < NJ; ++j)
-#pragma unroll
-          for (int r = 0; r < 4; ++r)
-            stg[(64 * wm + 16 * ii + 4 * quad + r) * kStride + wn * WN + 16 * j + col_in] = acc[4 * pass + ii][j][r];
-    } else if (wm == pass) {
+    if (wm == pass) {
 #pragma unroll
       for (int i = 0; i < 8; ++i)
 #pragma unroll
@@ -537,14 +524,13 @@ __device__ __forceinline__ void staged_store(char* smem, const f32x4 (&acc)[8][N
     }
     __syncthreads();
     const int rbase = m0 + pass * 128;
-    // tile row of image row R (R's 4-row quads never straddle a 64-row block)
-    auto grow = [&](int R) { return ROWSPLIT ? m0 + ((R >> 6) << 7) + 64 * pass + (R & 63) : rbase + R; };
+    auto grow = [&](int R) { return rbase + R; };  // tile row of image row R
     if (EPI == kEpiStoreBf16) {
       bf16_t* C = reinterpret_cast<bf16_t*>(out);
       constexpr int CPR = W / 8;  // 128 rows x W/8 chunks of 8 columns
 #pragma unroll
-      for (int u = 0; u < 128 * CPR / kT; ++u) {
-        const int idx = tid + u * kT;
+      for (int u = 0; u < 128 * CPR / kThreads; ++u) {
+        const int idx = tid + u * kThreads;
         const int row = idx / CPR, c8 = idx % CPR;
         if (grow(row) >= M || n0 + 8 * c8 >= N) continue;
         const f32x4 lo = *reinterpret_cast<const f32x4*>(stg + row * kStride + 8 * c8);
@@ -581,8 +567,8 @@ __device__ __forceinline__ void staged_store(char* smem, const f32x4 (&acc)[8][N
       // are 8 row quads of one column (128 contiguous output bytes).
       float* C = reinterpret_cast<float*>(out);
 #pragma unroll 4
-      for (int u = 0; u < 32 * W / kT; ++u) {
-        const int idx = tid + u * kT;
+      for (int u = 0; u < 32 * W / kThreads; ++u) {
+        const int idx = tid + u * kThreads;
         const int mq = (idx & 7) + 8 * (idx / (8 * W)), n = (idx >> 3) % W;
         if (grow(4 * mq) >= M || n0 + n >= N) continue;
         const float* sp = stg + 4 * mq * kStride + n;
@@ -599,8 +585,8 @@ __device__ __forceinline__ void staged_store(char* smem, const f32x4 (&acc)[8][N
       float* C = reinterpret_cast<float*>(out);
       constexpr int CPR = W / 4;  // 128 rows x W/4 chunks of 4 columns
 #pragma unroll
-      for (int u = 0; u < 128 * CPR / kT; ++u) {
-        const int idx = tid + u * kT;
+      for (int u = 0; u < 128 * CPR / kThreads; ++u) {
+        const int idx = tid + u * kThreads;
         const int row = idx / CPR, c4 = idx % CPR;
         if (grow(row) >= M || n0 + 4 * c4 >= N) continue;
         const float4 v = *reinterpret_cast<const float4*>(stg + row * kStride + 4 * c4);
@@ -628,10 +614,10 @@ __device__ __forceinline__ void staged_store(char* smem, const f32x4 (&acc)[8][N
 // (18432 x 6400 x 1600, GELU, p 0.1, pre saved) cost 542 us against 358 plain
 // (tools/epilogue_cost_probe.py).  Also the activation backward of a dgrad
 // whose forward had dropout (dact_in with the mask regenerated).
-template <int ACT, int W, int NJ = W / 64, int kT = 512, bool ROWSPLIT = false>
-__device__ __forceinline__ void staged_store_act(char* smem, const f32x4 (&acc)[8][NJ], int wm, int wn,
+template <int ACT, int W>
+__device__ __forceinline__ void staged_store_act(char* smem, const f32x4 (&acc)[8][W / 64], int wm, int wn,
                                                  int lane, int tid, int m0, int n0, const GemmArgs& g) {
-  constexpr int WN = 16 * NJ, kStride = W + 4, CB = W / 8;
+  constexpr int NJ = W / 64, WN = 16 * NJ, kStride = W + 4, CB = W / 8;
   const int quad = lane >> 4, col_in = lane & 15;
   float* stg = reinterpret_cast<float*>(smem);
   bf16_t* C = reinterpret_cast<bf16_t*>(g.C);
@@ -645,15 +631,7 @@ __device__ __forceinline__ void staged_store_act(char* smem, const f32x4 (&acc)[
   const uint32_t thr16 = g.threshold >> 16;
 #pragma unroll
   for (int pass = 0; pass < 2; ++pass) {
-    if (ROWSPLIT) {
-#pragma unroll
-      for (int ii = 0; ii < 4; ++ii)
-#pragma unroll
-        for (int j = 0; j < NJ; ++j)
-#pragma unroll
-          for (int r = 0; r < 4; ++r)
-            stg[(64 * wm + 16 * ii + 4 * quad + r) * kStride + wn * WN + 16 * j + col_in] = acc[4 * pass + ii][j][r];
-    } else if (wm == pass) {
+    if (wm == pass) {
 #pragma unroll
       for (int i = 0; i < 8; ++i)
 #pragma unroll
@@ -665,11 +643,11 @@ __device__ __forceinline__ void staged_store_act(char* smem, const f32x4 (&acc)[
     __syncthreads();
     const int rbase = m0 + pass * 128;
 #pragma unroll
-    for (int u = 0; u < 32 * CB / kT; ++u) {
-      const int idx = tid + u * kT;
+    for (int u = 0; u < 32 * CB / kThreads; ++u) {
+      const int idx = tid + u * kThreads;
       const int rq = idx / CB, c8 = idx % CB;  // consecutive lanes on consecutive 8-column chunks
       const int col = n0 + 8 * c8;
-      const int row0 = ROWSPLIT ? m0 + (((4 * rq) >> 6) << 7) + 64 * pass + ((4 * rq) & 63) : rbase + 4 * rq;
+      const int row0 = rbase + 4 * rq;
       if (col >= g.N || row0 >= g.M) continue;
       uint32_t wd[4][4];  // [column pair][row]: two 16-bit uniforms per word
       if (drop) {
@@ -727,78 +705,44 @@ __device__ __forceinline__ void staged_store_act(char* smem, const f32x4 (&acc)[
   }
 }
 
-// Ping-pong main loop (PP = true).  The two wave groups (wm = 0: waves 0-3,
+// Main loop: whole-tile ping-pong.  The two wave groups (wm = 0: waves 0-3,
 // wm = 1: waves 4-7; each SIMD hosts one wave of each) run one barrier
-// interval apart, so in every interval one wave per SIMD issues its 16-MFMA
-// cluster while its partner issues the LDS fragment reads (and LDS-DMA
-// staging) for its next cluster -- the LDS latency of one group hides behind
-// the other's MFMAs instead of stalling both (guide: 256^2 8-phase template,
-// T5 s_setprio).  A K-tile is 4 phases, one per 64x32 quadrant of the wave's
-// 128x64 tile, in the order (0,0) (0,1) (1,1) (1,0): A fragments are read in
-// phases 0 and 2, B in phases 0 and 1 and kept, phase 3 reads nothing.
-// Buffer hand-off (intervals counted from group 0's first phase of tile u,
-// group 1 one behind):
-//   * tile u+1 is DMA'd into the other buffer in phases 0/1 (A/B) of tile u:
-//     that buffer (tile u-1) was last read in tile u-1's phase 2, retired by
-//     the lgkmcnt(0) of phase 2's MFMA interval, behind >= 1 barrier;
-//   * each wave drains its own DMA (vmcnt(0)) before the barrier that ends
-//     the last interval of tile u -- group 0 after its phase-3 MFMAs, group 1
-//     in its phase-3 load interval -- so every wave's reads of tile u+1 start
-//     after a barrier all DMAs of the tile have landed behind.
+// interval apart, so in every interval one wave per SIMD issues the 64 MFMAs
+// of its whole 128 x W/4 tile of a K-tile while its partner issues the LDS
+// fragment reads (and the LDS-DMA staging) for its next one -- the LDS
+// latency of one group hides behind the other's MFMAs instead of stalling
+// both, and s_setprio keeps the MFMA wave ahead of the loading one.  One load
+// and one MFMA interval per K-tile and wave (236-242 VGPRs, no scratch), two
+// barriers per 1024 MFMA cycles.  The buffer hand-off, the staging shares that
+// keep a DMA off bytes a sibling wave may still read, the three-buffer rotation
+// of an I-contiguous B and the waits are described at the loop itself.
 //
-// 3 / 4 (default): as 2 / 1 with the B operand staged two K-tiles ahead (PP = 2).
-// 0: one barrier per K-tile everywhere, 1: ping-pong everywhere, 2:
-// ping-pong except the weight-gradient layout (both operands I-contiguous),
-// where the per-tile loop measured 1-4 % faster (profiles/gemm_saddr_ab.txt).
-// (A piece-staged variant -- each half-tile re-staged as soon as its own last
-// reader was 2 phases behind, 6 phases of DMA lead, counted vmcnt -- measured
-// 1-8 % slower than ping-pong: profiles/gemm_schedules_ab.txt.)
-// Default 4: the B lead measured +3-7 % on the KC-layout forward / dgrad GEMMs
-// (enc12 qkv fwd 1313 -> 1365 TF/s, dec dgrad 1297 -> 1388, GPT-2-XL dgrads
-// +3-4 %; profiles/gemm_sched_ab.txt), and with it the ping-pong loop beats
-// the per-tile one on the weight-gradient layout as well (+3-5 % at the sizes
-// of a step's flush: profiles/wgrad_flush_sched.txt).
-// 5: half-tile ping-pong (PP = 3: 2 phases of 32 MFMAs per K-tile), 6: 5 on the
-// KC layouts and 4 on the weight-gradient layout, 7 (DEFAULT, round 3): whole-
-// tile ping-pong (PP = 4: one 64-MFMA interval per K-tile and wave, 236-242
-// VGPRs, no scratch).  Fewer, longer intervals pay the two barriers of a phase
-// less often: enc12 qkv fwd 1369 -> 1438 TF/s, dec dgrad 1387 -> 1500, the
-// enc12 PP=1 bench 139.0k -> 143.8k tok/s (same box, arms alternated;
-// profiles/gemm_sched_ab.txt).
-// Only schedule 7 is compiled into the product build (launch_big_w); the
-// others need -DMIPIPE_GEMM_AB.
-int g_gemm_sched = -1;  // -1: MIPIPE_GEMM_SCHED (default 7) not read yet
-int gemm_sched() {
-  if (g_gemm_sched < 0) {
-#ifdef MIPIPE_GEMM_AB
-    const char* e = getenv("MIPIPE_GEMM_SCHED");
-    g_gemm_sched = e ? atoi(e) : 7;
-#else
-    g_gemm_sched = 7;
-#endif
-  }
-  return g_gemm_sched;
-}
+// Tried and lost, and no longer in this file: one barrier per K-tile with no
+// ping-pong, ping-pong in four 16-MFMA phases per K-tile (with and without the
+// B operand staged two K-tiles ahead) and in two 32-MFMA phases, a
+// piece-staged variant, and a 4-wave kernel with a 128x128 tile per wave.  The
+// whole-tile loop beat the best of the phased ones by 3-7 % (fewer, longer
+// intervals pay the barriers less often: profiles/gemm_sched_ab.txt,
+// profiles/gemm_schedules_ab.txt, and profiles/wgrad_flush_sched.txt for the
+// weight-gradient layout); the 4-wave kernel measured 2-11 % slower at the
+// power cap (profiles/gemm4w_r5.txt).
 
 // W: block tile width along N -- 256, or 128 for grids where 256x256 tiles
 // would leave CUs idle (256x128 block, 128x32 per wave).
 // EXTRA: the bf16 epilogue also applies dropout and/or stores the
 // pre-activation (otherwise it is branch-free bias + activation).
-// PP: 0 = one barrier per K-tile, 1 = ping-pong, 2 = ping-pong with the B
-// operand staged two K-tiles ahead (below).
 // X: main-loop extras, 0 none, kXEmit the A^T emission (GemmArgs::at), kXColsum
 // the B-side bias fold (GemmArgs::colsum) -- separate instantiations, so the
 // plain kernels keep their register allocation.
 constexpr int kXEmit = 1, kXColsum = 2;
 
-template <bool A_KC, bool B_KC, int EPI, int ACT, int PP, int W, bool EXTRA, int X = 0>
+template <bool A_KC, bool B_KC, int EPI, int ACT, int W, bool EXTRA, int X = 0>
 __global__ void __launch_bounds__(kThreads, 1) gemm256_kernel(GemmArgs g) {
   constexpr int NJ = W / 64;          // 16-wide MFMA column tiles per wave
-  constexpr int JJ = NJ / 2;          // ... per ping-pong quadrant
   constexpr int WN = W / 4;           // wave tile width
   constexpr int kBuf = kTileBytes + W * BK * 2;  // A + B tile
-  constexpr bool AH = PP == 4 && !A_KC;          // A tile as two 128-wide halves (stage_offsets_halves)
-  constexpr bool B3 = PP == 4 && !B_KC;          // B tiles in three buffers (smem_bytes)
+  constexpr bool AH = !A_KC;          // A tile as two 128-wide halves (stage_offsets_halves)
+  constexpr bool B3 = !B_KC;          // B tiles in three buffers (smem_bytes)
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -820,7 +764,7 @@ __global__ void __launch_bounds__(kThreads, 1) gemm256_kernel(GemmArgs g) {
   // [16 tn + 4 (t & 3), +4) of K-row t >> 2 of every A tile (I-contiguous image)
   const bool rsum = g.rowsum != nullptr && tn < 16 && !A_KC;
   float rs[4] = {0.f, 0.f, 0.f, 0.f};
-  // The fold is split into its LDS read and its adds: the PP == 4 loop issues
+  // The fold is split into its LDS read and its adds: the main loop issues
   // the read with the fragment reads and adds after the DMA issue, behind the
   // interval's own lgkmcnt(0) (adding right after the read put a second drain
   // of all the fragment reads in front of the DMA issue).
@@ -836,11 +780,6 @@ __global__ void __launch_bounds__(kThreads, 1) gemm256_kernel(GemmArgs g) {
 #pragma unroll
       for (int e = 0; e < 4; ++e) rs[e] += __uint_as_float((uint32_t)(uint16_t)v[e] << 16);
     }
-  };
-  auto rowsum_step = [&](const char* tile) {
-    s16x4 v;
-    rowsum_read(tile, v);
-    rowsum_add(v);
   };
   // fused bias gradient on the B side (GemmArgs::colsum): the tile column is cut
   // into slices of 16 cm columns spread over its tile rows -- block tm, wave
@@ -858,7 +797,7 @@ __global__ void __launch_bounds__(kThreads, 1) gemm256_kernel(GemmArgs g) {
   float cs[4] = {0.f, 0.f, 0.f, 0.f};
   // Unlike the row fold this one is not split into read and adds: holding its
   // value across the DMA issue cost the X = kXColsum kernels 2-6 VGPRs more
-  // than they had (254 -> 256, 168 -> 172).  The PP == 4 loop runs the whole
+  // than they had (254 -> 256, 168 -> 172).  The main loop runs the whole
   // step below the DMA issue instead -- the B tile read is not restaged before
   // the interval's barrier -- so its wait is the interval's own drain.
   auto colsum_step = [&](const char* btile) {
@@ -910,361 +849,158 @@ __global__ void __launch_bounds__(kThreads, 1) gemm256_kernel(GemmArgs g) {
     kt0 = (int)blockIdx.y * total / g.k_splits;
     nk = ((int)blockIdx.y + 1) * total / g.k_splits - kt0;
   }
-  // Staging shares of the PP == 4 schedule (see its loop): the waves of group 1
-  // (which restage the buffer their siblings are still reading) take bytes no
-  // sibling reads -- A rows 0-127 (group 0's half: share of "wave" w ^ 4; for
+  // Staging shares (see the loop): the waves of group 1 (which restage the
+  // buffer their siblings are still reading) take bytes no sibling reads -- A rows 0-127 (group 0's half: share of "wave" w ^ 4; for
   // an I-contiguous A the tile is kept as two halves for this) and, for a
   // K-contiguous B, the first 32 of the 64 rows the wave itself reads (share
   // 2 wn; group 0 the other 32: 2 wn + 1).  An I-contiguous B (every wave
   // reads every k-row) rotates through three buffers instead and keeps the
   // per-wave k-row shares.
-  const int shA = PP == 4 ? wave ^ 4 : wave;
-  const int shB = PP == 4 && B_KC ? 2 * wn + (wm == 0 ? 1 : 0) : wave;
+  const int shA = wave ^ 4;
+  const int shB = B_KC ? 2 * wn + (wm == 0 ? 1 : 0) : wave;
   uint32_t offA[4], offB[NJ];
   if constexpr (AH) stage_offsets_halves(g.lda, m0, g.M, shA, lane, offA);
   else stage_offsets<A_KC, 256>(g.lda, m0, g.M, shA, lane, offA);
   stage_offsets<B_KC, W>(g.ldb, n0, g.N, shB, lane, offB);
-  // PP == 2 (LEADB): the B tile of K-tile u+2 is staged in phase 3 of tile u,
-  // into the buffer tile u is being computed from -- its B region is dead by
-  // then (B fragments are read in phases 0/1 and kept in registers; group 1's
-  // last B read of tile u, phase 1, retired two barriers earlier).  B thus has
-  // ~1.5 K-tiles to land instead of ~2 phases; the tile-end waits become
-  // vmcnt(NB): all but the B DMAs just issued (loads retire in order).
-  constexpr bool LEADB = PP == 2 || PP == 3 || PP == 4;
   constexpr int NB = W / 64;  // B DMAs per wave per K-tile
   constexpr int NA = 4;       // A DMAs per wave per K-tile
-  // PP == 4: `kc` runs ahead of the loop, always at the tile this wave group
-  // stages next (tile u + 1 for group 0, u + 2 for group 1).  The A/B-only
-  // schedules stage A and B at different leads and take their bases from
-  // tile_at(), a KCursor initialised per use (a division and kernel-argument
-  // reads per tile: not for the product loop).
+  // `kc` runs ahead of the loop, always at the tile this wave group stages
+  // next (tile u + 1 for group 0, u + 2 for group 1).
   KCursor kc;
   kc.init<A_KC, B_KC>(g, kt0);
-  auto tile_at = [&](int kt) {
-    KCursor c;
-    c.init<A_KC, B_KC>(g, kt0 + kt);
-    return c;
-  };
-  {
-    stage_fast<256>(kc.a, offA, smem, shA);
-    stage_fast<W>(kc.b, offB, smem + kTileBytes, shB);
-    if ((PP == 2 || PP == 3) && nk > 1) stage_fast<W>(tile_at(1).b, offB, smem + kBuf + kTileBytes, wave);
-    if (PP == 3 && wm == 1 && nk > 1)  // group 1 stages its A share one tile earlier (below)
-      stage_fast<256>(tile_at(1).a, offA, smem + kBuf, wave);
-    if constexpr (PP == 4) {
-      kc.next(g);
-      if (wm == 1 && nk > 1) {  // group 1 stages whole tiles one tile earlier (below)
-        stage_fast<256>(kc.a, offA, smem + kBuf, shA);
-        stage_fast<W>(kc.b, offB, smem + kBuf + kTileBytes, shB);
-        kc.next(g);
-      }
-    }
+  stage_fast<256>(kc.a, offA, smem, shA);
+  stage_fast<W>(kc.b, offB, smem + kTileBytes, shB);
+  kc.next(g);
+  if (wm == 1 && nk > 1) {  // group 1 stages whole tiles one tile earlier (below)
+    stage_fast<256>(kc.a, offA, smem + kBuf, shA);
+    stage_fast<W>(kc.b, offB, smem + kBuf + kTileBytes, shB);
+    kc.next(g);
   }
 
-  if constexpr (PP == 4) {
-    // Whole-tile ping-pong: one load and one MFMA interval per K-tile and wave
-    // (64 MFMAs: the wave's whole 128x64 tile), barriers paid once per 1024
-    // MFMA cycles.  Group 0 loads tile u in interval 2u, group 1 in 2u+1
-    // (global count).  Tile u+1 goes into tile u-1's buffer, last read by
-    // group 1 in 2u-1: group 1 stages its share right after those reads
-    // (program order), group 0 in its load interval 2u.  Group 1's DMA into
-    // tile u's buffer may land while a SIBLING wave still has reads of it
-    // queued (no barrier separates the waves of a group; a sibling delayed by
-    // its A^T emission piece was seen to read the next tile's rows once), so
-    // group 1 restages only bytes none of its siblings reads: A rows 0-127
-    // (shA above; an I-contiguous A is kept as two 128-row halves for that)
-    // and, for a K-contiguous B, half of the i-rows the wave itself reads
-    // (shB).  An I-contiguous B has no such share (every wave reads every
-    // k-row of its columns), so its tiles rotate through three buffers: tile
-    // u+2 goes into tile u-1's B buffer, whose last reads (group 1, interval
-    // 2u-1) retired before the barrier ending that interval.  Tile u+1 must
-    // have landed by the barrier ending 2u+1: group 0 drains after its MFMAs
-    // (vmcnt(0)), group 1 in its load interval 2u+1 after staging tile u+2
-    // (vmcnt(NA + NB)).
-    // The load interval reads no kernel argument: the operand addresses of
-    // the tile a group stages come from its KCursor `kc`, advanced once per
-    // staged tile, and it has ONE LDS drain, the lgkmcnt(0) before its
-    // barrier (static counts and timings: profiles/gemm_loop_scalar.txt).
-    if (wm == 1 && nk > 1) vmcnt_keep<NA + NB>();
-    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    if (wm == 1) __builtin_amdgcn_s_barrier();  // stagger group 1 by one interval
-    bf16x8 af[8][2], bq[NJ][2];
-    int ekt = kt0 % ntn;  // (kt0 + u) mod tiles_n (A^T emission rotation)
-    // B3: B buffer of slot s (tiles kt0, kt0 + 1 were staged into slots 0, 1)
-    auto bslot = [&](int s) { return s == 2 ? smem + 2 * kBuf : smem + s * kBuf + kTileBytes; };
-    int bs = 0;  // B3: slot of tile u (u mod 3)
-    for (int u = 0; u < nk; ++u) {
-      char* cur = smem + (u & 1) * kBuf;
-      char* nxt = smem + ((u + 1) & 1) * kBuf;
-      char* bcur = B3 ? bslot(bs) : cur + kTileBytes;
-      // emission first: its reads precede this wave's DMA that may restage
-      // `cur`, and its stores (waiting for those reads) precede the fragment
-      // reads, so its 16 data registers are dead before the fragments load
-      // this wave's A^T piece of K-tile kt0 + u, if any: j with (4 wave + j + kt) mod tiles_n == tn
-      // (grids under 4 tile columns give a wave several pieces of a K-tile:
-      // those are read and stored one after the other, here)
-      int ej = -1;
-      if (X == kXEmit && A_KC) {
-        int e = ewb + ekt;
-        while (e >= ntn) e -= ntn;
-        ej = tn - e;  // first piece index (the wrap: tn + ntn - e)
-        if (ej < 0) ej += ntn;
-        if (ntn < 4) {
-          for (int j = ej; j < 4; j += ntn) {
-            s16x4 a, b;
-            emit_reads(cur, j, a, b);
-            emit_store(kt0 + u, j, a, b);
-          }
-          ej = -1;
-        } else if (ej > 3) {
-          ej = -1;
+  // Whole-tile ping-pong: one load and one MFMA interval per K-tile and wave
+  // (64 MFMAs: the wave's whole 128x64 tile), barriers paid once per 1024
+  // MFMA cycles.  Group 0 loads tile u in interval 2u, group 1 in 2u+1
+  // (global count).  Tile u+1 goes into tile u-1's buffer, last read by
+  // group 1 in 2u-1: group 1 stages its share right after those reads
+  // (program order), group 0 in its load interval 2u.  Group 1's DMA into
+  // tile u's buffer may land while a SIBLING wave still has reads of it
+  // queued (no barrier separates the waves of a group; a sibling delayed by
+  // its A^T emission piece was seen to read the next tile's rows once), so
+  // group 1 restages only bytes none of its siblings reads: A rows 0-127
+  // (shA above; an I-contiguous A is kept as two 128-row halves for that)
+  // and, for a K-contiguous B, half of the i-rows the wave itself reads
+  // (shB).  An I-contiguous B has no such share (every wave reads every
+  // k-row of its columns), so its tiles rotate through three buffers: tile
+  // u+2 goes into tile u-1's B buffer, whose last reads (group 1, interval
+  // 2u-1) retired before the barrier ending that interval.  Tile u+1 must
+  // have landed by the barrier ending 2u+1: group 0 drains after its MFMAs
+  // (vmcnt(0)), group 1 in its load interval 2u+1 after staging tile u+2
+  // (vmcnt(NA + NB)).
+  // The load interval reads no kernel argument: the operand addresses of
+  // the tile a group stages come from its KCursor `kc`, advanced once per
+  // staged tile, and it has ONE LDS drain, the lgkmcnt(0) before its
+  // barrier (static counts and timings: profiles/gemm_loop_scalar.txt).
+  if (wm == 1 && nk > 1) vmcnt_keep<NA + NB>();
+  else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __builtin_amdgcn_s_barrier();
+  if (wm == 1) __builtin_amdgcn_s_barrier();  // stagger group 1 by one interval
+  bf16x8 af[8][2], bq[NJ][2];
+  int ekt = kt0 % ntn;  // (kt0 + u) mod tiles_n (A^T emission rotation)
+  // B3: B buffer of slot s (tiles kt0, kt0 + 1 were staged into slots 0, 1)
+  auto bslot = [&](int s) { return s == 2 ? smem + 2 * kBuf : smem + s * kBuf + kTileBytes; };
+  int bs = 0;  // B3: slot of tile u (u mod 3)
+  for (int u = 0; u < nk; ++u) {
+    char* cur = smem + (u & 1) * kBuf;
+    char* nxt = smem + ((u + 1) & 1) * kBuf;
+    char* bcur = B3 ? bslot(bs) : cur + kTileBytes;
+    // emission first: its reads precede this wave's DMA that may restage
+    // `cur`, and its stores (waiting for those reads) precede the fragment
+    // reads, so its 16 data registers are dead before the fragments load
+    // this wave's A^T piece of K-tile kt0 + u, if any: j with (4 wave + j + kt) mod tiles_n == tn
+    // (grids under 4 tile columns give a wave several pieces of a K-tile:
+    // those are read and stored one after the other, here)
+    int ej = -1;
+    if (X == kXEmit && A_KC) {
+      int e = ewb + ekt;
+      while (e >= ntn) e -= ntn;
+      ej = tn - e;  // first piece index (the wrap: tn + ntn - e)
+      if (ej < 0) ej += ntn;
+      if (ntn < 4) {
+        for (int j = ej; j < 4; j += ntn) {
+          s16x4 a, b;
+          emit_reads(cur, j, a, b);
+          emit_store(kt0 + u, j, a, b);
         }
+        ej = -1;
+      } else if (ej > 3) {
+        ej = -1;
       }
-      s16x4 ea, eb;
-      if (X == kXEmit && A_KC && ej >= 0) emit_reads(cur, ej, ea, eb);
+    }
+    s16x4 ea, eb;
+    if (X == kXEmit && A_KC && ej >= 0) emit_reads(cur, ej, ea, eb);
+#pragma unroll
+    for (int ii = 0; ii < 8; ++ii)
+#pragma unroll
+      for (int s = 0; s < 2; ++s)
+        af[ii][s] = AH ? frag<false, 128>(cur + wm * (kTileBytes / 2), 16 * ii, s, lane)
+                       : frag<A_KC, 256>(cur, wm * 128 + 16 * ii, s, lane);
+#pragma unroll
+    for (int j = 0; j < NJ; ++j)
+#pragma unroll
+      for (int s = 0; s < 2; ++s) bq[j][s] = frag<B_KC, W>(bcur, wn * WN + 16 * j, s, lane);
+    // row fold: read here, added below the DMA issue (the column fold runs there whole)
+    s16x4 rv;
+    rowsum_read(cur, rv);
+    if (X == kXEmit && A_KC && ej >= 0) emit_store(kt0 + u, ej, ea, eb);
+    ekt = ekt + 1 == ntn ? 0 : ekt + 1;
+    // The DMA issue needs nothing but scalars already in registers (kc: no
+    // kernel-argument load, no division, no wait), so it goes out while the
+    // fragment reads above are still in flight.
+    const int ahead = wm == 0 ? 1 : 2;  // the tile this group stages now
+    if (u + ahead < nk) {
+      char* dst = wm == 0 ? nxt : cur;
+      stage_fast<256>(kc.a, offA, dst, shA);
+      int bn = bs + ahead;
+      if (bn >= 3) bn -= 3;
+      stage_fast<W>(kc.b, offB, B3 ? bslot(bn) : dst + kTileBytes, shB);
+      kc.next(g);  // a segment crossing loads the pointers of the segment after: retired by the wait below
+    }
+    bs = bs == 2 ? 0 : bs + 1;
+    colsum_step(bcur);
+    if (wm == 1) {
+      if (u + 2 < nk) vmcnt_keep<NA + NB>();
+      else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    }
+    // Retire this interval's LDS reads BEFORE the barrier: right after it the
+    // other group restages the buffer just read (group 0 DMAs tile u+1 over
+    // tile u-1, group 1 tile u+2 over tile u), and a read still queued in
+    // the LDS when that DMA lands returns the new tile -- an intermittent
+    // wrong accumulator (tools/gemm_round_screen.py caught it: ~1 launch in
+    // 3 of one shape).  Guide rule: restage one phase after a read only when
+    // an lgkmcnt before the reading phase's barrier retired it.
+    // The wait is the builtin, not asm, so that the compiler's own counting
+    // sees it: the fold adds below and the MFMAs after the barrier then need
+    // no further lgkmcnt wait, and this is the interval's only one.
+    __builtin_amdgcn_s_waitcnt(kWaitLgkm0);
+    rowsum_add(rv);
+    __builtin_amdgcn_sched_barrier(0);
+    __builtin_amdgcn_s_barrier();
+    __builtin_amdgcn_sched_barrier(0);
+    __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+    for (int s = 0; s < 2; ++s)
 #pragma unroll
       for (int ii = 0; ii < 8; ++ii)
 #pragma unroll
-        for (int s = 0; s < 2; ++s)
-          af[ii][s] = AH ? frag<false, 128>(cur + wm * (kTileBytes / 2), 16 * ii, s, lane)
-                         : frag<A_KC, 256>(cur, wm * 128 + 16 * ii, s, lane);
-#pragma unroll
-      for (int j = 0; j < NJ; ++j)
-#pragma unroll
-        for (int s = 0; s < 2; ++s) bq[j][s] = frag<B_KC, W>(bcur, wn * WN + 16 * j, s, lane);
-      // row fold: read here, added below the DMA issue (the column fold runs there whole)
-      s16x4 rv;
-      rowsum_read(cur, rv);
-      if (X == kXEmit && A_KC && ej >= 0) emit_store(kt0 + u, ej, ea, eb);
-      ekt = ekt + 1 == ntn ? 0 : ekt + 1;
-      // The DMA issue needs nothing but scalars already in registers (kc: no
-      // kernel-argument load, no division, no wait), so it goes out while the
-      // fragment reads above are still in flight.
-      const int ahead = wm == 0 ? 1 : 2;  // the tile this group stages now
-      if (u + ahead < nk) {
-        char* dst = wm == 0 ? nxt : cur;
-        stage_fast<256>(kc.a, offA, dst, shA);
-        int bn = bs + ahead;
-        if (bn >= 3) bn -= 3;
-        stage_fast<W>(kc.b, offB, B3 ? bslot(bn) : dst + kTileBytes, shB);
-        kc.next(g);  // a segment crossing loads the pointers of the segment after: retired by the wait below
-      }
-      bs = bs == 2 ? 0 : bs + 1;
-      colsum_step(bcur);
-      if (wm == 1) {
-        if (u + 2 < nk) vmcnt_keep<NA + NB>();
-        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      }
-      // Retire this interval's LDS reads BEFORE the barrier: right after it the
-      // other group restages the buffer just read (group 0 DMAs tile u+1 over
-      // tile u-1, group 1 tile u+2 over tile u), and a read still queued in
-      // the LDS when that DMA lands returns the new tile -- an intermittent
-      // wrong accumulator (tools/gemm_round_screen.py caught it: ~1 launch in
-      // 3 of one shape).  Guide rule: restage one phase after a read only when
-      // an lgkmcnt before the reading phase's barrier retired it.
-      // The wait is the builtin, not asm, so that the compiler's own counting
-      // sees it: the fold adds below and the MFMAs after the barrier then need
-      // no further lgkmcnt wait, and this is the interval's only one.
-      __builtin_amdgcn_s_waitcnt(kWaitLgkm0);
-      rowsum_add(rv);
-      __builtin_amdgcn_sched_barrier(0);
-      __builtin_amdgcn_s_barrier();
-      __builtin_amdgcn_sched_barrier(0);
-      __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-      for (int s = 0; s < 2; ++s)
-#pragma unroll
-        for (int ii = 0; ii < 8; ++ii)
-#pragma unroll
-          for (int j = 0; j < NJ; ++j)
-            acc[ii][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[ii][s], bq[j][s], acc[ii][j], 0, 0, 0);
-      __builtin_amdgcn_s_setprio(0);
-      if (wm == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __builtin_amdgcn_sched_barrier(0);
-      __builtin_amdgcn_s_barrier();
-      __builtin_amdgcn_sched_barrier(0);
-    }
-    if (wm == 0) __builtin_amdgcn_s_barrier();  // equalise the barrier count
-  } else
-
-  if constexpr (PP == 3) {
-    // Half-tile ping-pong: as PP = 2, but a K-tile is 2 phases of 32 MFMAs
-    // (one 64-row half of the wave's 128x64 tile each, all NJ column tiles:
-    // A fragments read in both phases, B in phase 0 and kept), so the two
-    // barriers of a phase are paid once per 512 MFMA cycles instead of 256.
-    // Intervals (global count, group 1 one behind): group 0 loads in 4u and
-    // 4u+2, group 1 in 4u+1 and 4u+3.  A read issued before a DMA into the
-    // same bytes returns the old bytes (same wave: program order; another
-    // wave: a barrier between), so a region may be restaged by a DMA issued
-    // after the barrier that follows its last read's ISSUE:
-    //   * the A region of tile u-1's buffer is last read by group 1 in 4u-1
-    //     (its phase-1 load): group 1 restages it with A(u+1) right there,
-    //     after its own reads (tile u+1 = tile u-1's buffer), group 0 in 4u;
-    //   * the B region of tile u's buffer is last read by group 1 in 4u+1:
-    //     both groups stage B(u+2) into it in their phase-1 loads (4u+2/4u+3).
-    // Every wave drains what tile u+1 needs before the barrier ending 4u+3:
-    // group 0 after its phase-1 MFMAs (vmcnt(NB): B(u+2) may be in flight),
-    // group 1 in its phase-1 load (vmcnt(NA + NB): A(u+2) and B(u+2)).
-    // DMA budget: 4-6 intervals (~2-3k cycles) per piece.
-    if (nk > 1) {
-      if (wm == 1) vmcnt_keep<NA + NB>();
-      else vmcnt_keep<NB>();
-    } else {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
+        for (int j = 0; j < NJ; ++j)
+          acc[ii][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[ii][s], bq[j][s], acc[ii][j], 0, 0, 0);
+    __builtin_amdgcn_s_setprio(0);
+    if (wm == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __builtin_amdgcn_sched_barrier(0);
     __builtin_amdgcn_s_barrier();
-    if (wm == 1) __builtin_amdgcn_s_barrier();  // stagger group 1 by one interval
-    bf16x8 af[4][2], bq[NJ][2];
-    for (int u = 0; u < nk; ++u) {
-      char* cur = smem + (u & 1) * kBuf;
-      char* nxt = smem + ((u + 1) & 1) * kBuf;
-      const bool more = u + 1 < nk, lead = u + 2 < nk;
-#pragma unroll
-      for (int ph = 0; ph < 2; ++ph) {
-        // ---- load interval ----
-#pragma unroll
-        for (int ii = 0; ii < 4; ++ii)
-#pragma unroll
-          for (int s = 0; s < 2; ++s) af[ii][s] = frag<A_KC, 256>(cur, wm * 128 + ph * 64 + 16 * ii, s, lane);
-        if (ph == 0) rowsum_step(cur);
-        if (ph == 0) {
-#pragma unroll
-          for (int j = 0; j < NJ; ++j)
-#pragma unroll
-            for (int s = 0; s < 2; ++s) bq[j][s] = frag<B_KC, W>(cur + kTileBytes, wn * WN + 16 * j, s, lane);
-          if (wm == 0 && more) {
-            stage_fast<256>(tile_at(u + 1).a, offA, nxt, wave);
-          }
-        } else if (lead) {
-          if (wm == 1) {
-            stage_fast<256>(tile_at(u + 2).a, offA, cur, wave);
-          }
-          stage_fast<W>(tile_at(u + 2).b, offB, cur + kTileBytes, wave);
-        }
-        if (ph == 1 && wm == 1) {
-          if (lead) vmcnt_keep<NA + NB>();
-          else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        }
-        __builtin_amdgcn_sched_barrier(0);
-        __builtin_amdgcn_s_barrier();
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_sched_barrier(0);
-        // ---- MFMA interval ----
-        __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-        for (int s = 0; s < 2; ++s)
-#pragma unroll
-          for (int ii = 0; ii < 4; ++ii)
-#pragma unroll
-            for (int j = 0; j < NJ; ++j)
-              acc[ph * 4 + ii][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[ii][s], bq[j][s], acc[ph * 4 + ii][j], 0, 0, 0);
-        __builtin_amdgcn_s_setprio(0);
-        if (ph == 1 && wm == 0) {
-          if (lead) vmcnt_keep<NB>();
-          else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        }
-        __builtin_amdgcn_sched_barrier(0);
-        __builtin_amdgcn_s_barrier();
-        __builtin_amdgcn_sched_barrier(0);
-      }
-    }
-    if (wm == 0) __builtin_amdgcn_s_barrier();  // equalise the barrier count
-  } else if constexpr (PP) {
-    if (LEADB && nk > 1) vmcnt_keep<NB>();
-    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    if (wm == 1) __builtin_amdgcn_s_barrier();  // stagger group 1 by one interval
-    bf16x8 af[4][2], bf[2][JJ][2];
-    for (int u = 0; u < nk; ++u) {
-      const char* cur = smem + (u & 1) * kBuf;
-      char* nxt = smem + ((u + 1) & 1) * kBuf;
-      const bool more = u + 1 < nk;
-#pragma unroll
-      for (int ph = 0; ph < 4; ++ph) {
-        const int qm = ph >= 2 ? 1 : 0;
-        const int qn = (ph == 1 || ph == 2) ? 1 : 0;
-        // ---- load interval: this cluster's fragments, then staging DMA ----
-        if (ph == 0 || ph == 2) {
-#pragma unroll
-          for (int ii = 0; ii < 4; ++ii)
-#pragma unroll
-            for (int s = 0; s < 2; ++s) af[ii][s] = frag<A_KC, 256>(cur, wm * 128 + qm * 64 + 16 * ii, s, lane);
-        }
-        if (ph == 0) rowsum_step(cur);
-        if (ph == 0 || ph == 1) {
-#pragma unroll
-          for (int jj = 0; jj < JJ; ++jj)
-#pragma unroll
-            for (int s = 0; s < 2; ++s)
-              bf[qn][jj][s] = frag<B_KC, W>(cur + kTileBytes, wn * WN + qn * (WN / 2) + 16 * jj, s, lane);
-        }
-        if (ph == 0 && more) {
-          stage_fast<256>(tile_at(u + 1).a, offA, nxt, wave);
-        }
-        if (!LEADB && ph == 1 && more) {
-          stage_fast<W>(tile_at(u + 1).b, offB, nxt + kTileBytes, wave);
-        }
-        const bool lead = LEADB && u + 2 < nk;  // a B DMA two tiles ahead is issued this tile
-        if (ph == 3 && lead) {
-          stage_fast<W>(tile_at(u + 2).b, offB, const_cast<char*>(cur) + kTileBytes, wave);
-        }
-        if (ph == 3 && wm == 1) {
-          if (lead) vmcnt_keep<NB>();
-          else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        }
-        __builtin_amdgcn_sched_barrier(0);
-        __builtin_amdgcn_s_barrier();
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_sched_barrier(0);
-        // ---- MFMA interval ----
-        __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-        for (int s = 0; s < 2; ++s)
-#pragma unroll
-          for (int ii = 0; ii < 4; ++ii)
-#pragma unroll
-            for (int jj = 0; jj < JJ; ++jj)
-              acc[qm * 4 + ii][qn * JJ + jj] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-                  af[ii][s], bf[qn][jj][s], acc[qm * 4 + ii][qn * JJ + jj], 0, 0, 0);
-        __builtin_amdgcn_s_setprio(0);
-        if (ph == 3 && wm == 0) {
-          if (lead) vmcnt_keep<NB>();
-          else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        }
-        __builtin_amdgcn_sched_barrier(0);
-        __builtin_amdgcn_s_barrier();
-        __builtin_amdgcn_sched_barrier(0);
-      }
-    }
-    if (wm == 0) __builtin_amdgcn_s_barrier();  // equalise the barrier count
-  } else {
-  for (int kt = 0; kt < nk; ++kt) {
-    // Tile kt has landed (every wave drained its own DMA) and every wave is
-    // done reading the buffer the next prefetch overwrites.
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (kt + 1 < nk) {
-      char* nxt = smem + ((kt + 1) & 1) * kBuf;
-      stage_fast<256>(tile_at(kt + 1).a, offA, nxt, wave);
-      stage_fast<W>(tile_at(kt + 1).b, offB, nxt + kTileBytes, wave);
-    }
-    const char* cur = smem + (kt & 1) * kBuf;
-    rowsum_step(cur);
-#pragma unroll
-    for (int s = 0; s < 2; ++s) {
-      bf16x8 bfr[NJ];
-#pragma unroll
-      for (int t = 0; t < NJ; ++t) bfr[t] = frag<B_KC, W>(cur + kTileBytes, wn * WN + 16 * t, s, lane);
-#pragma unroll
-      for (int i = 0; i < 8; ++i) {
-        const bf16x8 af = frag<A_KC, 256>(cur, wm * 128 + 16 * i, s, lane);
-#pragma unroll
-        for (int j = 0; j < NJ; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af, bfr[j], acc[i][j], 0, 0, 0);
-      }
-    }
+    __builtin_amdgcn_sched_barrier(0);
   }
-  }
+  if (wm == 0) __builtin_amdgcn_s_barrier();  // equalise the barrier count
 
   if (rsum) {  // K-rows -> one sum per row: lanes (xor over the K-row bits), then the 4 group-0 waves through LDS
     __syncthreads();  // every wave is done reading the operand buffers
@@ -1367,301 +1103,6 @@ __global__ void __launch_bounds__(kThreads, 1) gemm256_kernel(GemmArgs g) {
                          EPI == kEpiStoreBf16 ? reinterpret_cast<const bf16_t*>(g.res) : nullptr, g.ldr);
 }
 
-#ifdef MIPIPE_GEMM_AB
-// ============================================================================
-// 4-wave variant: the same 256x256x64 block tile, LDS
-// images, staging offsets and epilogues, computed by 4 waves instead of 8 --
-// 2 M x 2 N, a 128x128 tile per wave (8x8 v_mfma_f32_16x16x32_bf16
-// accumulators: 256 registers, AGPRs), ONE wave per SIMD.  Per k32-step a
-// wave reads 16 fragments (8 A + 8 B) for 64 MFMAs, 256 B of LDS per MFMA
-// against the 8-wave kernel's 384 (128x64 wave tile): a third less LDS
-// traffic and issue.  With no partner wave on the SIMD, the LDS latency is
-// hidden inside the wave: the fragments of the next k32-step are read
-// between the MFMAs of this one (one read after every 4th MFMA), and the
-// K-tile two ahead is staged by LDS-DMA in the same stream (one 1 KiB piece
-// after every 4th MFMA of the second k-step).  One barrier per K-tile,
-// between its two k-steps:
-//   k-step 0 of tile u:  MFMAs on fragments (u, 0); reads of (u, 1) from cur
-//   wait: this wave's DMAs of tile u+1 landed, its reads of cur retired
-//   barrier            -> cur is free for restaging, tile u+1 readable
-//   k-step 1 of tile u:  MFMAs on (u, 1); reads of (u+1, 0) from nxt; DMA of
-//                        tile u+2 into cur
-// Past the last tiles the DMA restages the last tile and the reads read the
-// other buffer (both harmless: nothing reads them), so the stream has no
-// branches.  Compiler scheduling is pinned by sched_barriers between the
-// MFMA groups.  A^T emission is not supported (launch_big_w keeps those on
-// the 8-wave kernel).
-template <bool A_KC, bool B_KC, int EPI, int ACT, bool EXTRA, int X = 0>
-__global__ void __launch_bounds__(256, 1) gemm4w_kernel(GemmArgs g) {
-  constexpr int W = 256, NJ = 8, WN = 128;
-  constexpr int kBuf = 2 * kTileBytes;  // A + B tile
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wm = wave >> 1, wn = wave & 1;
-  int tm, tn;
-  tile_coords((g.M + BM - 1) / BM, (g.N + W - 1) / W, tm, tn, g.group_m);
-  tm = __builtin_amdgcn_readfirstlane(tm);
-  tn = __builtin_amdgcn_readfirstlane(tn);
-  const int m0 = tm * BM, n0 = tn * W;
-  f32x4 acc[8][NJ];
-#pragma unroll
-  for (int i = 0; i < 8; ++i)
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-  // fused bias gradient, A side (GemmArgs::rowsum): as the 8-wave kernel's
-  // group 0, with all 256 threads
-  const bool rsum = g.rowsum != nullptr && tn < 16 && !A_KC;
-  float rs[4] = {0.f, 0.f, 0.f, 0.f};
-  auto rowsum_step = [&](const char* tile) {
-    if (rsum) {
-      const int r = tid >> 2, c8 = 4 * tn + (tid & 3);
-      const s16x4 v = *reinterpret_cast<const s16x4*>(tile + ic_off_w<256>(r, c8));
-#pragma unroll
-      for (int e = 0; e < 4; ++e) rs[e] += __uint_as_float((uint32_t)(uint16_t)v[e] << 16);
-    }
-  };
-  // fused bias gradient, B side (GemmArgs::colsum): the 8-wave kernel's two
-  // group slices, both summed by these 256 threads
-  const int tiles_m = (g.M + BM - 1) / BM;
-  const int cm_log = __builtin_amdgcn_readfirstlane(2 * tiles_m * 16 >= W ? 0 : 2 * tiles_m * 32 >= W ? 1
-                                                    : 2 * tiles_m * 64 >= W ? 2 : 3);
-  const bool csum0 = X == kXColsum && !B_KC && g.colsum != nullptr && tm < (W / 16 >> cm_log);
-  const bool csum1 = X == kXColsum && !B_KC && g.colsum != nullptr && tm + tiles_m < (W / 16 >> cm_log);
-  float cs[2][4] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
-  auto colsum_step = [&](const char* btile) {
-#pragma unroll
-    for (int q = 0; q < 2; ++q) {
-      if (q == 0 ? csum0 : csum1) {
-        const int csl = tm + tiles_m * q;
-        const int qq = tid & ((4 << cm_log) - 1), r0 = tid >> (2 + cm_log);
-        for (int j = 0; j < (1 << cm_log); ++j) {
-          const s16x4 v = *reinterpret_cast<const s16x4*>(
-              btile + ic_off_w<W>(r0 + (j << (6 - cm_log)), (4 << cm_log) * csl + qq));
-#pragma unroll
-          for (int e = 0; e < 4; ++e) cs[q][e] += __uint_as_float((uint32_t)(uint16_t)v[e] << 16);
-        }
-      }
-    }
-  };
-
-  int kt0 = 0, nk = g.K / BK;
-  if (g.k_splits > 1) {
-    const int total = nk;
-    kt0 = (int)blockIdx.y * total / g.k_splits;
-    nk = ((int)blockIdx.y + 1) * total / g.k_splits - kt0;
-  }
-  // staging: wave w takes the 8-wave shares w and w + 4 of each operand tile
-  uint32_t offA0[4], offA1[4], offB0[4], offB1[4];
-  stage_offsets<A_KC, 256>(g.lda, m0, g.M, wave, lane, offA0);
-  stage_offsets<A_KC, 256>(g.lda, m0, g.M, wave + 4, lane, offA1);
-  stage_offsets<B_KC, W>(g.ldb, n0, g.N, wave, lane, offB0);
-  stage_offsets<B_KC, W>(g.ldb, n0, g.N, wave + 4, lane, offB1);
-  // Operand bases of K-tile kt (scalar).  Every GemmArgs field the loop needs
-  // is read into a local first: the DMA asm clobbers "memory", and a field
-  // read after it is re-loaded from the kernel arguments -- an s_load whose
-  // s_waitcnt lgkmcnt(0) also drains every LDS read in flight (that cost the
-  // first version of this kernel 20 %).  The bases of the tile staged in k-step
-  // 1 are computed at the top of the iteration, before any DMA of it.
-  const int64_t lda = g.lda, ldb = g.ldb;
-  const int seg_k = g.seg_k;
-  const char* const gA = reinterpret_cast<const char*>(g.A);
-  const char* const gB = reinterpret_cast<const char*>(g.B);
-  auto tile_bases = [&](int kt, const char*& bA, const char*& bB) {
-    int kl = (kt0 + kt) * BK;
-    const char *a = gA, *b = gB;
-    if (seg_k > 0) {  // segmented operands: the segment's pointers (the only scalar loads in the loop)
-      const int sg = kl / seg_k;
-      kl -= sg * seg_k;
-      a = reinterpret_cast<const char*>(g.a_seg[sg]);
-      b = reinterpret_cast<const char*>(g.b_seg[sg]);
-    }
-    bA = a + (A_KC ? (int64_t)kl * 2 : (int64_t)kl * lda * 2);
-    bB = b + (B_KC ? (int64_t)kl * 2 : (int64_t)kl * ldb * 2);
-  };
-  // piece d (0-15) of a K-tile into buffer buf: A shares (d 0-7), then B
-  auto stage_piece = [&](const char* bA, const char* bB, char* buf, int d) {
-    if (d < 8) {
-      const int sh = d < 4 ? wave : wave + 4;
-      glds16_saddr(bA, d < 4 ? offA0[d & 3] : offA1[d & 3], buf + (sh * 4 + (d & 3)) * 1024);
-    } else {
-      const int sh = d < 12 ? wave : wave + 4;
-      glds16_saddr(bB, d < 12 ? offB0[d & 3] : offB1[d & 3], buf + kTileBytes + (sh * 4 + (d & 3)) * 1024);
-    }
-  };
-  const char *bA, *bB;
-  tile_bases(0, bA, bB);
-  const char *bA1 = bA, *bB1 = bB;
-  if (nk > 1) tile_bases(1, bA1, bB1);
-#pragma unroll
-  for (int d = 0; d < 16; ++d) stage_piece(bA, bB, smem, d);
-  if (nk > 1) {
-#pragma unroll
-    for (int d = 0; d < 16; ++d) stage_piece(bA1, bB1, smem + kBuf, d);
-    vmcnt_keep<16>();
-  } else {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  }
-  __builtin_amdgcn_s_barrier();
-  bf16x8 fa[2][8], fb[2][8];  // [k-step][tile]
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    fa[0][i] = frag<A_KC, 256>(smem, wm * 128 + 16 * i, 0, lane);
-    fb[0][i] = frag<B_KC, W>(smem + kTileBytes, wn * WN + 16 * i, 0, lane);
-  }
-  for (int u = 0; u < nk; ++u) {
-    char* cur = smem + (u & 1) * kBuf;
-    char* nxt = smem + ((u + 1) & 1) * kBuf;
-    __builtin_amdgcn_sched_barrier(0);
-    // ---- k-step 0: MFMAs on (u, 0), fragment reads of (u, 1) ----
-#pragma unroll
-    for (int i = 0; i < 8; ++i)
-#pragma unroll
-      for (int j = 0; j < NJ; ++j) {
-        acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[0][i], fb[0][j], acc[i][j], 0, 0, 0);
-        // read q after MFMA 3 q: all 16 issued by MFMA 45, so they have landed by
-        // the k-step's end (the wait before the barrier, and the compiler's wait
-        // at the top of the next k-step, find them retired)
-        const int gi = NJ * i + j;
-        if (gi % 3 == 0 && gi / 3 < 16) {
-          const int q = gi / 3;  // read order A0, B0-B7, A1-A7: the order the MFMAs use them
-          const int ia = q == 0 ? 0 : q - 8;
-          if (q == 0 || q > 8) fa[1][ia] = frag<A_KC, 256>(cur, wm * 128 + 16 * ia, 1, lane);
-          else fb[1][q - 1] = frag<B_KC, W>(cur + kTileBytes, wn * WN + 16 * (q - 1), 1, lane);
-        }
-        __builtin_amdgcn_sched_barrier(0);
-      }
-    rowsum_step(cur);
-    colsum_step(cur + kTileBytes);
-    // Bases of tile u+2 (past the end: the last tile again), whose scalar
-    // loads (segmented operands) the wait below drains with the LDS reads: no
-    // scalar load is ever pending where the compiler counts LDS reads, so its
-    // own waits stay counted (lgkmcnt(N)) rather than lgkmcnt(0).
-    __builtin_amdgcn_sched_barrier(0);
-    const char *sA, *sB;
-    tile_bases(u + 2 < nk ? u + 2 : nk - 1, sA, sB);
-    // this wave's DMAs of tile u+1 have landed and its reads of cur retired;
-    // after the barrier cur may be restaged and nxt read
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_sched_barrier(0);
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_sched_barrier(0);
-    // ---- k-step 1: MFMAs on (u, 1), reads of (u+1, 0), DMA of tile u+2 ----
-#pragma unroll
-    for (int i = 0; i < 8; ++i)
-#pragma unroll
-      for (int j = 0; j < NJ; ++j) {
-        acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[1][i], fb[1][j], acc[i][j], 0, 0, 0);
-        const int gi = NJ * i + j;
-        // DMA piece after every 4th MFMA from 1, fragment read after every 4th from 3
-        // (harness schedule 2: tools/micro/gemm4w.hip, profiles/gemm4w_r5.txt)
-        if ((gi & 3) == 1) stage_piece(sA, sB, cur, gi >> 2);
-        if ((gi & 3) == 3) {
-          const int q = gi >> 2, ia = q == 0 ? 0 : q - 8;
-          if (q == 0 || q > 8) fa[0][ia] = frag<A_KC, 256>(nxt, wm * 128 + 16 * ia, 0, lane);
-          else fb[0][q - 1] = frag<B_KC, W>(nxt + kTileBytes, wn * WN + 16 * (q - 1), 0, lane);
-        }
-        __builtin_amdgcn_sched_barrier(0);
-      }
-  }
-  asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-
-  if (rsum) {  // K-rows -> one sum per row: lanes (xor over the K-row bits), then the 4 waves through LDS
-    __syncthreads();
-    float* red = reinterpret_cast<float*>(smem);
-#pragma unroll
-    for (int e = 0; e < 4; ++e)
-#pragma unroll
-      for (int o = 4; o < 64; o <<= 1) rs[e] += __shfl_xor(rs[e], o, 64);
-    if (lane < 4)
-#pragma unroll
-      for (int e = 0; e < 4; ++e) red[wave * 16 + 4 * lane + e] = rs[e];
-    __syncthreads();
-    if (tid < 16) {
-      const float v = red[tid] + red[16 + tid] + red[32 + tid] + red[48 + tid];
-      const int row = m0 + 16 * tn + tid;
-      if (row < g.M) g.rowsum[row] += v;
-    }
-  }
-  if (X == kXColsum && g.colsum != nullptr) {  // the 8-wave kernel's reduction, slice q in place of group q
-    __syncthreads();
-    const int sw = 16 << cm_log;
-    float* red = reinterpret_cast<float*>(smem) + 64;  // [2 slices x 4 waves][sw columns]
-#pragma unroll
-    for (int q = 0; q < 2; ++q) {
-#pragma unroll
-      for (int e = 0; e < 4; ++e)
-        for (int o = 4 << cm_log; o < 64; o <<= 1) cs[q][e] += __shfl_xor(cs[q][e], o, 64);
-      if (lane < (4 << cm_log))
-#pragma unroll
-        for (int e = 0; e < 4; ++e) red[(4 * q + wave) * sw + 4 * lane + e] = cs[q][e];
-    }
-    __syncthreads();
-    for (int t = tid; t < 2 * sw; t += 256) {
-      const int gq = t >> (4 + cm_log), c = t & (sw - 1);
-      const int sl = tm + tiles_m * gq;
-      float v = 0.f;
-#pragma unroll
-      for (int w = 0; w < 4; ++w) v += red[(4 * gq + w) * sw + c];
-      const int col = n0 + sw * sl + c;
-      if (sl < (W / 16 >> cm_log) && col < g.N) {
-        if (g.k_splits > 1) g.colsum[(int64_t)blockIdx.y * g.N + col] = v;
-        else g.colsum[col] += v;
-      }
-    }
-  }
-  // ---- epilogue (as the 8-wave kernel's, on the 128x128 wave layout) ----
-  const int quad = lane >> 4, col_in = lane & 15;
-  __syncthreads();
-  if (EPI == kEpiStoreBf16 && EXTRA) {
-    const int ncol = n0 + wn * WN + col_in;
-    if (g.bias != nullptr) {
-#pragma unroll
-      for (int j = 0; j < NJ; ++j) {
-        const float b = ncol + 16 * j < g.N ? bf2f(reinterpret_cast<const bf16_t*>(g.bias)[ncol + 16 * j]) : 0.f;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) acc[i][j] += b;
-      }
-    }
-    staged_store_act<ACT, W, NJ, 256, true>(smem, acc, wm, wn, lane, tid, m0, n0, g);
-    return;
-  }
-  if (EPI == kEpiStoreBf16 && (ACT != kActNone || g.bias != nullptr)) {
-    const int ncol = n0 + wn * WN + col_in, nrow = m0 + wm * 128 + 4 * quad;
-    const float pscale = g.p > 0.f ? 1.f / (1.f - g.p) : 1.f;
-    const EpiParams ep{g.seed, g.offset, g.N, g.p, pscale, g.threshold, g.mask_row0, g.mask_col0,
-                       g.mask_ld > 0 ? g.mask_ld : g.N};
-    float bias[NJ];
-#pragma unroll
-    for (int j = 0; j < NJ; ++j)
-      bias[j] = (g.bias != nullptr && ncol + 16 * j < g.N) ? bf2f(reinterpret_cast<const bf16_t*>(g.bias)[ncol + 16 * j]) : 0.f;
-    epi_rows<0, ACT, NJ, EXTRA>(ep, acc, nrow, ncol, bias);
-    epi_rows<1, ACT, NJ, EXTRA>(ep, acc, nrow, ncol, bias);
-    epi_rows<2, ACT, NJ, EXTRA>(ep, acc, nrow, ncol, bias);
-    epi_rows<3, ACT, NJ, EXTRA>(ep, acc, nrow, ncol, bias);
-    epi_rows<4, ACT, NJ, EXTRA>(ep, acc, nrow, ncol, bias);
-    epi_rows<5, ACT, NJ, EXTRA>(ep, acc, nrow, ncol, bias);
-    epi_rows<6, ACT, NJ, EXTRA>(ep, acc, nrow, ncol, bias);
-    epi_rows<7, ACT, NJ, EXTRA>(ep, acc, nrow, ncol, bias);
-  }
-  void* out = EPI == kEpiStoreBf16 ? g.C
-                                   : reinterpret_cast<void*>(reinterpret_cast<float*>(g.C) +
-                                                             (int64_t)blockIdx.y * g.M * g.ldc);
-  if (EPI == kEpiStoreBf16 && g.dact_in != nullptr)
-    staged_store<EPI, W, NJ, 256, true>(smem, acc, wm, wn, lane, tid, m0, n0, g.M, g.N, g.ldc, out,
-                                  reinterpret_cast<const bf16_t*>(g.res), g.ldr,
-                                  reinterpret_cast<const bf16_t*>(g.dact_in), g.ldd, g.dact, g.dact_scale);
-  else if (EPI != kEpiStoreBf16 && g.trans_c && g.k_splits <= 1)
-    staged_store<EPI, W, NJ, 256, true>(smem, acc, wm, wn, lane, tid, m0, n0, g.M, g.N, g.ldc, out, nullptr, 0, nullptr, 0,
-                                  0, 1.f, true);
-  else
-    staged_store<EPI, W, NJ, 256, true>(smem, acc, wm, wn, lane, tid, m0, n0, g.M, g.N, g.ldc, out,
-                                  EPI == kEpiStoreBf16 ? reinterpret_cast<const bf16_t*>(g.res) : nullptr, g.ldr);
-}
-#endif  // MIPIPE_GEMM_AB (the 4-wave kernel: A/B builds only, profiles/gemm4w_r5.txt)
-
 }  // namespace big
 
 int big_tiles(const GemmArgs& g, int w) { return ((g.M + big::BM - 1) / big::BM) * ((g.N + w - 1) / w); }
@@ -1698,104 +1139,41 @@ int big_width(const GemmArgs& g) {
   return 0.75 * r128 < 1.0 * r256 ? 128 : 256;
 }
 
-template <bool A_KC, bool B_KC, int EPI, int ACT, int PP, int W, bool EXTRA, int X = 0>
+template <bool A_KC, bool B_KC, int EPI, int ACT, int W, bool EXTRA, int X = 0>
 void launch_big(const GemmArgs& g, hipStream_t s) {
-  constexpr int smem = big::smem_bytes<B_KC, PP, W>();
+  constexpr int smem = big::smem_bytes<B_KC, W>();
   static bool attr_set = false;
   if (!attr_set) {
     (void)hipFuncSetAttribute(
-        reinterpret_cast<const void*>(&big::gemm256_kernel<A_KC, B_KC, EPI, ACT, PP, W, EXTRA, X>),
+        reinterpret_cast<const void*>(&big::gemm256_kernel<A_KC, B_KC, EPI, ACT, W, EXTRA, X>),
         hipFuncAttributeMaxDynamicSharedMemorySize, smem);
     attr_set = true;
   }
-  hipLaunchKernelGGL((big::gemm256_kernel<A_KC, B_KC, EPI, ACT, PP, W, EXTRA, X>), dim3(big_tiles(g, W), g.k_splits),
+  hipLaunchKernelGGL((big::gemm256_kernel<A_KC, B_KC, EPI, ACT, W, EXTRA, X>), dim3(big_tiles(g, W), g.k_splits),
                      dim3(big::kThreads), smem, s, g);
 }
 
-// The product build instantiates the default main loop only (schedule 7, the
-// whole-tile ping-pong).  The A/B schedules 0-6 are compiled in only with
-// -DMIPIPE_GEMM_AB (python -m mipipe.build --gemm-ab), for tools/gemm_sched_ab.py
-// and the like; without it gemm_set_schedule() accepts 7 alone.
-// 256-wide blocks: the 4-wave kernel (gemm4w_kernel, -DMIPIPE_GEMM_AB builds
-// only: 2-11 % slower at the power cap, profiles/gemm4w_r5.txt) or the 8-wave
-// one.  gemm_set_waves(4 / 8) or MIPIPE_GEMM_WAVES picks in an A/B build; the
-// product build has the 8-wave kernel alone.
-int g_gemm_waves = -1;
-int gemm_waves() {
-#ifdef MIPIPE_GEMM_AB
-  if (g_gemm_waves < 0) {
-    const char* e = getenv("MIPIPE_GEMM_WAVES");
-    g_gemm_waves = e ? atoi(e) : 0;
-  }
-  return g_gemm_waves == 4 ? 4 : 8;
-#else
-  return 8;
-#endif
-}
-
-#ifdef MIPIPE_GEMM_AB
-template <bool A_KC, bool B_KC, int EPI, int ACT, bool EXTRA, int X = 0>
-void launch_4w(const GemmArgs& g, hipStream_t s) {
-  constexpr int smem = big::kSmemBytes;  // the epilogue's staging image (130 KiB); the main loop uses 128 KiB
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&big::gemm4w_kernel<A_KC, B_KC, EPI, ACT, EXTRA, X>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-    attr_set = true;
-  }
-  hipLaunchKernelGGL((big::gemm4w_kernel<A_KC, B_KC, EPI, ACT, EXTRA, X>), dim3(big_tiles(g, 256), g.k_splits),
-                     dim3(256), smem, s, g);
-}
-#endif
-
+// One kernel, 256 or 128 wide, plus its two main-loop extras (the compared-
+// and-lost loops and the 4-wave kernel are gone: see above gemm256_kernel).
 template <bool A_KC, bool B_KC, int EPI, int ACT, bool EXTRA>
 void launch_big_w(const GemmArgs& g, hipStream_t s) {
   const bool narrow = big_width(g) == 128;
-#ifdef MIPIPE_GEMM_AB
-  if (!narrow && g.at == nullptr && gemm_waves() == 4) {
-    if constexpr (A_KC && !B_KC && EPI != kEpiStoreBf16 && !EXTRA) {
-      if (g.colsum != nullptr) {
-        launch_4w<A_KC, B_KC, EPI, ACT, EXTRA, big::kXColsum>(g, s);
-        return;
-      }
-    }
-    launch_4w<A_KC, B_KC, EPI, ACT, EXTRA>(g, s);
-    return;
-  }
-#endif
   if constexpr (A_KC && B_KC && EPI == kEpiStoreBf16 && !(ACT == kActGelu && EXTRA)) {
     if (g.at != nullptr) {  // forward GEMM that also writes A^T (gemm_emit_ok)
-      if (narrow) launch_big<A_KC, B_KC, EPI, ACT, 4, 128, EXTRA, big::kXEmit>(g, s);
-      else launch_big<A_KC, B_KC, EPI, ACT, 4, 256, EXTRA, big::kXEmit>(g, s);
+      if (narrow) launch_big<A_KC, B_KC, EPI, ACT, 128, EXTRA, big::kXEmit>(g, s);
+      else launch_big<A_KC, B_KC, EPI, ACT, 256, EXTRA, big::kXEmit>(g, s);
       return;
     }
   }
   if constexpr (A_KC && !B_KC && EPI != kEpiStoreBf16 && !EXTRA) {
     if (g.colsum != nullptr) {  // transposed weight gradient with the bias fold
-      if (narrow) launch_big<A_KC, B_KC, EPI, ACT, 4, 128, EXTRA, big::kXColsum>(g, s);
-      else launch_big<A_KC, B_KC, EPI, ACT, 4, 256, EXTRA, big::kXColsum>(g, s);
+      if (narrow) launch_big<A_KC, B_KC, EPI, ACT, 128, EXTRA, big::kXColsum>(g, s);
+      else launch_big<A_KC, B_KC, EPI, ACT, 256, EXTRA, big::kXColsum>(g, s);
       return;
     }
   }
-#ifndef MIPIPE_GEMM_AB
-  if (narrow) launch_big<A_KC, B_KC, EPI, ACT, 4, 128, EXTRA>(g, s);
-  else launch_big<A_KC, B_KC, EPI, ACT, 4, 256, EXTRA>(g, s);
-#else
-  const int sc = big::gemm_sched();
-  const bool pp = sc == 1 || sc == 4 || sc == 6 || ((sc == 2 || sc == 3) && (A_KC || B_KC));
-  const bool lead = sc == 3 || sc == 4 || sc == 6;
-  const bool half = sc == 5 || (sc == 6 && (A_KC || B_KC));
-  if (sc == 7 && narrow) launch_big<A_KC, B_KC, EPI, ACT, 4, 128, EXTRA>(g, s);
-  else if (sc == 7) launch_big<A_KC, B_KC, EPI, ACT, 4, 256, EXTRA>(g, s);
-  else if (half && narrow) launch_big<A_KC, B_KC, EPI, ACT, 3, 128, EXTRA>(g, s);
-  else if (half) launch_big<A_KC, B_KC, EPI, ACT, 3, 256, EXTRA>(g, s);
-  else if (pp && lead && narrow) launch_big<A_KC, B_KC, EPI, ACT, 2, 128, EXTRA>(g, s);
-  else if (pp && lead) launch_big<A_KC, B_KC, EPI, ACT, 2, 256, EXTRA>(g, s);
-  else if (pp && narrow) launch_big<A_KC, B_KC, EPI, ACT, 1, 128, EXTRA>(g, s);
-  else if (pp) launch_big<A_KC, B_KC, EPI, ACT, 1, 256, EXTRA>(g, s);
-  else if (narrow) launch_big<A_KC, B_KC, EPI, ACT, 0, 128, EXTRA>(g, s);
-  else launch_big<A_KC, B_KC, EPI, ACT, 0, 256, EXTRA>(g, s);
-#endif
+  if (narrow) launch_big<A_KC, B_KC, EPI, ACT, 128, EXTRA>(g, s);
+  else launch_big<A_KC, B_KC, EPI, ACT, 256, EXTRA>(g, s);
 }
 
 int g_gemm_group = -1;  // MIPIPE_GEMM_G: tile-rows per ordering group (A/B); -1 unread, 0 default
@@ -1907,28 +1285,9 @@ void launch_act(const GemmArgs& g, hipStream_t s) {
 
 }  // namespace
 
-bool gemm_set_schedule(int mode) {
-#ifndef MIPIPE_GEMM_AB
-  if (mode != 7) return false;
-#else
-  if (mode < 0 || mode > 7) return false;
-#endif
-  big::g_gemm_sched = mode;
-  return true;
-}
-bool gemm_ab_build() {
-#ifdef MIPIPE_GEMM_AB
-  return true;
-#else
-  return false;
-#endif
-}
 void gemm_set_width(int w) { g_gemm_width = w; }
 void gemm_set_rounds(int on) { g_gemm_rounds = on; }
-void gemm_set_waves(int w) { g_gemm_waves = w; }  // 4 takes effect in -DMIPIPE_GEMM_AB builds only
-int gemm_get_waves() { return gemm_waves(); }
 void gemm_set_splitk(int n) { g_gemm_splitk = n; }
-int gemm_get_schedule() { return big::gemm_sched(); }
 
 bool gemm_rowsum_ok(const GemmArgs& g) {
   return !g.a_kc && (g.epi == kEpiAccumF32 || g.epi == kEpiStoreF32) && use_big(g) && gemm_splitk_factor(g) <= 1 &&

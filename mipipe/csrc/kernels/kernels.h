@@ -254,18 +254,11 @@ bool gemm_colsum_ok(const GemmArgs& g);
 // Split-K factor gemm_bf16 would use for g (1 = none); the caller provides
 // g.ws with k_splits * M * N floats when it is > 1.
 int gemm_splitk_factor(const GemmArgs& g);
-// Main-loop schedule of the 256x256 GEMM: 7 (default, the only one in the product build) = whole-tile
-// ping-pong.  A -DMIPIPE_GEMM_AB build also has 0 = one barrier per K-tile, 1 = 4-phase ping-pong,
-// 2 = 1 except the wgrad layout, 3 / 4 = 2 / 1 with the B operand staged two K-tiles ahead, 5 / 6 =
-// half-tile ping-pong (everywhere / on the K-contiguous layouts).  Returns false for a schedule not built.
-bool gemm_set_schedule(int mode);
-bool gemm_ab_build();
+// The 256-row GEMM has one main loop, the whole-tile ping-pong (gemm.hip, above gemm256_kernel, also
+// names what it was compared against); the switches below select between live paths.
 void gemm_set_width(int w);    // 256-row GEMM block width: 0 auto, 128, 256
 void gemm_set_rounds(int on);  // 1: multi-round grids launched one round at a time (default), 0: one launch
-void gemm_set_waves(int w);   // 256x256 GEMM blocks: 4 (gemm4w_kernel, -DMIPIPE_GEMM_AB builds only) or 8 waves; 0 default
-int gemm_get_waves();
 void gemm_set_splitk(int n);  // split-K factor: 0 off, 1 auto (gemm_splitk_factor), n >= 2 forced (A/B tools)
-int gemm_get_schedule();
 void gemm_bf16(const GemmArgs& g, hipStream_t s);
 // Same interface with fp32 operands (and fp32 bias / res / aux / C): v_mfma_f32_32x32x2_f32.
 bool gemm_f32_supported(int64_t M, int64_t N, int64_t K);

@@ -413,19 +413,12 @@ def test_gemm_layouts(k, a_kc, b_kc, M, N, K):
 
 
 @pytest.mark.parametrize("width", [256, 128])
-@pytest.mark.parametrize("sched", [0, 1, 2, 3, 4, 5, 6, 7])
-def test_gemm_main_loop_schedules(k, sched, width):
-    """Every 256x256 main loop built in (the product build: the default whole-tile
-    ping-pong; a --gemm-ab build also the per-tile barrier, ping-pong, the mixes,
-    ping-pong with the B lead) on every layout, for 1, 2, 3 and many K-tiles, edge
-    tiles, K-segments and the bf16 epilogue."""
+def test_gemm_main_loop(k, width):
+    """The main loop of the 256-row GEMM (whole-tile ping-pong), at both block
+    widths, on every layout, for 1, 2, 3 and many K-tiles, edge tiles,
+    K-segments and the bf16 epilogue."""
     from mipipe.ops import linear
 
-    if sched != 7 and not k.gemm_ab_build():
-        assert not k.gemm_set_schedule(sched)  # refused, not silently ignored
-        pytest.skip("A/B GEMM schedule not in the product build (python -m mipipe.build --gemm-ab)")
-    old = k.gemm_get_schedule()
-    assert k.gemm_set_schedule(sched)
     k.gemm_set_width(width)
     try:
         torch.manual_seed(7)
@@ -455,39 +448,30 @@ def test_gemm_main_loop_schedules(k, sched, width):
         ref = x.float() @ w.float().t() + bias.float() + r.float()
         assert torch.allclose(y.float(), ref, atol=3e-2, rtol=3e-2)
     finally:
-        k.gemm_set_schedule(old)
         k.gemm_set_width(0)
 
 
-@pytest.mark.parametrize("sched", [0, 4, 5, 6, 7])
-def test_wgrad_segments_fused_bias(k, sched):
+def test_wgrad_segments_fused_bias(k):
     """The bias gradient folded into the K-segmented weight-gradient GEMM
     (GemmArgs::rowsum): equal to the column sums of every dY, accumulated; a
     shape that cannot take the fold (< 16 tile columns, or split-K) returns
     False and leaves the bias gradient alone."""
-    if sched != 7 and not k.gemm_ab_build():
-        pytest.skip("A/B GEMM schedule not in the product build (python -m mipipe.build --gemm-ab)")
-    old = k.gemm_get_schedule()
-    assert k.gemm_set_schedule(sched)
-    try:
-        torch.manual_seed(11)
-        for N, Kin, T, nseg in [(520, 4096, 256, 3), (1000, 4104, 128, 18), (256, 512, 128, 2), (1024, 4096, 1024, 16)]:
-            dys = [torch.randn(T, N, device=DEV).to(torch.bfloat16) for _ in range(nseg)]
-            xs = [torch.randn(T, Kin, device=DEV).to(torch.bfloat16) for _ in range(nseg)]
-            main = torch.zeros(N, Kin, device=DEV)
-            bias = torch.full((N,), 0.5, device=DEV)
-            fused = k.linear_wgrad_segments(dys, xs, main, True, bias)
-            expect = sum(d.float().t() @ x.float() for d, x in zip(dys, xs))
-            assert ((main - expect).abs().max() / expect.abs().max()).item() < 1e-3, (N, Kin, sched)
-            if Kin < 4096:
-                assert not fused
-            if fused:
-                ref = 0.5 + sum(d.float().sum(0) for d in dys)
-                assert torch.allclose(bias, ref, atol=1e-2, rtol=1e-4), (N, Kin, sched, (bias - ref).abs().max())
-            else:
-                assert torch.all(bias == 0.5)
-    finally:
-        k.gemm_set_schedule(old)
+    torch.manual_seed(11)
+    for N, Kin, T, nseg in [(520, 4096, 256, 3), (1000, 4104, 128, 18), (256, 512, 128, 2), (1024, 4096, 1024, 16)]:
+        dys = [torch.randn(T, N, device=DEV).to(torch.bfloat16) for _ in range(nseg)]
+        xs = [torch.randn(T, Kin, device=DEV).to(torch.bfloat16) for _ in range(nseg)]
+        main = torch.zeros(N, Kin, device=DEV)
+        bias = torch.full((N,), 0.5, device=DEV)
+        fused = k.linear_wgrad_segments(dys, xs, main, True, bias)
+        expect = sum(d.float().t() @ x.float() for d, x in zip(dys, xs))
+        assert ((main - expect).abs().max() / expect.abs().max()).item() < 1e-3, (N, Kin)
+        if Kin < 4096:
+            assert not fused
+        if fused:
+            ref = 0.5 + sum(d.float().sum(0) for d in dys)
+            assert torch.allclose(bias, ref, atol=1e-2, rtol=1e-4), (N, Kin, (bias - ref).abs().max())
+        else:
+            assert torch.all(bias == 0.5)
 
 
 
