@@ -1223,17 +1223,29 @@ bool use_long(const Tensor& q, int S, int D) {
   return on && q.scalar_type() == at::kBFloat16 && attention_long_supported(S, D);
 }
 
+// Sliding-window attention (`window` keys per query, the query's own included; 0 = none): causal bf16 only,
+// and always on attention.hip's generic kernels.  A window that covers the sequence is none.
+int attn_window(const char* who, int64_t window, bool causal, const Tensor& q, int S) {
+  MP_CHECK(window >= 0, who, ": window must be >= 0 (0 = none), got ", window);
+  if (window == 0) return 0;
+  MP_CHECK(causal, who, ": a sliding window needs causal attention");
+  MP_CHECK(q.scalar_type() == at::kBFloat16, who, ": sliding-window attention runs on the bf16 kernels only, got ",
+           q.scalar_type());
+  return window >= S ? 0 : (int)window;
+}
+
 // Returns (o, lse, seed, offset, dropout keep bits): the bits tensor (int32
 // [B*H, S/32, S]) is non-empty only for the long-sequence kernels with p > 0
-// and must be handed back to attention_bwd.
+// and must be handed back to attention_bwd.  A windowed call (0 < window < S) returns none.
 // `words` (with the Philox draw it was made under): keep words an earlier forward of this same draw returned
 // (a checkpoint's first forward, reused by its recompute) -- read instead of made, when the draw matches.
 std::tuple<Tensor, Tensor, int64_t, int64_t, Tensor> py_attention_fwd(Tensor q, Tensor k, Tensor v, bool causal,
                                                                       double p, double scale, int64_t kv_len,
                                                                       std::optional<Tensor> words, int64_t words_seed,
-                                                                      int64_t words_offset) {
+                                                                      int64_t words_offset, int64_t window) {
   AttnArgs a;
   fill_qkv(a, q, k, v);
+  a.window = attn_window("attention", window, causal, q, a.S);
   MP_CHECK(p >= 0.0 && p < 1.0, "attention: bad dropout p");
   MP_CHECK(kv_len == 0 || (q.scalar_type() == at::kFloat && kv_len > 0 && kv_len <= a.S),
            "attention: kv_len (a key-length bound) is for fp32, 0 < kv_len <= S");
@@ -1249,7 +1261,7 @@ std::tuple<Tensor, Tensor, int64_t, int64_t, Tensor> py_attention_fwd(Tensor q, 
   Tensor bits = at::empty({0}, q.options().dtype(at::kInt));
   if (q.scalar_type() == at::kFloat) {
     attention_f32_fwd(a, cur_stream(q));
-  } else if (use_long(q, a.S, a.D)) {
+  } else if (a.window == 0 && use_long(q, a.S, a.D)) {
     bool reuse = false;
     if (p > 0.0) {
       const std::vector<int64_t> shape = {(int64_t)a.B * a.H, a.S / 32, a.S};
@@ -1269,9 +1281,10 @@ std::tuple<Tensor, Tensor, int64_t, int64_t, Tensor> py_attention_fwd(Tensor q, 
 
 void py_attention_bwd(Tensor dout, Tensor q, Tensor k, Tensor v, Tensor o, Tensor lse, bool causal, double p,
                       double scale, int64_t seed, int64_t offset, Tensor dq, Tensor dk, Tensor dv,
-                      std::optional<Tensor> bits, int64_t kv_len) {
+                      std::optional<Tensor> bits, int64_t kv_len, int64_t window) {
   AttnArgs a;
   fill_qkv(a, q, k, v);
+  a.window = attn_window("attention_bwd", window, causal, q, a.S);
   MP_CHECK(kv_len == 0 || (q.scalar_type() == at::kFloat && kv_len > 0 && kv_len <= a.S),
            "attention_bwd: kv_len (a key-length bound) is for fp32, 0 < kv_len <= S");
   a.kv_len = (int)kv_len;
@@ -1313,7 +1326,7 @@ void py_attention_bwd(Tensor dout, Tensor q, Tensor k, Tensor v, Tensor o, Tenso
   a.scale = (float)scale; a.p = (float)p; a.seed = (uint64_t)seed; a.offset = (uint64_t)offset; a.causal = causal;
   if (q.scalar_type() == at::kFloat) {
     attention_f32_bwd(a, cur_stream(q));
-  } else if (use_long(q, a.S, a.D)) {
+  } else if (a.window == 0 && use_long(q, a.S, a.D)) {
     if (p > 0.0) {
       MP_CHECK(bits && bits->is_cuda() && bits->scalar_type() == at::kInt &&
                    bits->numel() == (int64_t)a.B * a.H * (a.S / 32) * a.S,
@@ -1531,10 +1544,11 @@ PYBIND11_MODULE(_C, m) {
   m.def("attention_f32_supported", [](int64_t S, int64_t D) { return attention_f32_supported((int)S, (int)D); });
   m.def("attention_fwd", &py_attention_fwd, py::arg("q"), py::arg("k"), py::arg("v"), py::arg("causal"), py::arg("p"),
         py::arg("scale"), py::arg("kv_len") = 0, py::arg("words") = py::none(), py::arg("words_seed") = 0,
-        py::arg("words_offset") = 0);
+        py::arg("words_offset") = 0, py::arg("window") = 0);
   m.def("attention_bwd", &py_attention_bwd, py::arg("dout"), py::arg("q"), py::arg("k"), py::arg("v"), py::arg("o"),
         py::arg("lse"), py::arg("causal"), py::arg("p"), py::arg("scale"), py::arg("seed"), py::arg("offset"),
-        py::arg("dq"), py::arg("dk"), py::arg("dv"), py::arg("bits") = py::none(), py::arg("kv_len") = 0);
+        py::arg("dq"), py::arg("dk"), py::arg("dv"), py::arg("bits") = py::none(), py::arg("kv_len") = 0,
+        py::arg("window") = 0);
   m.def("attention_long_supported", [](int64_t S, int64_t D) { return attention_long_supported((int)S, (int)D); });
   m.def("attention_long_set_fused_rng", &attention_long_set_fused_rng,
         "long-sequence attention: make the dropout keep words inside the forward kernel (true, default) or in a "

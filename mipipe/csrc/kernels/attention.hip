@@ -191,8 +191,14 @@ __device__ __forceinline__ float row_reduce_sum16(float v) {
 }
 
 // ------------------------------------------------------------------ forward
-template <int D, bool CAUSAL>
+// WINDOW (only with CAUSAL): sliding-window attention, query i sees the a.window keys (i - a.window, i].  The
+// key-tile loop then starts at the first tile that holds a visible key of the tile's first query row instead of
+// at 0; the tiles wholly below the band are never loaded.  A later row of the query tile can find the first
+// visited tile wholly masked: its running max stays -inf there and the m == -inf guards below give alpha = 0 and
+// p = 0, as they do for a fresh row, so exp2 never sees (-inf) - (-inf).
+template <int D, bool CAUSAL, bool WINDOW = false>
 __global__ void __launch_bounds__(kThreads, D == 256 ? 1 : 2) attn_fwd_kernel(AttnArgs a) {
+  static_assert(!WINDOW || CAUSAL, "the sliding window is a band of the causal mask");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   char* kimg = smem;
   char* vimg = smem + Img<D>::kBytes;
@@ -230,14 +236,16 @@ __global__ void __launch_bounds__(kThreads, D == 256 ? 1 : 2) attn_fwd_kernel(At
   const float pscale = a.p > 0.f ? 1.f / (1.f - a.p) : 1.f;
   const int qrow0 = q0 + wave * 16 + 4 * (lane >> 4);  // this lane's rows qrow0 .. +3
   const int ntiles = CAUSAL ? qt + 1 : a.S / kRows;
+  const int tbeg = WINDOW ? max(0, q0 - a.window + 1) / kRows : 0;  // first tile with a key row q0 sees
+  const int wrow0 = WINDOW ? qrow0 - a.window : 0;                  // row qrow0 + r sees keys > wrow0 + r
 
   constexpr bool PF = D <= 128;
   TileRegs kr, vr;
   if constexpr (PF) {
-    load_tile<D>(K, a.ld_qkv, tid, kr);
-    load_tile<D>(V, a.ld_qkv, tid, vr);
+    load_tile<D>(K + (int64_t)tbeg * kRows * a.ld_qkv, a.ld_qkv, tid, kr);
+    load_tile<D>(V + (int64_t)tbeg * kRows * a.ld_qkv, a.ld_qkv, tid, vr);
   }
-  for (int t = 0; t < ntiles; ++t) {
+  for (int t = tbeg; t < ntiles; ++t) {
     const int k0 = t * kRows;
     __syncthreads();
     if constexpr (PF) {
@@ -272,6 +280,7 @@ __global__ void __launch_bounds__(kThreads, D == 256 ? 1 : 2) attn_fwd_kernel(At
       for (int r = 0; r < 4; ++r) {
         float x = sacc[j][r] * sl2;
         if (CAUSAL && key > qrow0 + r) x = -INFINITY;
+        if (WINDOW && key <= wrow0 + r) x = -INFINITY;
         sv[j][r] = x;
         tmax[r] = fmaxf(tmax[r], x);
       }
@@ -550,9 +559,40 @@ __global__ void __launch_bounds__(256) attn_delta_kernel(AttnArgs a, int D) {
   }
 }
 
+// ------------------------------------------------------------------ delta on the MFMA (the windowed backward)
+// delta_i = dO_i . O_i as the diagonal of a 16 x 16 MFMA tile of dO rows against O rows: the same instruction,
+// operand layout and k order that give dP_ij = dO_i . V_j in the dQ and dK/dV kernels.  Where a query attends a
+// single key (the first row of every sequence; every row at window = 1) O_i is V_j bit for bit, so delta_i equals
+// dP_ij bit for bit and dS = P (dP - delta) is exactly 0, as in exact arithmetic -- attn_delta_kernel adds the
+// same products in another order and leaves an ulp of |dO . V| there.  15 of the 16 columns of each tile are not
+// used; the kernel stays bound by its reads of O and dO.  One wave per 16 rows, a workgroup per 64.
+template <int D>
+__global__ void __launch_bounds__(kThreads) attn_delta_mfma_kernel(AttnArgs a) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int bh = blockIdx.y;
+  const int b = bh / a.H, h = bh % a.H;
+  const int row0 = blockIdx.x * kRows + wave * 16;
+  const int64_t base = (int64_t)b * a.sb_o + (int64_t)h * a.sh_o + (int64_t)(row0 + (lane & 15)) * a.ld_o;
+  const bf16_t* o = reinterpret_cast<const bf16_t*>(a.o) + base;
+  const bf16_t* d = reinterpret_cast<const bf16_t*>(a.dout) + base;
+  f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int s = 0; s < D / 32; ++s)
+    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_global(d, s, lane), frag_global(o, s, lane), acc, 0, 0, 0);
+  // lane (g = lane >> 4, c = lane & 15) holds M[4g + r][c]: the diagonal element of column c sits in the lanes
+  // with c >> 2 == g, at r = c & 3
+  const int g = lane >> 4, c = lane & 15, r = c & 3;
+  if ((c >> 2) == g) {
+    const float v = r == 0 ? acc[0] : (r == 1 ? acc[1] : (r == 2 ? acc[2] : acc[3]));
+    a.delta[(int64_t)bh * a.S + row0 + c] = v;
+  }
+}
+
 // ------------------------------------------------------------------ dQ
-template <int D, bool CAUSAL>
+// WINDOW: the forward's key-tile range and band mask (see attn_fwd_kernel).
+template <int D, bool CAUSAL, bool WINDOW = false>
 __global__ void __launch_bounds__(kThreads, D == 256 ? 1 : 2) attn_dq_kernel(AttnArgs a) {
+  static_assert(!WINDOW || CAUSAL, "the sliding window is a band of the causal mask");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   char* kimg = smem;
   char* vimg = smem + Img<D>::kBytes;
@@ -591,14 +631,16 @@ __global__ void __launch_bounds__(kThreads, D == 256 ? 1 : 2) attn_dq_kernel(Att
   const float sl2 = a.scale * kLog2e;
   const float pscale = a.p > 0.f ? 1.f / (1.f - a.p) : 1.f;
   const int ntiles = CAUSAL ? qt + 1 : a.S / kRows;
+  const int tbeg = WINDOW ? max(0, q0 - a.window + 1) / kRows : 0;  // first tile with a key row q0 sees
+  const int wrow0 = WINDOW ? qrow0 - a.window : 0;                  // row qrow0 + r sees keys > wrow0 + r
 
   constexpr bool PF = D <= 128;
   TileRegs kr, vr;
   if constexpr (PF) {
-    load_tile<D>(K, a.ld_qkv, tid, kr);
-    load_tile<D>(V, a.ld_qkv, tid, vr);
+    load_tile<D>(K + (int64_t)tbeg * kRows * a.ld_qkv, a.ld_qkv, tid, kr);
+    load_tile<D>(V + (int64_t)tbeg * kRows * a.ld_qkv, a.ld_qkv, tid, vr);
   }
-  for (int t = 0; t < ntiles; ++t) {
+  for (int t = tbeg; t < ntiles; ++t) {
     const int k0 = t * kRows;
     __syncthreads();
     if constexpr (PF) {
@@ -636,6 +678,7 @@ __global__ void __launch_bounds__(kThreads, D == 256 ? 1 : 2) attn_dq_kernel(Att
       for (int r = 0; r < 4; ++r) {
         float pr = __builtin_amdgcn_exp2f(sacc[j][r] * sl2 - lse2[r]);
         if (CAUSAL && key > qrow0 + r) pr = 0.f;
+        if (WINDOW && key <= wrow0 + r) pr = 0.f;
         float dp = pacc[j][r];
         if (a.p > 0.f) dp = w[r] >= a.threshold ? dp * pscale : 0.f;
         ds[j][r] = pr * (dp - dl[r]);
@@ -795,8 +838,11 @@ __global__ void __launch_bounds__(kThreads, 2) attn_dq_wide_kernel(AttnArgs a) {
 }
 
 // ------------------------------------------------------------------ dK, dV
-template <int D, bool CAUSAL>
+// WINDOW (only with CAUSAL): key j is seen by the queries [j, j + a.window), so the query-tile loop ends at the
+// tile of query k0 + 63 + a.window - 1 instead of at the sequence's last one.
+template <int D, bool CAUSAL, bool WINDOW = false>
 __global__ void __launch_bounds__(kThreads, D >= 128 ? 1 : 2) attn_dkdv_kernel(AttnArgs a) {
+  static_assert(!WINDOW || CAUSAL, "the sliding window is a band of the causal mask");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   char* qimg = smem;
   char* dimg = smem + Img<D>::kBytes;
@@ -830,7 +876,9 @@ __global__ void __launch_bounds__(kThreads, D >= 128 ? 1 : 2) attn_dkdv_kernel(A
   const float sl2 = a.scale * kLog2e;
   const float pscale = a.p > 0.f ? 1.f / (1.f - a.p) : 1.f;
   const int first = CAUSAL ? kt : 0;
-  const int nq = a.S / kRows;
+  // one past the last query tile: the loop end, computed once (the window is not read again)
+  const int nq = WINDOW ? min(a.S / kRows, (k0 + kRows - 1 + a.window - 1) / kRows + 1) : a.S / kRows;
+  const int wkey0 = WINDOW ? key0 + a.window : 0;  // key key0 + r is seen by the queries < wkey0 + r
 
   constexpr bool PF = D <= 128;
   TileRegs qr, dr;
@@ -900,6 +948,7 @@ __global__ void __launch_bounds__(kThreads, D >= 128 ? 1 : 2) attn_dkdv_kernel(A
         const int key = key0 + r;
         float pr = __builtin_amdgcn_exp2f(sacc[j][r] * sl2 - l2);
         if (CAUSAL && key > q) pr = 0.f;
+        if (WINDOW && q >= wkey0 + r) pr = 0.f;
         float dp = pacc[j][r];
         float pdrop = pr;
         if (a.p > 0.f) {
@@ -1409,6 +1458,35 @@ void run_bwd(const AttnArgs& a, hipStream_t s) {
   hipLaunchKernelGGL((attn_dq_kernel<D, CAUSAL>), dim3(a.S / kRows, a.B * a.H), dim3(kThreads), sm, s, a);
 }
 
+// Sliding window (0 < a.window < a.S, causal): always the generic 64-row kernels, whatever S and D -- the
+// S = 128, wide D = 64 and long-sequence kernels know no window.
+template <int D>
+void run_fwd_window(const AttnArgs& a, hipStream_t s) {
+  const size_t sm = fwd_smem<D>();
+  static bool once = false;
+  if (!once) { set_smem(attn_fwd_kernel<D, true, true>, sm); once = true; }
+  hipLaunchKernelGGL((attn_fwd_kernel<D, true, true>), dim3(a.S / kRows, a.B * a.H), dim3(kThreads), sm, s, a);
+}
+
+template <int D>
+void run_bwd_window(const AttnArgs& a, hipStream_t s) {
+  const size_t sm = fwd_smem<D>(), sm2 = dkdv_smem<D>();
+  static bool once = false;
+  if (!once) {
+    set_smem(attn_dq_kernel<D, true, true>, sm);
+    set_smem(attn_dkdv_kernel<D, true, true>, sm2);
+    once = true;
+  }
+  hipLaunchKernelGGL((attn_delta_mfma_kernel<D>), dim3(a.S / kRows, a.B * a.H), dim3(kThreads), 0, s, a);
+  hipLaunchKernelGGL((attn_dkdv_kernel<D, true, true>), dim3(a.S / kRows, a.B * a.H), dim3(kThreads), sm2, s, a);
+  hipLaunchKernelGGL((attn_dq_kernel<D, true, true>), dim3(a.S / kRows, a.B * a.H), dim3(kThreads), sm, s, a);
+}
+
+// A window that covers the sequence (or a non-causal call, which has none) is no window.
+void normalise_window(AttnArgs& a) {
+  if (!a.causal || a.window < 0 || a.window >= a.S) a.window = 0;
+}
+
 }  // namespace
 
 void attention_set_fused_bwd(int on) { g_attn_fused_bwd = on; }
@@ -1418,6 +1496,13 @@ bool attention_supported(int S, int D) { return S > 0 && S % kRows == 0 && (D ==
 void attention_fwd(const AttnArgs& ai, hipStream_t s) {
   AttnArgs a = attn_resolved(ai);
   a.threshold = dropout_threshold(a.p);
+  normalise_window(a);
+  if (a.window > 0) {
+    if (a.D == 64) run_fwd_window<64>(a, s);
+    else if (a.D == 128) run_fwd_window<128>(a, s);
+    else run_fwd_window<256>(a, s);
+    return;
+  }
   if (a.causal) {
     if (a.D == 64) run_fwd<64, true>(a, s);
     else if (a.D == 128) run_fwd<128, true>(a, s);
@@ -1432,6 +1517,13 @@ void attention_fwd(const AttnArgs& ai, hipStream_t s) {
 void attention_bwd(const AttnArgs& ai, hipStream_t s) {
   AttnArgs a = attn_resolved(ai);
   a.threshold = dropout_threshold(a.p);
+  normalise_window(a);
+  if (a.window > 0) {
+    if (a.D == 64) run_bwd_window<64>(a, s);
+    else if (a.D == 128) run_bwd_window<128>(a, s);
+    else run_bwd_window<256>(a, s);
+    return;
+  }
   if (a.causal) {
     if (a.D == 64) run_bwd<64, true>(a, s);
     else if (a.D == 128) run_bwd<128, true>(a, s);

@@ -299,6 +299,9 @@ struct AttnArgs {
   int group = 1;
   uint32_t group_rcp = 1u << 20;  // ceil(2^20 / group): set by attn_resolved (kv_head)
   int64_t ld_dkv = 0, sb_dkv = 0, sh_dkv = 0;
+  // Sliding-window attention (bf16 attention.hip, causal only): query i sees the `window` keys (i - window, i];
+  // 0 = no window.  Kept the LAST member: no other member's offset in the kernel-argument segment moves.
+  int window = 0;
 };
 // K / V head of query head h: h / group as a scalar multiply by ceil(2^20 / group) and a shift instead of a
 // division.  Exact for every h when group == 1 (the 64-bit product is h * 2^20) and while h * group < 2^20

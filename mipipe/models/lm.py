@@ -207,6 +207,7 @@ class LMConfig:
     rope_base: float = 10000.0
     positions: Optional[str] = None  # Encoder positions; None: "learned" if learned_positions else "sinusoidal"
     n_kv_heads: Optional[int] = None  # grouped-query attention: K/V heads (a divisor of nhead); None = nhead
+    window: Optional[int] = None      # sliding-window attention: keys a query sees, its own included (causal only)
 
     def qkv_dim(self) -> int:
         """Width of the QKV projection: ``(H + 2 Hkv) D`` (``3 d_model`` without grouped-query attention)."""
@@ -268,6 +269,17 @@ CONFIGS = {
                           norm_first=True, causal=True, scale_embedding=False, act_dropout=0.0, norm="rms",
                           bias=False, rope=True, rope_base=500000.0, positions="none", n_kv_heads=8,
                           notes="LLaMA-3 8B's block; the decoder is untied and keeps its (zero-initialised) bias"),
+    # llama_gqa_tiny with sliding-window attention: at head dim 64 and 192 tokens a window of 48 skips key tiles
+    # on both sides of the band.
+    "mistral_tiny": LMConfig("mistral_tiny", 2, 256, 4, 512, 1000, 192, dropout=0.0, activation="swiglu",
+                             norm_first=True, causal=True, scale_embedding=False, act_dropout=0.0, norm="rms",
+                             bias=False, rope=True, positions="none", n_kv_heads=2, window=48,
+                             notes="tiny Mistral-style model (grouped-query, sliding-window attention) for tests"),
+    # Mistral 7B v0.1: llama3_8b's block with a 32,000-token vocabulary, rope base 10,000 and a 4096-key window.
+    "mistral_7b": LMConfig("mistral_7b", 32, 4096, 32, 14336, 32000, 8192, dropout=0.0, activation="swiglu",
+                           norm_first=True, causal=True, scale_embedding=False, act_dropout=0.0, norm="rms",
+                           bias=False, rope=True, rope_base=10000.0, positions="none", n_kv_heads=8, window=4096,
+                           notes="Mistral 7B's block; the decoder is untied and keeps its (zero-initialised) bias"),
 }
 
 
@@ -281,7 +293,7 @@ def build_lm_blocks(cfg: LMConfig, *, device=None, dtype=None) -> List[nn.Module
     blocks += transformer_blocks(cfg.num_layers, cfg.d_model, cfg.nhead, cfg.dim_feedforward, cfg.dropout,
                                  cfg.activation, norm_first=cfg.norm_first, causal=cfg.causal, norm=cfg.norm,
                                  bias=cfg.bias, rope=cfg.rope, rope_base=cfg.rope_base, n_kv_heads=cfg.n_kv_heads,
-                                 device=device, dtype=dtype)
+                                 window=cfg.window, device=device, dtype=dtype)
     if cfg.act_dropout is not None:
         for b in blocks:
             if isinstance(b, FeedForwardBlock):

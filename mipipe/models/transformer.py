@@ -28,7 +28,9 @@ still exchange an ``F``-wide ``h``).  ``n_kv_heads=Hkv`` (a divisor of ``nhead``
 ``None`` means ``nhead``) is grouped-query attention: ``in_proj_weight`` is
 ``[(H + 2 Hkv) D, E]`` -- rows of the ``H`` Q heads, then of the ``Hkv`` K heads,
 then of the ``Hkv`` V heads -- and query head ``h`` attends with K/V head
-``h // (H / Hkv)`` (``ops.attention_gqa_packed``).
+``h // (H / Hkv)`` (``ops.attention_gqa_packed``).  ``window=W`` (causal blocks
+only; ``None`` means none) is sliding-window attention: a query attends the
+last ``W`` keys, its own included (Mistral's ``sliding_window``).
 """
 from __future__ import annotations
 
@@ -126,10 +128,17 @@ class AttentionCore(nn.Module):
 
     def __init__(self, d_model: int, nhead: int, dropout: float, *, norm_first: bool, causal: bool,
                  layer_norm_eps: float, norm: str = "layer", bias: bool = True, rope: bool = False,
-                 rope_base: float = 10000.0, n_kv_heads: Optional[int] = None, device=None, dtype=None) -> None:
+                 rope_base: float = 10000.0, n_kv_heads: Optional[int] = None, window: Optional[int] = None,
+                 device=None, dtype=None) -> None:
         super().__init__()
         fk = {"device": device, "dtype": dtype}
         self.d_model, self.nhead, self.head_dim = d_model, nhead, d_model // nhead
+        if window is not None:
+            if isinstance(window, bool) or not isinstance(window, int) or window < 1:
+                raise ValueError(f"window must be an int >= 1 or None, got {window!r}")
+            if not causal:
+                raise ValueError("window (sliding-window attention) needs causal=True")
+        self.window = window
         self.n_kv_heads = nhead if n_kv_heads is None else int(n_kv_heads)
         if self.n_kv_heads <= 0 or nhead % self.n_kv_heads != 0:
             raise ValueError(f"n_kv_heads must divide nhead, got nhead={nhead}, n_kv_heads={n_kv_heads}")
@@ -199,7 +208,7 @@ class AttentionCore(nn.Module):
             else:
                 qkv4 = qkv.view(B, S, H + 2 * Hkv, D)
             o = ops.attention_gqa_packed(qkv4, Hkv, causal=self.causal, dropout_p=self.dropout,
-                                         training=self.training)
+                                         training=self.training, window=self.window)
             return o.reshape(B, S, E), xr
         if self.rope:
             # Q and K rotated: in the projection's own output where no graph is recorded, else into a new tensor
@@ -207,12 +216,20 @@ class AttentionCore(nn.Module):
             qkv5 = ops.rope_projection(qkv, cos, sin, H)
         else:
             qkv5 = qkv.view(B, S, 3, H, D)
-        o = ops.attention_packed(qkv5, causal=self.causal, dropout_p=self.dropout, training=self.training)
+        o = ops.attention_packed(qkv5, causal=self.causal, dropout_p=self.dropout, training=self.training,
+                                 window=self.window)
         return o.reshape(B, S, E), xr
 
     def flops_per_token(self, seq_len: int) -> float:
         e = self.d_model
-        return 2 * self.qkv_dim * e + 4 * seq_len * e * (0.5 if self.causal else 1.0)
+        # mean number of keys a query sees: all, half of them under the causal mask (the kernels skip the tiles
+        # above the diagonal), and under a window w < seq_len the first w rows' 1 .. w and w for every later row
+        w = self.window
+        if w is not None and w < seq_len:
+            keys = (w * (w + 1) / 2 + (seq_len - w) * w) / seq_len
+        else:
+            keys = seq_len * (0.5 if self.causal else 1.0)
+        return 2 * self.qkv_dim * e + 4 * keys * e
 
 
 class AttentionOutput(nn.Module):
@@ -259,13 +276,14 @@ class SelfAttentionBlock(nn.Module):
     def __init__(self, d_model: int, nhead: int, dropout: float = 0.1, *, norm_first: bool = False,
                  causal: bool = False, layer_norm_eps: float = 1e-5, norm: str = "layer", bias: bool = True,
                  rope: bool = False, rope_base: float = 10000.0, n_kv_heads: Optional[int] = None,
-                 device=None, dtype=None) -> None:
+                 window: Optional[int] = None, device=None, dtype=None) -> None:
         super().__init__()
         if d_model % nhead != 0:
             raise ValueError("d_model must be divisible by nhead")
         self.core = AttentionCore(d_model, nhead, dropout, norm_first=norm_first, causal=causal,
                                   layer_norm_eps=layer_norm_eps, norm=norm, bias=bias, rope=rope,
-                                  rope_base=rope_base, n_kv_heads=n_kv_heads, device=device, dtype=dtype)
+                                  rope_base=rope_base, n_kv_heads=n_kv_heads, window=window, device=device,
+                                  dtype=dtype)
         self.out = AttentionOutput(d_model, dropout, norm_first=norm_first, layer_norm_eps=layer_norm_eps,
                                    norm=norm, bias=bias, device=device, dtype=dtype)
 
@@ -549,11 +567,12 @@ class TransformerEncoderLayer(nn.Sequential):
         rope: bool = False,
         rope_base: float = 10000.0,
         n_kv_heads: Optional[int] = None,
+        window: Optional[int] = None,
     ) -> None:
         super().__init__(
             SelfAttentionBlock(d_model, nhead, dropout, norm_first=norm_first, causal=causal,
                                layer_norm_eps=layer_norm_eps, norm=norm, bias=bias, rope=rope, rope_base=rope_base,
-                               n_kv_heads=n_kv_heads, device=device, dtype=dtype),
+                               n_kv_heads=n_kv_heads, window=window, device=device, dtype=dtype),
             FeedForwardBlock(d_model, dim_feedforward, dropout, activation, norm_first=norm_first,
                              layer_norm_eps=layer_norm_eps, norm=norm, bias=bias, device=device, dtype=dtype),
         )
@@ -597,6 +616,7 @@ def transformer_blocks(
     rope: bool = False,
     rope_base: float = 10000.0,
     n_kv_heads: Optional[int] = None,
+    window: Optional[int] = None,
     device=None,
     dtype=None,
 ) -> List[nn.Module]:
@@ -605,7 +625,8 @@ def transformer_blocks(
     for _ in range(num_layers):
         layer = TransformerEncoderLayer(d_model, nhead, dim_feedforward, dropout, activation,
                                         norm_first=norm_first, causal=causal, norm=norm, bias=bias, rope=rope,
-                                        rope_base=rope_base, n_kv_heads=n_kv_heads, device=device, dtype=dtype)
+                                        rope_base=rope_base, n_kv_heads=n_kv_heads, window=window, device=device,
+                                        dtype=dtype)
         blocks.extend(layer.children())
     return blocks
 

@@ -34,6 +34,20 @@ reference's ``get_batch`` tail window, /root/reference/main.py:108-113) is
 zero-padded at the end to the next supported length: under the causal mask
 no real query sees a padded key, so the real rows are exact; the padded rows
 are sliced off (and get no gradient).
+
+Sliding-window attention: every entry point takes a keyword-only ``window=W``
+(an int >= 1, with ``causal=True``): query ``i`` attends the ``W`` keys ``i - W
+< j <= i``, its own included -- the Hugging Face / Mistral ``sliding_window``
+convention (flash-attn's ``window_size=(W - 1, 0)``).  ``window=None`` or ``W >=
+S`` is plain causal attention, on the code path it always took.  A bf16 call on
+the GPU with ``W < S`` runs attention.hip's generic kernels, which skip the
+64-key tiles wholly below the band as well as those above the diagonal (about
+``S * W`` work instead of ``S^2 / 2``); grouped-query heads are read in place
+as without a window, and the dropout mask is the causal call's restricted to
+the band.  The padded shapes above stay native too: padded keys lie after
+every real query and padded features add 0.  fp32 sliding-window attention is
+not native: it, the CPU and the shapes ``_run_shape`` rejects use the eager
+math of :func:`attention_reference` with the band mask.
 """
 from __future__ import annotations
 
@@ -53,14 +67,32 @@ from ._util import kernels_for
 __all__ = ["attention", "attention_packed", "attention_gqa_packed", "attention_reference", "clear_keep_words"]
 
 
-def attention_reference(q: Tensor, k: Tensor, v: Tensor, causal: bool, p: float, scale: Optional[float] = None) -> Tensor:
-    """Eager fp32 math on ``[B, H, S, D]`` (CPU path and test oracle)."""
+def _check_window(window: Optional[int], causal: bool, S: int) -> Optional[int]:
+    """``window`` validated (an int >= 1, causal only) and clamped: one that covers the sequence is ``None``."""
+    if window is None:
+        return None
+    if isinstance(window, bool) or not isinstance(window, int):
+        raise ValueError(f"attention: window must be an int >= 1 or None, got {window!r}")
+    if window < 1:
+        raise ValueError(f"attention: window must be >= 1 (None: no window), got {window}")
+    if not causal:
+        raise ValueError("attention: a sliding window needs causal=True (two-sided windows are not supported)")
+    return None if window >= S else window
+
+
+def attention_reference(q: Tensor, k: Tensor, v: Tensor, causal: bool, p: float, scale: Optional[float] = None,
+                        *, window: Optional[int] = None) -> Tensor:
+    """Eager fp32 math on ``[B, H, S, D]`` (CPU path and test oracle).  ``window``: query ``i`` sees the keys
+    ``i - window < j <= i`` only."""
     d = q.shape[-1]
     scale = scale if scale is not None else 1.0 / math.sqrt(d)
+    window = _check_window(window, bool(causal), q.shape[-2])
     s = torch.matmul(q.float(), k.float().transpose(-1, -2)) * scale
     if causal:
         n, m = s.shape[-2], s.shape[-1]
         mask = torch.ones(n, m, dtype=torch.bool, device=s.device).triu(1 + m - n)
+        if window is not None:  # keys at or below the band's lower edge: j <= i - window
+            mask |= torch.ones(n, m, dtype=torch.bool, device=s.device).tril(m - n - window)
         s = s.masked_fill(mask, float("-inf"))
     pr = torch.softmax(s, dim=-1)
     if p > 0:
@@ -104,8 +136,10 @@ def clear_keep_words() -> None:
         _keep_bytes = 0
 
 
-def _attention_fwd(kern, q, k, v, causal, p, scale, kv_len):
+def _attention_fwd(kern, q, k, v, causal, p, scale, kv_len, window=0):
     global _keep_bytes
+    if window:  # the generic kernels: the mask is regenerated from Philox, there are no keep words
+        return kern.attention_fwd(q, k, v, causal, p, scale, kv_len, None, 0, 0, window)
     reuse = _KEEP_REUSE and p > 0 and q.is_cuda and q.dtype == torch.bfloat16 and kv_len == 0
     words = key = None
     if reuse and is_recomputing():
@@ -137,12 +171,13 @@ class _AttentionPacked(torch.autograd.Function):
     backward produces the packed ``dqkv`` in one buffer."""
 
     @staticmethod
-    def forward(ctx, qkv, causal, p, scale, kv_len=0):  # type: ignore[override]
+    def forward(ctx, qkv, causal, p, scale, kv_len=0, window=0):  # type: ignore[override]
         kern = kernels_for(qkv)
         q, k, v = qkv.select(2, 0), qkv.select(2, 1), qkv.select(2, 2)
-        o, lse, seed, offset, bits = _attention_fwd(kern, q, k, v, causal, p, scale, kv_len)
+        o, lse, seed, offset, bits = _attention_fwd(kern, q, k, v, causal, p, scale, kv_len, window)
         ctx.save_for_backward(qkv, o, lse, bits)
         ctx.causal, ctx.p, ctx.scale, ctx.seed, ctx.offset, ctx.kv_len = causal, p, scale, seed, offset, kv_len
+        ctx.window = window
         return o
 
     @staticmethod
@@ -154,19 +189,20 @@ class _AttentionPacked(torch.autograd.Function):
         dqkv = torch.empty_like(qkv)
         kern.attention_bwd(do, qkv.select(2, 0), qkv.select(2, 1), qkv.select(2, 2), o, lse, ctx.causal, ctx.p,
                            ctx.scale, ctx.seed, ctx.offset, dqkv.select(2, 0), dqkv.select(2, 1), dqkv.select(2, 2),
-                           bits if bits.numel() else None, ctx.kv_len)
-        return dqkv, None, None, None, None
+                           bits if bits.numel() else None, ctx.kv_len, ctx.window)
+        return dqkv, None, None, None, None, None
 
 
 class _Attention(torch.autograd.Function):
     """Separate q, k, v as [B, S, H, D] views sharing one layout."""
 
     @staticmethod
-    def forward(ctx, q, k, v, causal, p, scale, kv_len=0):  # type: ignore[override]
+    def forward(ctx, q, k, v, causal, p, scale, kv_len=0, window=0):  # type: ignore[override]
         kern = kernels_for(q)
-        o, lse, seed, offset, bits = _attention_fwd(kern, q, k, v, causal, p, scale, kv_len)
+        o, lse, seed, offset, bits = _attention_fwd(kern, q, k, v, causal, p, scale, kv_len, window)
         ctx.save_for_backward(q, k, v, o, lse, bits)
         ctx.causal, ctx.p, ctx.scale, ctx.seed, ctx.offset, ctx.kv_len = causal, p, scale, seed, offset, kv_len
+        ctx.window = window
         return o
 
     @staticmethod
@@ -177,8 +213,8 @@ class _Attention(torch.autograd.Function):
             do = do.contiguous()
         dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
         kern.attention_bwd(do, q, k, v, o, lse, ctx.causal, ctx.p, ctx.scale, ctx.seed, ctx.offset, dq, dk, dv,
-                           bits if bits.numel() else None, ctx.kv_len)
-        return dq, dk, dv, None, None, None, None
+                           bits if bits.numel() else None, ctx.kv_len, ctx.window)
+        return dq, dk, dv, None, None, None, None, None
 
 
 class _AttentionGqaPacked(torch.autograd.Function):
@@ -187,13 +223,14 @@ class _AttentionGqaPacked(torch.autograd.Function):
     dK / dV into one packed ``dqkv`` of the same layout (the binding owns the per-query-head scratch)."""
 
     @staticmethod
-    def forward(ctx, qkv, n_kv, causal, p, scale):  # type: ignore[override]
+    def forward(ctx, qkv, n_kv, causal, p, scale, window=0):  # type: ignore[override]
         kern = kernels_for(qkv)
         H = qkv.shape[2] - 2 * n_kv
         q, k, v = qkv[:, :, :H], qkv[:, :, H:H + n_kv], qkv[:, :, H + n_kv:]
-        o, lse, seed, offset, bits = _attention_fwd(kern, q, k, v, causal, p, scale, 0)
+        o, lse, seed, offset, bits = _attention_fwd(kern, q, k, v, causal, p, scale, 0, window)
         ctx.save_for_backward(qkv, o, lse, bits)
         ctx.n_kv, ctx.causal, ctx.p, ctx.scale, ctx.seed, ctx.offset = n_kv, causal, p, scale, seed, offset
+        ctx.window = window
         return o
 
     @staticmethod
@@ -207,22 +244,30 @@ class _AttentionGqaPacked(torch.autograd.Function):
         dqkv = torch.empty_like(qkv)
         kern.attention_bwd(do, qkv[:, :, :H], qkv[:, :, H:H + n_kv], qkv[:, :, H + n_kv:], o, lse, ctx.causal, ctx.p,
                            ctx.scale, ctx.seed, ctx.offset, dqkv[:, :, :H], dqkv[:, :, H:H + n_kv],
-                           dqkv[:, :, H + n_kv:], bits if bits.numel() else None, 0)
-        return dqkv, None, None, None, None
+                           dqkv[:, :, H + n_kv:], bits if bits.numel() else None, 0, ctx.window)
+        return dqkv, None, None, None, None, None
 
 
 _noted = set()
 
 
-def _note_math_path(S: int, D: int, dtype) -> None:
+def _note_math_path(S: int, D: int, dtype, window: Optional[int] = None) -> None:
     """Shapes outside the kernels' tiling use the eager math path; say so once per shape."""
-    key = (S, D, dtype)
+    key = (S, D, dtype) if window is None else (S, D, dtype, "window")
     if key not in _noted:
         _noted.add(key)
         import warnings
 
-        warnings.warn(f"mipipe attention: S={S} D={D} {dtype} runs the eager math path (HIP kernels: bf16 with "
-                      "S % 64 == 0, D in {64, 128, 256}; fp32 with S % 32 == 0, D in {64, 128})", stacklevel=3)
+        extra = "" if window is None else f" window={window}"
+        tail = "" if window is None else ".  fp32 sliding-window attention is not native: the window runs on the bf16 kernels only"
+        warnings.warn(f"mipipe attention: S={S} D={D} {dtype}{extra} runs the eager math path (HIP kernels: bf16 "
+                      "with S % 64 == 0, D in {64, 128, 256}; fp32 with S % 32 == 0, D in {64, 128})" + tail,
+                      stacklevel=3)
+
+
+def _window_native(t: Tensor) -> bool:
+    """A windowed call runs on the kernels only in bf16 on the GPU."""
+    return t.is_cuda and t.dtype == torch.bfloat16
 
 
 def _gpu_ok(t: Tensor, S: int, D: int) -> bool:
@@ -276,13 +321,33 @@ def _run_shape(t: Tensor, S: int, D: int, causal: bool, scale: float) -> Optiona
     return None
 
 
+def _packed_window(qkv: Tensor, S: int, D: int, p: float, scale: float, window: int) -> Tensor:
+    """:func:`attention_packed` with a window ``< S`` (causal)."""
+    if _window_native(qkv):
+        if _gpu_ok(qkv, S, D):
+            return _AttentionPacked.apply(qkv.contiguous(), True, p, scale, 0, window)
+        run = _run_shape(qkv, S, D, True, scale)
+        if run is not None:  # causal bf16: end padding and feature padding only (no key bound)
+            sp, dp, _ = run
+            padded = F.pad(qkv, (0, dp - D, 0, 0, 0, 0, 0, sp - S))
+            return _AttentionPacked.apply(padded, True, p, scale, 0, window)[:, :S, :, :D]
+    q, k, v = qkv.select(2, 0), qkv.select(2, 1), qkv.select(2, 2)
+    if qkv.is_cuda:
+        _note_math_path(S, D, qkv.dtype, window)
+    o = attention_reference(q.transpose(1, 2), k.transpose(1, 2), v.transpose(1, 2), True, p, scale, window=window)
+    return o.transpose(1, 2)
+
+
 def attention_packed(qkv: Tensor, causal: bool = False, dropout_p: float = 0.0, training: bool = True,
-                     scale: Optional[float] = None) -> Tensor:
-    """``qkv [B, S, 3, H, D]`` -> ``o [B, S, H, D]``."""
+                     scale: Optional[float] = None, *, window: Optional[int] = None) -> Tensor:
+    """``qkv [B, S, 3, H, D]`` -> ``o [B, S, H, D]``.  ``window``: sliding-window attention (module doc)."""
     B, S, three, H, D = qkv.shape
     assert three == 3
     p = float(dropout_p) if training else 0.0
     scale = float(scale) if scale is not None else 1.0 / math.sqrt(D)
+    window = _check_window(window, bool(causal), S)
+    if window is not None:
+        return _packed_window(qkv, S, D, p, scale, window)
     if qkv.is_cuda and _gpu_ok(qkv, S, D):
         return _AttentionPacked.apply(qkv.contiguous(), bool(causal), p, scale)
     run = _run_shape(qkv, S, D, bool(causal), scale) if qkv.is_cuda else None
@@ -318,8 +383,10 @@ def _expand_kv(qkv: Tensor, n_kv: int) -> Tensor:
 
 
 def attention_gqa_packed(qkv: Tensor, n_kv_heads: int, causal: bool = False, dropout_p: float = 0.0,
-                         training: bool = True, scale: Optional[float] = None) -> Tensor:
-    """``qkv [B, S, H + 2 Hkv, D]`` -> ``o [B, S, H, D]`` (grouped-query attention, ``Hkv = n_kv_heads``)."""
+                         training: bool = True, scale: Optional[float] = None, *,
+                         window: Optional[int] = None) -> Tensor:
+    """``qkv [B, S, H + 2 Hkv, D]`` -> ``o [B, S, H, D]`` (grouped-query attention, ``Hkv = n_kv_heads``).
+    ``window``: sliding-window attention (module doc)."""
     if qkv.dim() != 4:
         raise ValueError(f"attention_gqa_packed: qkv must be [B, S, H + 2 Hkv, D], got {tuple(qkv.shape)}")
     B, S, heads, D = qkv.shape
@@ -328,22 +395,23 @@ def attention_gqa_packed(qkv: Tensor, n_kv_heads: int, causal: bool = False, dro
     if n_kv <= 0 or H <= 0 or H % n_kv != 0:
         raise ValueError(f"attention_gqa_packed: {heads} packed heads do not split into H + 2 * {n_kv} with "
                          f"{n_kv} dividing H")
+    window = _check_window(window, bool(causal), S)
     if n_kv == H:  # plain multi-head attention: the same bytes as [B, S, 3, H, D]
-        return attention_packed(qkv.reshape(B, S, 3, H, D), causal, dropout_p, training, scale)
+        return attention_packed(qkv.reshape(B, S, 3, H, D), causal, dropout_p, training, scale, window=window)
     if qkv.is_cuda and qkv.dtype == torch.bfloat16 and _gpu_ok(qkv, S, D):
         p = float(dropout_p) if training else 0.0
         scale = float(scale) if scale is not None else 1.0 / math.sqrt(D)
-        return _AttentionGqaPacked.apply(qkv.contiguous(), n_kv, bool(causal), p, scale)
-    return attention_packed(_expand_kv(qkv, n_kv), causal, dropout_p, training, scale)
+        return _AttentionGqaPacked.apply(qkv.contiguous(), n_kv, bool(causal), p, scale, window or 0)
+    return attention_packed(_expand_kv(qkv, n_kv), causal, dropout_p, training, scale, window=window)
 
 
 def attention(
     q: Tensor, k: Tensor, v: Tensor, causal: bool = False, dropout_p: float = 0.0, training: bool = True,
-    scale: Optional[float] = None,
+    scale: Optional[float] = None, *, window: Optional[int] = None,
 ) -> Tensor:
     """``q, k, v [B, H, S, D]`` -> ``[B, H, S, D]``.  ``k`` and ``v`` may have fewer heads, ``Hkv | H``
     (grouped-query attention): separate tensors do not share q's strides, so their heads are repeated
-    (autograd sums each group's gradient)."""
+    (autograd sums each group's gradient).  ``window``: sliding-window attention (module doc)."""
     if k.shape[1] != q.shape[1]:
         if k.shape[1] != v.shape[1] or k.shape[1] <= 0 or q.shape[1] % k.shape[1] != 0:
             raise ValueError(f"attention: {k.shape[1]} / {v.shape[1]} K/V heads do not divide {q.shape[1]} query heads")
@@ -351,9 +419,21 @@ def attention(
         k, v = k.repeat_interleave(g, dim=1), v.repeat_interleave(g, dim=1)
     p = float(dropout_p) if training else 0.0
     scale = float(scale) if scale is not None else 1.0 / math.sqrt(q.shape[-1])
+    window = _check_window(window, bool(causal), q.shape[2])
     if not q.is_cuda:
-        return attention_reference(q, k, v, causal, p, scale)
+        return attention_reference(q, k, v, causal, p, scale, window=window)
     S, D = q.shape[2], q.shape[3]
+    if window is not None:
+        run = (S, D, 0) if _gpu_ok(q, S, D) else _run_shape(q, S, D, True, scale)
+        if not _window_native(q) or run is None:
+            _note_math_path(S, D, q.dtype, window)
+            return attention_reference(q, k, v, True, p, scale, window=window)
+        sp, dp, _ = run  # causal bf16: end padding and feature padding only (no key bound)
+        pad = (lambda t: F.pad(t, (0, dp - D, 0, sp - S))) if (sp, dp) != (S, D) else (lambda t: t)  # noqa: E731
+        qs, ks, vs = (pad(t).transpose(1, 2) for t in (q, k, v))
+        if not (qs.stride() == ks.stride() == vs.stride()) or qs.stride(3) != 1:
+            qs, ks, vs = (t.contiguous() for t in (qs, ks, vs))
+        return _Attention.apply(qs, ks, vs, True, p, scale, 0, window).transpose(1, 2)[:, :, :S, :D]
     if not _gpu_ok(q, S, D):
         run = _run_shape(q, S, D, bool(causal), scale)
         if run is None:

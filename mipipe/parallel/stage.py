@@ -62,10 +62,12 @@ def block_costs(cfg: LMConfig, split_decoder: bool = False) -> List[float]:
     ``[Encoder, (attn core, attn out, mlp in, mlp out) x L, (final norm), Decoder]``
     (see ``mipipe.models.transformer.pipeline_units``)."""
     e, f, s, v = cfg.d_model, cfg.dim_feedforward, cfg.seq_len, cfg.vocab
-    causal = 0.5 if cfg.causal else 1.0
+    # mean number of keys a query sees (AttentionCore.flops_per_token): a sliding window w < s bounds it
+    w = cfg.window
+    keys = (w * (w + 1) / 2 + (s - w) * w) / s if w is not None and w < s else s * (0.5 if cfg.causal else 1.0)
     # the QKV projection is (H + 2 Hkv) D wide: 3 e without grouped-query attention
     qkv = cfg.qkv_dim()
-    core = 3.0 * (2 * qkv * e + 4 * s * e * causal) + 3.0 * 10 * e
+    core = 3.0 * (2 * qkv * e + 4 * keys * e) + 3.0 * 10 * e
     out = 3.0 * (2 * e * e) + 3.0 * 10 * e  # + LN/dropout traffic
     if cfg.activation == "swiglu":  # the gated first GEMM is 2F wide, and the gate is a pass of its own
         mlp_in = 3.0 * (2 * e * 2 * f) + 3.0 * 10 * f

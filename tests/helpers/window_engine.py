@@ -1,0 +1,19 @@
+"""The multi-rank engine case of tests/test_window_ops.py: helpers/engine_cases.py builds its own
+config (``case_cfg``) in every spawned rank, so the ranks start here, swap that config for the
+sliding-window replica and then run the unchanged ``engine_cases.worker``."""
+import dataclasses
+
+from helpers import engine_cases
+
+from mipipe.models import CONFIGS
+
+
+def window_cfg(mode=None):
+    """A 2-layer d 32 replica of ``mistral_tiny``: 4 query heads over 2 K/V heads, 8 tokens, a window of 3."""
+    return dataclasses.replace(CONFIGS["mistral_tiny"], d_model=32, nhead=4, n_kv_heads=2, dim_feedforward=64,
+                               vocab=100, seq_len=8, window=3)
+
+
+def worker(*args, **kwargs):
+    engine_cases.case_cfg = window_cfg
+    return engine_cases.worker(*args, **kwargs)
