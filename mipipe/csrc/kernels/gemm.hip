@@ -36,6 +36,7 @@
 //   kEpiStoreF32  -- fp32 store (first write of a step, split-K partials).
 #include <algorithm>
 #include <cstdlib>
+#include <type_traits>
 
 #include "common.h"
 #include "kernels.h"
@@ -444,6 +445,26 @@ __device__ __forceinline__ bf16x8 frag(const char* tile, int ib, int s, int lane
   }
 }
 
+// frag<false, W> with the address split into what a lane keeps in a register
+// and what goes into the reads' immediate offset: ic_frag_off is the byte
+// offset of the s = 0 `lo` read in the tile; k-step s lies 32 rows and the `hi`
+// read 4 rows further down, and neither changes ic_rk (bits 0, 1 and 3 of the
+// row), so both are constants for every lane.  ic_frag_at reads the fragment
+// at LDS byte address `addr` (tile base + ic_frag_off) + `imm`.
+template <int W>
+__device__ __forceinline__ uint32_t ic_frag_off(int ib, int lane) {
+  const int g = lane >> 4, q = (lane & 15) >> 2, p = lane & 3;
+  return (uint32_t)ic_off_w<W>(8 * g + q, (ib >> 2) + p);
+}
+
+template <int W>
+__device__ __forceinline__ bf16x8 ic_frag_at(uint32_t addr, int imm, int s) {
+  const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(addr + (uint32_t)(imm + s * 32 * 2 * W)));
+  const s16x4 hi =
+      __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(addr + (uint32_t)(imm + s * 32 * 2 * W + 4 * 2 * W)));
+  return __builtin_bit_cast(bf16x8, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
+}
+
 // Epilogue parameters as plain values, read from the kernel arguments once
 // (through a GemmArgs reference the fields were re-loaded -- an s_load plus
 // its wait -- after every store that might alias them).
@@ -743,6 +764,7 @@ __global__ void __launch_bounds__(kThreads, 1) gemm256_kernel(GemmArgs g) {
   constexpr int kBuf = kTileBytes + W * BK * 2;  // A + B tile
   constexpr bool AH = !A_KC;          // A tile as two 128-wide halves (stage_offsets_halves)
   constexpr bool B3 = !B_KC;          // B tiles in three buffers (smem_bytes)
+  constexpr bool II = AH && B3;       // both I-contiguous: own LDS map, K loop unrolled by two (below)
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -866,14 +888,24 @@ __global__ void __launch_bounds__(kThreads, 1) gemm256_kernel(GemmArgs g) {
   constexpr int NA = 4;       // A DMAs per wave per K-tile
   // `kc` runs ahead of the loop, always at the tile this wave group stages
   // next (tile u + 1 for group 0, u + 2 for group 1).
+  // LDS map.  A of buffer i (tile parity) and B of slot s (B3: u mod 3, else
+  // the parity): [A0 B0][A1 B1][B2], or, both operands I-contiguous (II),
+  // [A0 A1][B0 B1 B2] -- the two A tiles inside one 64 KiB window, so that a
+  // fragment address is ONE loop-invariant VGPR per 16-row block plus the
+  // ds_read's 16-bit immediate, whichever tile is read (see the loop).
+  auto abuf = [&](int i) { return II ? smem + i * kTileBytes : smem + i * kBuf; };
+  auto bslot = [&](int s) {
+    if (II) return smem + 2 * kTileBytes + s * (W * BK * 2);
+    return s == 2 ? smem + 2 * kBuf : smem + s * kBuf + kTileBytes;
+  };
   KCursor kc;
   kc.init<A_KC, B_KC>(g, kt0);
-  stage_fast<256>(kc.a, offA, smem, shA);
-  stage_fast<W>(kc.b, offB, smem + kTileBytes, shB);
+  stage_fast<256>(kc.a, offA, abuf(0), shA);
+  stage_fast<W>(kc.b, offB, bslot(0), shB);
   kc.next(g);
   if (wm == 1 && nk > 1) {  // group 1 stages whole tiles one tile earlier (below)
-    stage_fast<256>(kc.a, offA, smem + kBuf, shA);
-    stage_fast<W>(kc.b, offB, smem + kBuf + kTileBytes, shB);
+    stage_fast<256>(kc.a, offA, abuf(1), shA);
+    stage_fast<W>(kc.b, offB, bslot(1), shB);
     kc.next(g);
   }
 
@@ -906,10 +938,86 @@ __global__ void __launch_bounds__(kThreads, 1) gemm256_kernel(GemmArgs g) {
   if (wm == 1) __builtin_amdgcn_s_barrier();  // stagger group 1 by one interval
   bf16x8 af[8][2], bq[NJ][2];
   int ekt = kt0 % ntn;  // (kt0 + u) mod tiles_n (A^T emission rotation)
-  // B3: B buffer of slot s (tiles kt0, kt0 + 1 were staged into slots 0, 1)
-  auto bslot = [&](int s) { return s == 2 ? smem + 2 * kBuf : smem + s * kBuf + kTileBytes; };
-  int bs = 0;  // B3: slot of tile u (u mod 3)
-  for (int u = 0; u < nk; ++u) {
+  int bs = 0;  // B3: slot of tile u (u mod 3; tiles kt0, kt0 + 1 were staged into slots 0, 1)
+  // Both operands I-contiguous (II): the schedule, hand-offs, staging shares
+  // and waits of the loop below (described there), unrolled by two so that
+  // the tile's parity P is a constant.  The 8 + NJ column blocks of a fragment
+  // each need an address VGPR of their own (the XOR swizzle differs per lane;
+  // a K-contiguous operand gets by with two in all), and with the tile's buffer
+  // a run-time value the load interval OPENED with 15 VALU adds (buffer base +
+  // block address) before its first ds_read -- issued at priority 0 beside the
+  // partner's MFMAs at priority 1, they made this layout's kernel 1.22x the
+  // transposed one's cycles (profiles/wgrad_ii_loop.txt; now 1.12x, and level
+  // with it per FLOP inside the training step).  Here the A buffer's offset in
+  // its 64 KiB window (abuf) is part of each read's immediate, so the 8 A
+  // addresses are computed once; the NJ B addresses take one add each for the
+  // slot (three slots span 96 KiB, past the immediate), issued below the A
+  // reads.  Which bytes a group restages, and when, is what it is below --
+  // only where the buffers lie differs -- so the ownership argument given
+  // there covers every wave pair here as it stands.
+  if constexpr (II) {
+    const uint32_t lds0 = (uint32_t)(uintptr_t)((__attribute__((address_space(3))) const char*)smem);
+    uint32_t aaddr[8], baddr[NJ];  // tile-relative fragment addresses of s = 0 (A: in this group's half)
+#pragma unroll
+    for (int ii = 0; ii < 8; ++ii) aaddr[ii] = lds0 + wm * (kTileBytes / 2) + ic_frag_off<128>(16 * ii, lane);
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) baddr[j] = ic_frag_off<W>(wn * WN + 16 * j, lane);
+    auto k_tile = [&](const int u, auto parity) {
+      constexpr int P = decltype(parity)::value;
+      char* cur = abuf(P);
+      char* nxt = abuf(P ^ 1);
+      char* bcur = bslot(bs);
+#pragma unroll
+      for (int ii = 0; ii < 8; ++ii)
+#pragma unroll
+        for (int s = 0; s < 2; ++s) af[ii][s] = ic_frag_at<128>(aaddr[ii], P * kTileBytes, s);
+      const uint32_t bcur0 = (uint32_t)(uintptr_t)((__attribute__((address_space(3))) const char*)bcur);
+#pragma unroll
+      for (int j = 0; j < NJ; ++j) {
+        const uint32_t ba = bcur0 + baddr[j];
+#pragma unroll
+        for (int s = 0; s < 2; ++s) bq[j][s] = ic_frag_at<W>(ba, 0, s);
+      }
+      s16x4 rv;
+      rowsum_read(cur, rv);
+      const int ahead = wm == 0 ? 1 : 2;  // the tile this group stages now
+      if (u + ahead < nk) {
+        stage_fast<256>(kc.a, offA, wm == 0 ? nxt : cur, shA);
+        int bn = bs + ahead;
+        if (bn >= 3) bn -= 3;
+        stage_fast<W>(kc.b, offB, bslot(bn), shB);
+        kc.next(g);
+      }
+      bs = bs == 2 ? 0 : bs + 1;
+      if (wm == 1) {
+        if (u + 2 < nk) vmcnt_keep<NA + NB>();
+        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      }
+      __builtin_amdgcn_s_waitcnt(kWaitLgkm0);  // every read retired before the barrier (see below)
+      rowsum_add(rv);
+      __builtin_amdgcn_sched_barrier(0);
+      __builtin_amdgcn_s_barrier();
+      __builtin_amdgcn_sched_barrier(0);
+      __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+      for (int s = 0; s < 2; ++s)
+#pragma unroll
+        for (int ii = 0; ii < 8; ++ii)
+#pragma unroll
+          for (int j = 0; j < NJ; ++j)
+            acc[ii][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[ii][s], bq[j][s], acc[ii][j], 0, 0, 0);
+      __builtin_amdgcn_s_setprio(0);
+      if (wm == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      __builtin_amdgcn_sched_barrier(0);
+      __builtin_amdgcn_s_barrier();
+      __builtin_amdgcn_sched_barrier(0);
+    };
+    for (int u = 0; u < nk; u += 2) {
+      k_tile(u, std::integral_constant<int, 0>{});
+      if (u + 1 < nk) k_tile(u + 1, std::integral_constant<int, 1>{});
+    }
+  }
+  for (int u = 0; !II && u < nk; ++u) {  // every other layout (II ran its K-tiles above)
     char* cur = smem + (u & 1) * kBuf;
     char* nxt = smem + ((u + 1) & 1) * kBuf;
     char* bcur = B3 ? bslot(bs) : cur + kTileBytes;

@@ -331,11 +331,18 @@ _DEFERRED: Optional[dict] = None
 # (MIPIPE_FUSE_BIAS=0: separate column-sum kernels, for A/B runs).
 _FUSE_BIAS = os.environ.get("MIPIPE_FUSE_BIAS", "1") != "0"
 # Where the K-contiguous x^T of the transposed weight-gradient GEMM
-# (C^T = X^T . dY, ~15 % faster than reading both operands I-contiguous:
-# profiles/wgrad_layout_probe.txt) comes from -- MIPIPE_WGRAD_XT:
+# (C^T = X^T . dY, ~15 % faster than reading both operands I-contiguous in
+# profiles/wgrad_layout_probe.txt, ~7 % since: see auto) comes from -- MIPIPE_WGRAD_XT:
 #   auto (default): the flush transposes x (transpose_b16, a streaming kernel)
 #        for weights with more than 4608 output features, where the GEMM
-#        saving outgrows the transpose (~N_out / 3600 x its cost) -- and the
+#        saving outgrew the transpose (~N_out / 3600 x its cost) when the
+#        threshold was set.  The both-I-contiguous main loop has since lost
+#        most of that gap: at 4096^3 it takes 1.07x the transposed layout's time
+#        (was 1.11x) and 1.12x its cycles (was 1.22x), and in the enc12 step
+#        the 4096-wide I-contiguous weight gradients run at 1.40 PF/s against
+#        the transposed qkv one's 1.41 (profiles/wgrad_ii_loop.txt), so the
+#        break-even lies at least twice as high (~N_out / 7700); the threshold
+#        has not been re-tuned -- and the
 #        bias gradient folds into the GEMM (split-K grids included) instead of
 #        a column-sum pass over dY.  Measured: GPT-2-XL's qkv (4800 outputs)
 #        +0.5 % on the step, every weight (1600 outputs too) -1.4 %
