@@ -419,6 +419,132 @@ Tensor py_rope_heads(Tensor x, Tensor cos, Tensor sin, std::optional<Tensor> out
   return rope_impl(x, cos, sin, out, n_rot, pos0, inverse, "rope_heads");
 }
 
+// ------------------------------------------------------------------ QK-norm
+// The checks the forward and the backward share: x [B, S, heads, D] contiguous with the first n_q heads Q and the
+// next n_k heads K, both weights [D] of x's dtype, tables (both or neither) fp32 [>= pos0 + S, D / 2].
+void qknorm_check(const Tensor& x, const Tensor& wq, const Tensor& wk, const std::optional<Tensor>& cos,
+                  const std::optional<Tensor>& sin, int64_t n_q, int64_t n_k, int64_t pos0, const char* name) {
+  check_cuda(x, "x");
+  check_cuda(wq, "wq");
+  check_cuda(wk, "wk");
+  check_same(x, wq, "x", "wq");
+  check_same(x, wk, "x", "wk");
+  MP_CHECK(x.dim() == 4, name, ": x must be [B, S, heads, D]");
+  const int64_t S = x.size(1), heads = x.size(2), D = x.size(3);
+  MP_CHECK(n_q >= 0 && n_k >= 0 && n_q + n_k <= heads, name, ": n_q + n_k must be in [0, heads], got ", n_q, " + ", n_k,
+           " of ", heads);
+  MP_CHECK(qknorm_supported((int)std::min<int64_t>(D, 1 << 20)), name, ": head dim must be 16, 32, 64, 128 or 256, got ", D);
+  MP_CHECK(wq.numel() == D && wk.numel() == D, name, ": wq and wk must hold D = ", D, " values");
+  MP_CHECK(S <= INT32_MAX / 2 && heads * D <= INT32_MAX / 8 * 3 && x.numel() / D <= (int64_t)1 << 40, name,
+           ": shape too large");
+  MP_CHECK(pos0 >= 0 && pos0 <= INT32_MAX / 2, name, ": bad pos0 ", pos0);
+  MP_CHECK(cos.has_value() == sin.has_value(), name, ": give both cos and sin, or neither");
+  for (auto* t : {&cos, &sin}) {
+    if (!t->has_value()) continue;
+    const Tensor& v = **t;
+    MP_CHECK(v.is_cuda() && v.is_contiguous() && v.scalar_type() == at::kFloat && v.dim() == 2 && v.size(1) == D / 2 &&
+                 v.size(0) >= pos0 + S && v.device() == x.device(),
+             name, ": cos / sin must be contiguous fp32 [>= pos0 + S, D / 2] on x's device");
+    MP_CHECK(reinterpret_cast<uintptr_t>(v.data_ptr()) % 16 == 0, name, ": cos / sin must be 16-byte aligned");
+  }
+  for (auto* t : {&x, &wq, &wk})
+    MP_CHECK(reinterpret_cast<uintptr_t>(t->data_ptr()) % 16 == 0, name, ": x, wq and wk must be 16-byte aligned");
+}
+
+// (y, rstd): out None (a fresh tensor, V copied) or x itself / a disjoint tensor of x's layout; rstd fp32
+// [B * S, n_q + n_k] only with save_rstd (a forward under no_grad allocates none).
+std::tuple<Tensor, std::optional<Tensor>> py_qk_norm_rope_fwd(Tensor x, Tensor wq, Tensor wk, double eps,
+                                                              std::optional<Tensor> cos, std::optional<Tensor> sin,
+                                                              std::optional<Tensor> out, int64_t n_q, int64_t n_k,
+                                                              int64_t pos0, bool save_rstd) {
+  const char* name = "qk_norm_rope_fwd";
+  qknorm_check(x, wq, wk, cos, sin, n_q, n_k, pos0, name);
+  const int64_t B = x.size(0), S = x.size(1), heads = x.size(2), D = x.size(3);
+  at::hip::HIPGuardMasqueradingAsCUDA guard(x.device());
+  Tensor o;
+  if (out.has_value()) {
+    o = *out;
+    check_cuda(o, "out");
+    check_same(x, o, "x", "out");
+    MP_CHECK(o.sizes() == x.sizes(), name, ": out must have x's shape");
+    if (o.data_ptr() != x.data_ptr()) {  // the same tensor or a disjoint one: a partial overlap would race
+      const char* a = static_cast<const char*>(x.data_ptr());
+      const char* b = static_cast<const char*>(o.data_ptr());
+      const int64_t n = (int64_t)x.nbytes();
+      MP_CHECK(b + n <= a || a + n <= b, name, ": out partly overlaps x");
+      MP_CHECK(reinterpret_cast<uintptr_t>(o.data_ptr()) % 16 == 0, name, ": out must be 16-byte aligned");
+    }
+  } else {
+    o = at::empty_like(x);
+  }
+  std::optional<Tensor> rstd;
+  if (save_rstd) rstd = at::empty({B * S, n_q + n_k}, x.options().dtype(at::kFloat));
+  auto s = cur_stream(x);
+  dispatch_fb(x, name, [&](auto* tag) {
+    using T = std::remove_pointer_t<decltype(tag)>;
+    qknorm_rope_fwd<T>(cptr<T>(x), cptr<T>(wq), cptr<T>(wk), optr<float>(cos), optr<float>(sin), ptr<T>(o),
+                       rstd ? ptr<float>(*rstd) : nullptr, B * S, (int)S, (int)n_q, (int)n_k, (int)(heads - n_q - n_k),
+                       (int)D, (int)pos0, (float)eps, s);
+  });
+  return {o, rstd};
+}
+
+// (dx, dwq, dwk).  With acc_q / acc_k (fp32 main_grad views [D]) that weight's gradient is accumulated there and
+// None is returned for it; otherwise it comes back in the weights' dtype.
+std::tuple<Tensor, std::optional<Tensor>, std::optional<Tensor>> py_qk_norm_rope_bwd(
+    Tensor dout, Tensor x, Tensor rstd, Tensor wq, Tensor wk, std::optional<Tensor> cos, std::optional<Tensor> sin,
+    int64_t n_q, int64_t n_k, int64_t pos0, std::optional<Tensor> acc_q, std::optional<Tensor> acc_k) {
+  const char* name = "qk_norm_rope_bwd";
+  qknorm_check(x, wq, wk, cos, sin, n_q, n_k, pos0, name);
+  check_cuda(dout, "dout");
+  check_cuda(rstd, "rstd");
+  check_same(x, dout, "x", "dout");
+  MP_CHECK(dout.sizes() == x.sizes(), name, ": dout must have x's shape");
+  MP_CHECK(reinterpret_cast<uintptr_t>(dout.data_ptr()) % 16 == 0, name, ": dout must be 16-byte aligned");
+  const int64_t B = x.size(0), S = x.size(1), heads = x.size(2), D = x.size(3);
+  MP_CHECK(rstd.scalar_type() == at::kFloat && rstd.numel() == B * S * (n_q + n_k) && rstd.device() == x.device(),
+           name, ": rstd must be fp32 [B * S, n_q + n_k] on x's device");
+  for (auto* a : {&acc_q, &acc_k}) {
+    if (!a->has_value()) continue;
+    const Tensor& v = **a;
+    MP_CHECK(v.is_cuda() && v.device() == x.device() && v.is_contiguous() && v.scalar_type() == at::kFloat &&
+                 v.numel() == D,
+             name, ": an accumulation target must be contiguous fp32 [D] on x's device");
+  }
+  at::hip::HIPGuardMasqueradingAsCUDA guard(x.device());
+  auto dx = at::empty_like(x);
+  Tensor dwq = acc_q ? *acc_q : at::empty_like(wq);
+  Tensor dwk = acc_k ? *acc_k : at::empty_like(wk);
+  std::optional<Tensor> rq, rk;
+  if (!acc_q) rq = dwq;
+  if (!acc_k) rk = dwk;
+  if (x.numel() == 0) {
+    if (!acc_q) dwq.zero_();
+    if (!acc_k) dwk.zero_();
+    return {dx, rq, rk};
+  }
+  const int n_v = (int)(heads - n_q - n_k);
+  const int nparts = qknorm_bwd_parts(B * S, (int)n_q, (int)n_k, n_v, (int)D);
+  auto part = at::empty({2, nparts, D}, x.options().dtype(at::kFloat));
+  float* part_q = ptr<float>(part);
+  float* part_k = part_q + (int64_t)nparts * D;
+  auto s = cur_stream(x);
+  dispatch_fb(x, name, [&](auto* tag) {
+    using T = std::remove_pointer_t<decltype(tag)>;
+    qknorm_rope_bwd<T>(cptr<T>(dout), cptr<T>(x), cptr<float>(rstd), cptr<T>(wq), cptr<T>(wk), optr<float>(cos),
+                       optr<float>(sin), ptr<T>(dx), part_q, part_k, nparts, B * S, (int)S, (int)n_q, (int)n_k, n_v,
+                       (int)D, (int)pos0, s);
+  });
+  const bool f32_q = dwq.scalar_type() == at::kFloat, f32_k = dwk.scalar_type() == at::kFloat;
+  if (f32_q == f32_k && acc_q.has_value() == acc_k.has_value()) {
+    reduce_parts(part_q, part_k, nparts, (int)D, dwq.data_ptr(), dwk.data_ptr(), f32_q, acc_q.has_value(), s);
+  } else {  // one weight accumulates into its fp32 main_grad, the other is stored: one pass each
+    reduce_parts(part_q, nullptr, nparts, (int)D, dwq.data_ptr(), nullptr, f32_q, acc_q.has_value(), s);
+    reduce_parts(part_k, nullptr, nparts, (int)D, dwk.data_ptr(), nullptr, f32_k, acc_k.has_value(), s);
+  }
+  return {dx, rq, rk};
+}
+
 // dkv [B, S, 2, H, D] (per-query-head dK / dV partials) summed per group into the K and V heads of
 // dqkv [B, S, H + 2 Hkv, D]; the Q heads of dqkv are not touched.
 void py_gqa_reduce_dkv(Tensor dkv, Tensor dqkv, int64_t H, int64_t Hkv) {
@@ -1525,6 +1651,16 @@ PYBIND11_MODULE(_C, m) {
   m.def("gqa_reduce_dkv", &py_gqa_reduce_dkv, py::arg("dkv"), py::arg("dqkv"), py::arg("H"), py::arg("Hkv"),
         "dkv [B, S, 2, H, D] per-query-head dK / dV partials -> group sums in the K / V heads of dqkv "
         "[B, S, H + 2 Hkv, D]");
+  m.def("qk_norm_rope_supported", [](int64_t D) { return D > 0 && D <= 256 && qknorm_supported((int)D); });
+  m.def("qk_norm_rope_fwd", &py_qk_norm_rope_fwd, py::arg("x"), py::arg("wq"), py::arg("wk"), py::arg("eps"),
+        py::arg("cos") = py::none(), py::arg("sin") = py::none(), py::arg("out") = py::none(), py::arg("n_q"),
+        py::arg("n_k"), py::arg("pos0") = 0, py::arg("save_rstd") = true,
+        "x [B, S, heads, D]: per-head RMSNorm of the first n_q (wq) and next n_k (wk) heads, then rotated (no "
+        "tables: the norm alone); the rest passed through.  Returns (y, rstd or None)");
+  m.def("qk_norm_rope_bwd", &py_qk_norm_rope_bwd, py::arg("dout"), py::arg("x"), py::arg("rstd"), py::arg("wq"),
+        py::arg("wk"), py::arg("cos") = py::none(), py::arg("sin") = py::none(), py::arg("n_q"), py::arg("n_k"),
+        py::arg("pos0") = 0, py::arg("acc_q") = py::none(), py::arg("acc_k") = py::none(),
+        "(dx, dwq, dwk); a weight gradient with an fp32 accumulation target is added there and returned as None");
   m.def("bias_act_fwd", &py_bias_act_fwd);
   m.def("bias_act_bwd", &py_bias_act_bwd, py::arg("dy"), py::arg("saved"), py::arg("bias"), py::arg("act"),
         py::arg("p"), py::arg("seed"), py::arg("offset"), py::arg("need_dbias"), py::arg("dbias_acc") = py::none());

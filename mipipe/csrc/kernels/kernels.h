@@ -127,6 +127,26 @@ void rope_heads(const T* x, const float* cos_t, const float* sin_t, T* out, int6
 template <typename T>
 void gqa_reduce_dkv(const T* dkv, T* dqkv, int64_t tokens, int H, int Hkv, int D, hipStream_t s);
 
+// ------------------------------------------------------------------ QK-norm (qknorm.hip)
+// Per-head RMSNorm of the Q and K heads of x [tokens, n_q + n_k + n_v, D] (contiguous, rope_heads' layout; the
+// n_v V heads pass through) fused with the rotary rotation: y = rotate(x rsqrt(mean(x^2) + eps) w) with w = wq [D]
+// for the first n_q heads and wk [D] for the next n_k, fp32 arithmetic, one rounding at the store.  cos_t == nullptr
+// drops the rotation (the norm alone); otherwise cos / sin are fp32 [>= pos0 + S, D/2] and a token's position is
+// pos0 + token % S.  out == x works in place (V untouched), otherwise V is copied.  rstd (optional): fp32
+// [tokens, n_q + n_k], written for the backward.  D must satisfy qknorm_supported; 16-byte aligned pointers.
+bool qknorm_supported(int D);
+template <typename T>
+void qknorm_rope_fwd(const T* x, const T* wq, const T* wk, const float* cos_t, const float* sin_t, T* out, float* rstd,
+                     int64_t tokens, int S, int n_q, int n_k, int n_v, int D, int pos0, float eps, hipStream_t s);
+// dx (a tensor of its own) from dout, the forward's x and rstd: g = inverse-rotate(dout), xhat = x rstd, gy = g w,
+// dx = rstd (gy - xhat mean(gy xhat)); V rows: dx = dout.  Block b writes its fp32 sums over rows of g xhat into
+// part_q[b] and part_k[b] ([nparts, D] each, nparts = qknorm_bwd_parts(...)): the caller sums them with reduce_parts.
+int qknorm_bwd_parts(int64_t tokens, int n_q, int n_k, int n_v, int D);
+template <typename T>
+void qknorm_rope_bwd(const T* dout, const T* x, const float* rstd, const T* wq, const T* wk, const float* cos_t,
+                     const float* sin_t, T* dx, float* part_q, float* part_k, int nparts, int64_t tokens, int S,
+                     int n_q, int n_k, int n_v, int D, int pos0, hipStream_t s);
+
 // ------------------------------------------------------------------ elementwise
 enum Activation : int { kActNone = 0, kActRelu = 1, kActGelu = 2 };
 // Backward-only activation code: the saved tensor IS act'(pre) (a GELU forward

@@ -208,6 +208,7 @@ class LMConfig:
     positions: Optional[str] = None  # Encoder positions; None: "learned" if learned_positions else "sinusoidal"
     n_kv_heads: Optional[int] = None  # grouped-query attention: K/V heads (a divisor of nhead); None = nhead
     window: Optional[int] = None      # sliding-window attention: keys a query sees, its own included (causal only)
+    qk_norm: bool = False             # per-head RMSNorm on Q and K before the rotation (Qwen3): two [head_dim] weights
 
     def qkv_dim(self) -> int:
         """Width of the QKV projection: ``(H + 2 Hkv) D`` (``3 d_model`` without grouped-query attention)."""
@@ -226,6 +227,8 @@ class LMConfig:
         norm = e * (2 if self.norm == "layer" else 1)
         qkv = self.qkv_dim()
         layer = (qkv + e) * e + 2 * norm + f1 * e + e * f + nb * (qkv + e + f1 + e)
+        if self.qk_norm:
+            layer += 2 * (e // self.nhead)
         total = self.num_layers * layer + v * e
         if self.encoder_positions() == "learned":
             total += max(self.seq_len, 1024) * e
@@ -280,6 +283,16 @@ CONFIGS = {
                            norm_first=True, causal=True, scale_embedding=False, act_dropout=0.0, norm="rms",
                            bias=False, rope=True, rope_base=10000.0, positions="none", n_kv_heads=8, window=4096,
                            notes="Mistral 7B's block; the decoder is untied and keeps its (zero-initialised) bias"),
+    # llama_gqa_tiny with QK-norm: every Q and K head RMS-normalised before the rotation.
+    "qwen3_tiny": LMConfig("qwen3_tiny", 2, 256, 4, 512, 1000, 64, dropout=0.0, activation="swiglu",
+                           norm_first=True, causal=True, scale_embedding=False, act_dropout=0.0, norm="rms",
+                           bias=False, rope=True, positions="none", n_kv_heads=2, qk_norm=True,
+                           notes="tiny Qwen3-style model (grouped-query attention, QK-norm) for tests"),
+    # Qwen3 8B: 36 layers, 32 query heads over 8 K/V heads of width 128, QK-norm, rope base 1,000,000.
+    "qwen3_8b": LMConfig("qwen3_8b", 36, 4096, 32, 12288, 151936, 32768, dropout=0.0, activation="swiglu",
+                         norm_first=True, causal=True, scale_embedding=False, act_dropout=0.0, norm="rms",
+                         bias=False, rope=True, rope_base=1000000.0, positions="none", n_kv_heads=8, qk_norm=True,
+                         notes="Qwen3 8B's block; the decoder is untied and keeps its (zero-initialised) bias"),
 }
 
 
@@ -293,7 +306,7 @@ def build_lm_blocks(cfg: LMConfig, *, device=None, dtype=None) -> List[nn.Module
     blocks += transformer_blocks(cfg.num_layers, cfg.d_model, cfg.nhead, cfg.dim_feedforward, cfg.dropout,
                                  cfg.activation, norm_first=cfg.norm_first, causal=cfg.causal, norm=cfg.norm,
                                  bias=cfg.bias, rope=cfg.rope, rope_base=cfg.rope_base, n_kv_heads=cfg.n_kv_heads,
-                                 window=cfg.window, device=device, dtype=dtype)
+                                 window=cfg.window, qk_norm=cfg.qk_norm, device=device, dtype=dtype)
     if cfg.act_dropout is not None:
         for b in blocks:
             if isinstance(b, FeedForwardBlock):

@@ -31,6 +31,11 @@ then of the ``Hkv`` V heads -- and query head ``h`` attends with K/V head
 ``h // (H / Hkv)`` (``ops.attention_gqa_packed``).  ``window=W`` (causal blocks
 only; ``None`` means none) is sliding-window attention: a query attends the
 last ``W`` keys, its own included (Mistral's ``sliding_window``).
+``qk_norm=True`` (Qwen3) RMS-normalises every Q head and every K head over its
+``D`` features before the rotation, with the learned ``[D]`` weights
+``q_norm_weight`` and ``k_norm_weight`` of the attention core and the block's
+``layer_norm_eps`` (``ops.qk_norm_rope_projection``: one kernel with the
+rotation, or the norm alone with ``rope=False``).
 """
 from __future__ import annotations
 
@@ -129,7 +134,7 @@ class AttentionCore(nn.Module):
     def __init__(self, d_model: int, nhead: int, dropout: float, *, norm_first: bool, causal: bool,
                  layer_norm_eps: float, norm: str = "layer", bias: bool = True, rope: bool = False,
                  rope_base: float = 10000.0, n_kv_heads: Optional[int] = None, window: Optional[int] = None,
-                 device=None, dtype=None) -> None:
+                 qk_norm: bool = False, device=None, dtype=None) -> None:
         super().__init__()
         fk = {"device": device, "dtype": dtype}
         self.d_model, self.nhead, self.head_dim = d_model, nhead, d_model // nhead
@@ -157,6 +162,12 @@ class AttentionCore(nn.Module):
             empty = torch.empty(0, self.head_dim // 2, device=device, dtype=torch.float32)
             self.register_buffer("rope_cos", empty, persistent=False)
             self.register_buffer("rope_sin", empty.clone(), persistent=False)
+        self.qk_norm = bool(qk_norm)
+        if self.qk_norm:
+            # per-head RMSNorm weights of the Q and of the K heads (not GEMM weights: the norm's backward writes
+            # their gradients)
+            self.q_norm_weight = nn.Parameter(torch.empty(self.head_dim, **fk))
+            self.k_norm_weight = nn.Parameter(torch.empty(self.head_dim, **fk))
         self.reset_parameters()
 
     def reset_parameters(self) -> None:
@@ -166,6 +177,9 @@ class AttentionCore(nn.Module):
             nn.init.zeros_(self.in_proj_bias)
         if self.norm_first:
             _reset_norm(self)
+        if self.qk_norm:
+            nn.init.ones_(self.q_norm_weight)
+            nn.init.ones_(self.k_norm_weight)
 
     def _rope_tables(self, seq_len: int, device):
         # rebuilt when too short, on another device, or cast by a module-wide .to(dtype): the kernel reads fp32
@@ -199,6 +213,18 @@ class AttentionCore(nn.Module):
         # The projection output viewed as [B, S, 3, H, D] feeds the kernel in
         # place; its output [B, S, H, D] is already [B, S, E] -- no transposes.
         Hkv = self.n_kv_heads
+        if self.qk_norm:
+            # Q and K heads normalised (and rotated, with rope) in one pass: where rope_projection runs otherwise
+            cos, sin = self._rope_tables(S, qkv.device) if self.rope else (None, None)
+            qkv_n = ops.qk_norm_rope_projection(qkv, self.q_norm_weight, self.k_norm_weight, self.eps, cos, sin, H,
+                                                n_kv_heads=Hkv)
+            if Hkv != H:
+                o = ops.attention_gqa_packed(qkv_n, Hkv, causal=self.causal, dropout_p=self.dropout,
+                                             training=self.training, window=self.window)
+            else:
+                o = ops.attention_packed(qkv_n, causal=self.causal, dropout_p=self.dropout, training=self.training,
+                                         window=self.window)
+            return o.reshape(B, S, E), xr
         if Hkv != H:
             # grouped-query attention: [B, S, H + 2 Hkv, D], the K/V heads read in place by every query head
             # of their group
@@ -276,14 +302,14 @@ class SelfAttentionBlock(nn.Module):
     def __init__(self, d_model: int, nhead: int, dropout: float = 0.1, *, norm_first: bool = False,
                  causal: bool = False, layer_norm_eps: float = 1e-5, norm: str = "layer", bias: bool = True,
                  rope: bool = False, rope_base: float = 10000.0, n_kv_heads: Optional[int] = None,
-                 window: Optional[int] = None, device=None, dtype=None) -> None:
+                 window: Optional[int] = None, qk_norm: bool = False, device=None, dtype=None) -> None:
         super().__init__()
         if d_model % nhead != 0:
             raise ValueError("d_model must be divisible by nhead")
         self.core = AttentionCore(d_model, nhead, dropout, norm_first=norm_first, causal=causal,
                                   layer_norm_eps=layer_norm_eps, norm=norm, bias=bias, rope=rope,
-                                  rope_base=rope_base, n_kv_heads=n_kv_heads, window=window, device=device,
-                                  dtype=dtype)
+                                  rope_base=rope_base, n_kv_heads=n_kv_heads, window=window, qk_norm=qk_norm,
+                                  device=device, dtype=dtype)
         self.out = AttentionOutput(d_model, dropout, norm_first=norm_first, layer_norm_eps=layer_norm_eps,
                                    norm=norm, bias=bias, device=device, dtype=dtype)
 
@@ -568,11 +594,12 @@ class TransformerEncoderLayer(nn.Sequential):
         rope_base: float = 10000.0,
         n_kv_heads: Optional[int] = None,
         window: Optional[int] = None,
+        qk_norm: bool = False,
     ) -> None:
         super().__init__(
             SelfAttentionBlock(d_model, nhead, dropout, norm_first=norm_first, causal=causal,
                                layer_norm_eps=layer_norm_eps, norm=norm, bias=bias, rope=rope, rope_base=rope_base,
-                               n_kv_heads=n_kv_heads, window=window, device=device, dtype=dtype),
+                               n_kv_heads=n_kv_heads, window=window, qk_norm=qk_norm, device=device, dtype=dtype),
             FeedForwardBlock(d_model, dim_feedforward, dropout, activation, norm_first=norm_first,
                              layer_norm_eps=layer_norm_eps, norm=norm, bias=bias, device=device, dtype=dtype),
         )
@@ -617,6 +644,7 @@ def transformer_blocks(
     rope_base: float = 10000.0,
     n_kv_heads: Optional[int] = None,
     window: Optional[int] = None,
+    qk_norm: bool = False,
     device=None,
     dtype=None,
 ) -> List[nn.Module]:
@@ -625,8 +653,8 @@ def transformer_blocks(
     for _ in range(num_layers):
         layer = TransformerEncoderLayer(d_model, nhead, dim_feedforward, dropout, activation,
                                         norm_first=norm_first, causal=causal, norm=norm, bias=bias, rope=rope,
-                                        rope_base=rope_base, n_kv_heads=n_kv_heads, window=window, device=device,
-                                        dtype=dtype)
+                                        rope_base=rope_base, n_kv_heads=n_kv_heads, window=window, qk_norm=qk_norm,
+                                        device=device, dtype=dtype)
         blocks.extend(layer.children())
     return blocks
 

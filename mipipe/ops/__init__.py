@@ -12,6 +12,7 @@ from .attention import attention, attention_gqa_packed, attention_packed, attent
 from .activation import bias_act_dropout
 from .swiglu import swiglu, swiglu_reference
 from .rope import rope_heads, rope_packed, rope_projection, rope_reference, rope_tables
+from .qknorm import qk_norm_rope_heads, qk_norm_rope_projection, qk_norm_rope_reference
 from .loss import cross_entropy
 from .embedding import embed_scale_posenc_dropout
 
@@ -39,6 +40,9 @@ __all__ = [
     "rope_projection",
     "rope_heads",
     "rope_reference",
+    "qk_norm_rope_heads",
+    "qk_norm_rope_projection",
+    "qk_norm_rope_reference",
     "cross_entropy",
     "embed_scale_posenc_dropout",
 ]
