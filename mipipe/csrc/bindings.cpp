@@ -594,6 +594,80 @@ std::tuple<Tensor, int64_t, int64_t> py_bias_act_fwd(Tensor x, std::optional<Ten
 
 Tensor py_column_sum(Tensor x, std::optional<Tensor> out, bool accumulate);
 
+// Logit soft-capping.  A tensor is read as rows of its last dim: unit stride there, and leading dims that
+// collapse to one row stride (a contiguous tensor, or the [:, :V] view of a padded one).
+struct RowView { int64_t rows = 1, cols = 0, ld = 0; };
+RowView softcap_rows(const Tensor& t, const char* who, const char* name) {
+  RowView r;
+  if (t.dim() == 0) { r.cols = 1; r.ld = 1; return r; }
+  const int64_t n = t.dim();
+  r.cols = t.size(n - 1);
+  r.ld = r.cols;
+  MP_CHECK(r.cols <= 1 || t.stride(n - 1) == 1, who, ": ", name, " needs unit stride on its last dim");
+  if (n >= 2) {
+    r.ld = t.stride(n - 2);
+    r.rows = t.size(n - 2);
+    MP_CHECK(r.rows <= 1 || r.ld >= r.cols, who, ": ", name, " has overlapping rows");
+    for (int64_t i = n - 3; i >= 0; --i) {
+      MP_CHECK(t.size(i) <= 1 || t.stride(i) == t.stride(i + 1) * t.size(i + 1), who, ": ", name,
+               " must have one row stride (make it contiguous)");
+      r.rows *= t.size(i);
+    }
+  }
+  return r;
+}
+
+float softcap_cap(const char* who, double cap) {
+  const float c = (float)cap;
+  MP_CHECK(std::isfinite(cap) && cap > 0.0 && std::isfinite(c) && c > 0.f, who, ": cap must be a finite value > 0, got ",
+           cap);
+  return c;
+}
+
+// y = cap * tanh(x / cap); `out` (x itself for the in-place form) or a new contiguous tensor.
+Tensor py_softcap_fwd(Tensor x, double cap, std::optional<Tensor> out) {
+  MP_CHECK(x.is_cuda(), "softcap: x must be a GPU tensor");
+  const float c = softcap_cap("softcap", cap);
+  at::hip::HIPGuardMasqueradingAsCUDA guard(x.device());
+  Tensor y = out ? *out : at::empty(x.sizes(), x.options());
+  if (out) {
+    MP_CHECK(y.is_cuda(), "softcap: out must be a GPU tensor");
+    check_same(x, y, "x", "out");
+    MP_CHECK(y.sizes() == x.sizes(), "softcap: out must have x's shape");
+  }
+  const RowView rx = softcap_rows(x, "softcap", "x"), ry = softcap_rows(y, "softcap", "out");
+  auto s = cur_stream(x);
+  dispatch_fb(x, "softcap", [&](auto* tag) {
+    using T = std::remove_pointer_t<decltype(tag)>;
+    softcap_fwd<T>(cptr<T>(x), rx.ld, ptr<T>(y), ry.ld, rx.rows, rx.cols, c, s);
+  });
+  return y;
+}
+
+// dx = dy * (1 - (y / cap)^2) from the saved output y; `out` (dy itself for the in-place form) or a new tensor.
+Tensor py_softcap_bwd(Tensor dy, Tensor y, double cap, std::optional<Tensor> out) {
+  MP_CHECK(dy.is_cuda(), "softcap: dy must be a GPU tensor");
+  MP_CHECK(y.is_cuda(), "softcap: y must be a GPU tensor");
+  check_same(dy, y, "dy", "y");
+  MP_CHECK(dy.sizes() == y.sizes(), "softcap_bwd: dy and y shapes differ");
+  const float c = softcap_cap("softcap_bwd", cap);
+  at::hip::HIPGuardMasqueradingAsCUDA guard(dy.device());
+  Tensor dx = out ? *out : at::empty(dy.sizes(), dy.options());
+  if (out) {
+    MP_CHECK(dx.is_cuda(), "softcap: out must be a GPU tensor");
+    check_same(dy, dx, "dy", "out");
+    MP_CHECK(dx.sizes() == dy.sizes(), "softcap_bwd: out must have dy's shape");
+  }
+  const RowView rd = softcap_rows(dy, "softcap_bwd", "dy"), ry = softcap_rows(y, "softcap_bwd", "y"),
+                ro = softcap_rows(dx, "softcap_bwd", "out");
+  auto s = cur_stream(dy);
+  dispatch_fb(dy, "softcap_bwd", [&](auto* tag) {
+    using T = std::remove_pointer_t<decltype(tag)>;
+    softcap_bwd<T>(cptr<T>(dy), rd.ld, cptr<T>(y), ry.ld, ptr<T>(dx), ro.ld, rd.rows, rd.cols, c, s);
+  });
+  return dx;
+}
+
 std::tuple<Tensor, std::optional<Tensor>> py_bias_act_bwd(Tensor dy, Tensor saved, std::optional<Tensor> bias,
                                                           int64_t act, double p, int64_t seed, int64_t offset,
                                                           bool need_dbias, std::optional<Tensor> dbias_acc) {
@@ -1360,18 +1434,31 @@ int attn_window(const char* who, int64_t window, bool causal, const Tensor& q, i
   return window >= S ? 0 : (int)window;
 }
 
+// Logit soft-capping (0 = none, else a finite cap > 0): bf16 only, and always on attention.hip's generic kernels.
+float attn_softcap(const char* who, double softcap, const Tensor& q) {
+  MP_CHECK(std::isfinite(softcap) && softcap >= 0.0, who, ": softcap must be a finite value >= 0 (0 = none), got ",
+           softcap);
+  if (softcap == 0.0) return 0.f;
+  MP_CHECK(q.scalar_type() == at::kBFloat16, who, ": soft-capped attention runs on the bf16 kernels only, got ",
+           q.scalar_type());
+  const float c = (float)softcap;
+  MP_CHECK(std::isfinite(c) && c > 0.f, who, ": softcap ", softcap, " is not a finite positive float");
+  return c;
+}
+
 // Returns (o, lse, seed, offset, dropout keep bits): the bits tensor (int32
 // [B*H, S/32, S]) is non-empty only for the long-sequence kernels with p > 0
-// and must be handed back to attention_bwd.  A windowed call (0 < window < S) returns none.
+// and must be handed back to attention_bwd.  A windowed call (0 < window < S) or a soft-capped one returns none.
 // `words` (with the Philox draw it was made under): keep words an earlier forward of this same draw returned
 // (a checkpoint's first forward, reused by its recompute) -- read instead of made, when the draw matches.
 std::tuple<Tensor, Tensor, int64_t, int64_t, Tensor> py_attention_fwd(Tensor q, Tensor k, Tensor v, bool causal,
                                                                       double p, double scale, int64_t kv_len,
                                                                       std::optional<Tensor> words, int64_t words_seed,
-                                                                      int64_t words_offset, int64_t window) {
+                                                                      int64_t words_offset, int64_t window, double softcap) {
   AttnArgs a;
   fill_qkv(a, q, k, v);
   a.window = attn_window("attention", window, causal, q, a.S);
+  a.softcap = attn_softcap("attention", softcap, q);
   MP_CHECK(p >= 0.0 && p < 1.0, "attention: bad dropout p");
   MP_CHECK(kv_len == 0 || (q.scalar_type() == at::kFloat && kv_len > 0 && kv_len <= a.S),
            "attention: kv_len (a key-length bound) is for fp32, 0 < kv_len <= S");
@@ -1387,7 +1474,7 @@ std::tuple<Tensor, Tensor, int64_t, int64_t, Tensor> py_attention_fwd(Tensor q, 
   Tensor bits = at::empty({0}, q.options().dtype(at::kInt));
   if (q.scalar_type() == at::kFloat) {
     attention_f32_fwd(a, cur_stream(q));
-  } else if (a.window == 0 && use_long(q, a.S, a.D)) {
+  } else if (a.window == 0 && a.softcap == 0.f && use_long(q, a.S, a.D)) {
     bool reuse = false;
     if (p > 0.0) {
       const std::vector<int64_t> shape = {(int64_t)a.B * a.H, a.S / 32, a.S};
@@ -1407,10 +1494,11 @@ std::tuple<Tensor, Tensor, int64_t, int64_t, Tensor> py_attention_fwd(Tensor q, 
 
 void py_attention_bwd(Tensor dout, Tensor q, Tensor k, Tensor v, Tensor o, Tensor lse, bool causal, double p,
                       double scale, int64_t seed, int64_t offset, Tensor dq, Tensor dk, Tensor dv,
-                      std::optional<Tensor> bits, int64_t kv_len, int64_t window) {
+                      std::optional<Tensor> bits, int64_t kv_len, int64_t window, double softcap) {
   AttnArgs a;
   fill_qkv(a, q, k, v);
   a.window = attn_window("attention_bwd", window, causal, q, a.S);
+  a.softcap = attn_softcap("attention_bwd", softcap, q);
   MP_CHECK(kv_len == 0 || (q.scalar_type() == at::kFloat && kv_len > 0 && kv_len <= a.S),
            "attention_bwd: kv_len (a key-length bound) is for fp32, 0 < kv_len <= S");
   a.kv_len = (int)kv_len;
@@ -1452,7 +1540,7 @@ void py_attention_bwd(Tensor dout, Tensor q, Tensor k, Tensor v, Tensor o, Tenso
   a.scale = (float)scale; a.p = (float)p; a.seed = (uint64_t)seed; a.offset = (uint64_t)offset; a.causal = causal;
   if (q.scalar_type() == at::kFloat) {
     attention_f32_bwd(a, cur_stream(q));
-  } else if (a.window == 0 && use_long(q, a.S, a.D)) {
+  } else if (a.window == 0 && a.softcap == 0.f && use_long(q, a.S, a.D)) {
     if (p > 0.0) {
       MP_CHECK(bits && bits->is_cuda() && bits->scalar_type() == at::kInt &&
                    bits->numel() == (int64_t)a.B * a.H * (a.S / 32) * a.S,
@@ -1662,6 +1750,8 @@ PYBIND11_MODULE(_C, m) {
         py::arg("pos0") = 0, py::arg("acc_q") = py::none(), py::arg("acc_k") = py::none(),
         "(dx, dwq, dwk); a weight gradient with an fp32 accumulation target is added there and returned as None");
   m.def("bias_act_fwd", &py_bias_act_fwd);
+  m.def("softcap_fwd", &py_softcap_fwd, py::arg("x"), py::arg("cap"), py::arg("out") = py::none());
+  m.def("softcap_bwd", &py_softcap_bwd, py::arg("dy"), py::arg("y"), py::arg("cap"), py::arg("out") = py::none());
   m.def("bias_act_bwd", &py_bias_act_bwd, py::arg("dy"), py::arg("saved"), py::arg("bias"), py::arg("act"),
         py::arg("p"), py::arg("seed"), py::arg("offset"), py::arg("need_dbias"), py::arg("dbias_acc") = py::none());
   m.def("column_sum", &py_column_sum, py::arg("x"), py::arg("out") = py::none(), py::arg("accumulate") = false);
@@ -1680,11 +1770,11 @@ PYBIND11_MODULE(_C, m) {
   m.def("attention_f32_supported", [](int64_t S, int64_t D) { return attention_f32_supported((int)S, (int)D); });
   m.def("attention_fwd", &py_attention_fwd, py::arg("q"), py::arg("k"), py::arg("v"), py::arg("causal"), py::arg("p"),
         py::arg("scale"), py::arg("kv_len") = 0, py::arg("words") = py::none(), py::arg("words_seed") = 0,
-        py::arg("words_offset") = 0, py::arg("window") = 0);
+        py::arg("words_offset") = 0, py::arg("window") = 0, py::arg("softcap") = 0.0);
   m.def("attention_bwd", &py_attention_bwd, py::arg("dout"), py::arg("q"), py::arg("k"), py::arg("v"), py::arg("o"),
         py::arg("lse"), py::arg("causal"), py::arg("p"), py::arg("scale"), py::arg("seed"), py::arg("offset"),
         py::arg("dq"), py::arg("dk"), py::arg("dv"), py::arg("bits") = py::none(), py::arg("kv_len") = 0,
-        py::arg("window") = 0);
+        py::arg("window") = 0, py::arg("softcap") = 0.0);
   m.def("attention_long_supported", [](int64_t S, int64_t D) { return attention_long_supported((int)S, (int)D); });
   m.def("attention_long_set_fused_rng", &attention_long_set_fused_rng,
         "long-sequence attention: make the dropout keep words inside the forward kernel (true, default) or in a "

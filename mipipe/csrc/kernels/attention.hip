@@ -190,13 +190,25 @@ __device__ __forceinline__ float row_reduce_sum16(float v) {
   return v;
 }
 
+// ------------------------------------------------------------------ logit soft-capping
+// SOFTCAP: the score s = scale * (q . k) becomes c * tanh(s / c) (c = a.softcap > 0) before the masks and the
+// softmax.  With e = exp2(raw * cap_in), cap_in = 2 * scale * log2e / c, tanh(s / c) = 1 - 2 / (1 + e): one
+// exp2 and one rcp, no division.  e = inf gives r = 0 and t = 1, e = 0 gives r = 1 and t = -1: no NaN at either
+// end.  The absolute fp32 error of t is about 2e-7 (the cancellation in 1 - 2r near s = 0 is against 1, not
+// against t), so the capped score is off by about c * 2e-7: negligible against bf16 P for c up to a few hundred,
+// and growing with c.  Returns r; t = 1 - 2r, and the derivative 1 - t^2 = 4 r (1 - r).
+__device__ __forceinline__ float softcap_r(float raw, float cap_in) {
+  return __builtin_amdgcn_rcpf(1.f + __builtin_amdgcn_exp2f(raw * cap_in));
+}
+
 // ------------------------------------------------------------------ forward
+// SOFTCAP: the capped score (softcap_r) replaces the scaled one; lse is the log-sum-exp of the capped scores.
 // WINDOW (only with CAUSAL): sliding-window attention, query i sees the a.window keys (i - a.window, i].  The
 // key-tile loop then starts at the first tile that holds a visible key of the tile's first query row instead of
 // at 0; the tiles wholly below the band are never loaded.  A later row of the query tile can find the first
 // visited tile wholly masked: its running max stays -inf there and the m == -inf guards below give alpha = 0 and
 // p = 0, as they do for a fresh row, so exp2 never sees (-inf) - (-inf).
-template <int D, bool CAUSAL, bool WINDOW = false>
+template <int D, bool CAUSAL, bool WINDOW = false, bool SOFTCAP = false>
 __global__ void __launch_bounds__(kThreads, D == 256 ? 1 : 2) attn_fwd_kernel(AttnArgs a) {
   static_assert(!WINDOW || CAUSAL, "the sliding window is a band of the causal mask");
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -238,6 +250,8 @@ __global__ void __launch_bounds__(kThreads, D == 256 ? 1 : 2) attn_fwd_kernel(At
   const int ntiles = CAUSAL ? qt + 1 : a.S / kRows;
   const int tbeg = WINDOW ? max(0, q0 - a.window + 1) / kRows : 0;  // first tile with a key row q0 sees
   const int wrow0 = WINDOW ? qrow0 - a.window : 0;                  // row qrow0 + r sees keys > wrow0 + r
+  const float cap_in = SOFTCAP ? 2.f * sl2 / a.softcap : 0.f;       // raw score -> exponent of e (softcap_r)
+  const float cap_l2 = SOFTCAP ? a.softcap * kLog2e : 0.f;          // t -> capped score, log2 domain
 
   constexpr bool PF = D <= 128;
   TileRegs kr, vr;
@@ -278,7 +292,9 @@ __global__ void __launch_bounds__(kThreads, D == 256 ? 1 : 2) attn_fwd_kernel(At
       const int key = k0 + 16 * j + (lane & 15);
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        float x = sacc[j][r] * sl2;
+        float x;
+        if constexpr (SOFTCAP) x = (1.f - 2.f * softcap_r(sacc[j][r], cap_in)) * cap_l2;
+        else x = sacc[j][r] * sl2;
         if (CAUSAL && key > qrow0 + r) x = -INFINITY;
         if (WINDOW && key <= wrow0 + r) x = -INFINITY;
         sv[j][r] = x;
@@ -590,7 +606,7 @@ __global__ void __launch_bounds__(kThreads) attn_delta_mfma_kernel(AttnArgs a) {
 
 // ------------------------------------------------------------------ dQ
 // WINDOW: the forward's key-tile range and band mask (see attn_fwd_kernel).
-template <int D, bool CAUSAL, bool WINDOW = false>
+template <int D, bool CAUSAL, bool WINDOW = false, bool SOFTCAP = false>
 __global__ void __launch_bounds__(kThreads, D == 256 ? 1 : 2) attn_dq_kernel(AttnArgs a) {
   static_assert(!WINDOW || CAUSAL, "the sliding window is a band of the causal mask");
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -633,6 +649,8 @@ __global__ void __launch_bounds__(kThreads, D == 256 ? 1 : 2) attn_dq_kernel(Att
   const int ntiles = CAUSAL ? qt + 1 : a.S / kRows;
   const int tbeg = WINDOW ? max(0, q0 - a.window + 1) / kRows : 0;  // first tile with a key row q0 sees
   const int wrow0 = WINDOW ? qrow0 - a.window : 0;                  // row qrow0 + r sees keys > wrow0 + r
+  const float cap_in = SOFTCAP ? 2.f * sl2 / a.softcap : 0.f;       // as in attn_fwd_kernel
+  const float cap_l2 = SOFTCAP ? a.softcap * kLog2e : 0.f;
 
   constexpr bool PF = D <= 128;
   TileRegs kr, vr;
@@ -676,12 +694,20 @@ __global__ void __launch_bounds__(kThreads, D == 256 ? 1 : 2) attn_dq_kernel(Att
       }
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        float pr = __builtin_amdgcn_exp2f(sacc[j][r] * sl2 - lse2[r]);
+        float pr, dcap = 1.f;  // dcap: d(capped score) / d(score) = 1 - t^2
+        if constexpr (SOFTCAP) {
+          const float rc = softcap_r(sacc[j][r], cap_in);
+          pr = __builtin_amdgcn_exp2f((1.f - 2.f * rc) * cap_l2 - lse2[r]);
+          dcap = 4.f * rc * (1.f - rc);
+        } else {
+          pr = __builtin_amdgcn_exp2f(sacc[j][r] * sl2 - lse2[r]);
+        }
         if (CAUSAL && key > qrow0 + r) pr = 0.f;
         if (WINDOW && key <= wrow0 + r) pr = 0.f;
         float dp = pacc[j][r];
         if (a.p > 0.f) dp = w[r] >= a.threshold ? dp * pscale : 0.f;
         ds[j][r] = pr * (dp - dl[r]);
+        if constexpr (SOFTCAP) ds[j][r] *= dcap;
       }
     }
     scratch_write(scr, ds, lane);
@@ -840,7 +866,7 @@ __global__ void __launch_bounds__(kThreads, 2) attn_dq_wide_kernel(AttnArgs a) {
 // ------------------------------------------------------------------ dK, dV
 // WINDOW (only with CAUSAL): key j is seen by the queries [j, j + a.window), so the query-tile loop ends at the
 // tile of query k0 + 63 + a.window - 1 instead of at the sequence's last one.
-template <int D, bool CAUSAL, bool WINDOW = false>
+template <int D, bool CAUSAL, bool WINDOW = false, bool SOFTCAP = false>
 __global__ void __launch_bounds__(kThreads, D >= 128 ? 1 : 2) attn_dkdv_kernel(AttnArgs a) {
   static_assert(!WINDOW || CAUSAL, "the sliding window is a band of the causal mask");
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -879,6 +905,8 @@ __global__ void __launch_bounds__(kThreads, D >= 128 ? 1 : 2) attn_dkdv_kernel(A
   // one past the last query tile: the loop end, computed once (the window is not read again)
   const int nq = WINDOW ? min(a.S / kRows, (k0 + kRows - 1 + a.window - 1) / kRows + 1) : a.S / kRows;
   const int wkey0 = WINDOW ? key0 + a.window : 0;  // key key0 + r is seen by the queries < wkey0 + r
+  const float cap_in = SOFTCAP ? 2.f * sl2 / a.softcap : 0.f;  // as in attn_fwd_kernel
+  const float cap_l2 = SOFTCAP ? a.softcap * kLog2e : 0.f;
 
   constexpr bool PF = D <= 128;
   TileRegs qr, dr;
@@ -946,7 +974,14 @@ __global__ void __launch_bounds__(kThreads, D >= 128 ? 1 : 2) attn_dkdv_kernel(A
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int key = key0 + r;
-        float pr = __builtin_amdgcn_exp2f(sacc[j][r] * sl2 - l2);
+        float pr, dcap = 1.f;  // dcap: d(capped score) / d(score) = 1 - t^2
+        if constexpr (SOFTCAP) {
+          const float rc = softcap_r(sacc[j][r], cap_in);
+          pr = __builtin_amdgcn_exp2f((1.f - 2.f * rc) * cap_l2 - l2);
+          dcap = 4.f * rc * (1.f - rc);
+        } else {
+          pr = __builtin_amdgcn_exp2f(sacc[j][r] * sl2 - l2);
+        }
         if (CAUSAL && key > q) pr = 0.f;
         if (WINDOW && q >= wkey0 + r) pr = 0.f;
         float dp = pacc[j][r];
@@ -959,6 +994,7 @@ __global__ void __launch_bounds__(kThreads, D >= 128 ? 1 : 2) attn_dkdv_kernel(A
         }
         pd[j][r] = pdrop;
         ds[j][r] = pr * (dp - dl);
+        if constexpr (SOFTCAP) ds[j][r] *= dcap;
       }
     }
     scratch_write(scr, pd, lane);
@@ -1487,6 +1523,47 @@ void normalise_window(AttnArgs& a) {
   if (!a.causal || a.window < 0 || a.window >= a.S) a.window = 0;
 }
 
+// Logit soft-capping (a.softcap > 0): always the generic 64-row kernels too, at every S and D, non-causal,
+// causal, or causal with a window -- the S = 128, wide D = 64 and long-sequence kernels know no cap.
+template <int D, bool CAUSAL, bool WINDOW>
+void run_fwd_softcap(const AttnArgs& a, hipStream_t s) {
+  const size_t sm = fwd_smem<D>();
+  static bool once = false;
+  if (!once) { set_smem(attn_fwd_kernel<D, CAUSAL, WINDOW, true>, sm); once = true; }
+  hipLaunchKernelGGL((attn_fwd_kernel<D, CAUSAL, WINDOW, true>), dim3(a.S / kRows, a.B * a.H), dim3(kThreads), sm, s,
+                     a);
+}
+
+// delta from attn_delta_mfma_kernel on every path, as the windowed backward takes it.
+template <int D, bool CAUSAL, bool WINDOW>
+void run_bwd_softcap(const AttnArgs& a, hipStream_t s) {
+  const size_t sm = fwd_smem<D>(), sm2 = dkdv_smem<D>();
+  static bool once = false;
+  if (!once) {
+    set_smem(attn_dq_kernel<D, CAUSAL, WINDOW, true>, sm);
+    set_smem(attn_dkdv_kernel<D, CAUSAL, WINDOW, true>, sm2);
+    once = true;
+  }
+  const dim3 grid(a.S / kRows, a.B * a.H);
+  hipLaunchKernelGGL((attn_delta_mfma_kernel<D>), grid, dim3(kThreads), 0, s, a);
+  hipLaunchKernelGGL((attn_dkdv_kernel<D, CAUSAL, WINDOW, true>), grid, dim3(kThreads), sm2, s, a);
+  hipLaunchKernelGGL((attn_dq_kernel<D, CAUSAL, WINDOW, true>), grid, dim3(kThreads), sm, s, a);
+}
+
+template <int D>
+void fwd_softcap(const AttnArgs& a, hipStream_t s) {
+  if (a.window > 0) run_fwd_softcap<D, true, true>(a, s);
+  else if (a.causal) run_fwd_softcap<D, true, false>(a, s);
+  else run_fwd_softcap<D, false, false>(a, s);
+}
+
+template <int D>
+void bwd_softcap(const AttnArgs& a, hipStream_t s) {
+  if (a.window > 0) run_bwd_softcap<D, true, true>(a, s);
+  else if (a.causal) run_bwd_softcap<D, true, false>(a, s);
+  else run_bwd_softcap<D, false, false>(a, s);
+}
+
 }  // namespace
 
 void attention_set_fused_bwd(int on) { g_attn_fused_bwd = on; }
@@ -1497,6 +1574,12 @@ void attention_fwd(const AttnArgs& ai, hipStream_t s) {
   AttnArgs a = attn_resolved(ai);
   a.threshold = dropout_threshold(a.p);
   normalise_window(a);
+  if (a.softcap > 0.f) {
+    if (a.D == 64) fwd_softcap<64>(a, s);
+    else if (a.D == 128) fwd_softcap<128>(a, s);
+    else fwd_softcap<256>(a, s);
+    return;
+  }
   if (a.window > 0) {
     if (a.D == 64) run_fwd_window<64>(a, s);
     else if (a.D == 128) run_fwd_window<128>(a, s);
@@ -1518,6 +1601,12 @@ void attention_bwd(const AttnArgs& ai, hipStream_t s) {
   AttnArgs a = attn_resolved(ai);
   a.threshold = dropout_threshold(a.p);
   normalise_window(a);
+  if (a.softcap > 0.f) {
+    if (a.D == 64) bwd_softcap<64>(a, s);
+    else if (a.D == 128) bwd_softcap<128>(a, s);
+    else bwd_softcap<256>(a, s);
+    return;
+  }
   if (a.window > 0) {
     if (a.D == 64) run_bwd_window<64>(a, s);
     else if (a.D == 128) run_bwd_window<128>(a, s);

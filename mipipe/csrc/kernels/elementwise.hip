@@ -8,6 +8,8 @@
 // stores nothing extra.  GELU (erf form, torch's default) reads the
 // pre-activation.  Memory-bound: 16-byte vectors, grid-stride, mask from
 // Philox, never stored.
+//
+// Also here: logit soft-capping, y = cap * tanh(x / cap) (softcap_kernel).
 #include "common.h"
 #include "kernels.h"
 
@@ -167,6 +169,61 @@ __global__ void __launch_bounds__(256) colsum_part_scalar_kernel(const T* __rest
   }
 }
 
+// Logit soft-capping y = cap * tanh(x / cap), and its backward from the saved OUTPUT: dx = dy * (1 - (y / cap)^2).
+// `rows` rows of `cols` values, row r of each tensor at r * its ld (rows of a padded buffer, as loss.hip reads
+// them).  A thread owns 8 consecutive values of one row: one 16-byte load and store where every base and ld is
+// 16-byte aligned (row_vec8_ok) and the 8 lie inside the row, else element by element -- the tail of a row whose
+// width is no multiple of 8, and every chunk of an unaligned tensor.  fp32 arithmetic, one rounding at the store;
+// out may be in (or dy) itself: each value is read and written by the same thread.
+template <typename T>
+__device__ __forceinline__ bool row_vec8_ok(const T* p, int64_t ld) {
+  return (reinterpret_cast<uintptr_t>(p) % 16 == 0) && ((ld * (int64_t)sizeof(T)) % 16 == 0);
+}
+
+template <typename T, bool BWD>
+__global__ void __launch_bounds__(256) softcap_kernel(const T* in, int64_t ld_in, const T* saved,
+                                                      int64_t ld_saved, T* out, int64_t ld_out, int64_t rows,
+                                                      int64_t cols, float cap, float inv_cap) {
+  const int64_t cvec = (cols + 7) >> 3;
+  const int64_t ntiles = rows * cvec;
+  const bool vec = row_vec8_ok(in, ld_in) && row_vec8_ok(out, ld_out) && (!BWD || row_vec8_ok(saved, ld_saved));
+  for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; t < ntiles; t += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t r = t / cvec;
+    const int64_t c0 = (t - r * cvec) * 8;
+    const T* x = in + r * ld_in + c0;
+    T* o = out + r * ld_out + c0;
+    if (vec && c0 + 8 <= cols) {
+      float a[8];
+      Io<T>::load8(x, a);
+      if (BWD) {
+        float y[8];
+        Io<T>::load8(saved + r * ld_saved + c0, y);
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+          const float tn = y[i] * inv_cap;
+          a[i] *= 1.f - tn * tn;
+        }
+      } else {
+#pragma unroll
+        for (int i = 0; i < 8; ++i) a[i] = cap * tanhf(a[i] * inv_cap);
+      }
+      Io<T>::store8(o, a);
+    } else {
+      const int n = (int)(cols - c0 < 8 ? cols - c0 : 8);
+      for (int i = 0; i < n; ++i) {
+        float a = Io<T>::load(x + i);
+        if (BWD) {
+          const float tn = Io<T>::load(saved + r * ld_saved + c0 + i) * inv_cap;
+          a *= 1.f - tn * tn;
+        } else {
+          a = cap * tanhf(a * inv_cap);
+        }
+        Io<T>::store(o + i, a);
+      }
+    }
+  }
+}
+
 int64_t grid_for(int64_t nvec) {
   int64_t g = (nvec + 255) / 256;
   return g < 2048 ? (g < 1 ? 1 : g) : 2048;
@@ -201,6 +258,23 @@ template <typename T>
 void bias_act_dropout_bwd(const T* dy, const T* saved, const T* bias, T* dx, int64_t rows, int cols, int act, float p,
                           uint64_t seed, uint64_t offset, hipStream_t s) {
   launch_bias_act<T, true>(dy, saved, bias, dx, rows, cols, act, p, seed, offset, s);
+}
+
+template <typename T>
+void softcap_fwd(const T* x, int64_t ld_x, T* y, int64_t ld_y, int64_t rows, int64_t cols, float cap, hipStream_t s) {
+  const int64_t ntiles = rows * ((cols + 7) / 8);
+  if (ntiles == 0) return;
+  hipLaunchKernelGGL((softcap_kernel<T, false>), dim3((unsigned)grid_for(ntiles)), dim3(256), 0, s, x, ld_x,
+                     (const T*)nullptr, (int64_t)0, y, ld_y, rows, cols, cap, 1.f / cap);
+}
+
+template <typename T>
+void softcap_bwd(const T* dy, int64_t ld_dy, const T* y, int64_t ld_y, T* dx, int64_t ld_dx, int64_t rows,
+                 int64_t cols, float cap, hipStream_t s) {
+  const int64_t ntiles = rows * ((cols + 7) / 8);
+  if (ntiles == 0) return;
+  hipLaunchKernelGGL((softcap_kernel<T, true>), dim3((unsigned)grid_for(ntiles)), dim3(256), 0, s, dy, ld_dy, y, ld_y,
+                     dx, ld_dx, rows, cols, cap, 1.f / cap);
 }
 
 int colsum_parts(int64_t rows, int64_t cols) {
@@ -265,6 +339,10 @@ template void bias_act_dropout_fwd<float>(const float*, const float*, float*, in
 template void bias_act_dropout_fwd<bf16_t>(const bf16_t*, const bf16_t*, bf16_t*, int64_t, int, int, float, uint64_t, uint64_t, hipStream_t);
 template void bias_act_dropout_bwd<float>(const float*, const float*, const float*, float*, int64_t, int, int, float, uint64_t, uint64_t, hipStream_t);
 template void bias_act_dropout_bwd<bf16_t>(const bf16_t*, const bf16_t*, const bf16_t*, bf16_t*, int64_t, int, int, float, uint64_t, uint64_t, hipStream_t);
+template void softcap_fwd<float>(const float*, int64_t, float*, int64_t, int64_t, int64_t, float, hipStream_t);
+template void softcap_fwd<bf16_t>(const bf16_t*, int64_t, bf16_t*, int64_t, int64_t, int64_t, float, hipStream_t);
+template void softcap_bwd<float>(const float*, int64_t, const float*, int64_t, float*, int64_t, int64_t, int64_t, float, hipStream_t);
+template void softcap_bwd<bf16_t>(const bf16_t*, int64_t, const bf16_t*, int64_t, bf16_t*, int64_t, int64_t, int64_t, float, hipStream_t);
 template void column_sum_partial<float>(const float*, int64_t, int, float*, int, hipStream_t);
 template void column_sum_partial<bf16_t>(const bf16_t*, int64_t, int, float*, int, hipStream_t);
 template bool column_sum_partial_multi<float>(const ColsumSegs&, int, int64_t, int, float*, int, hipStream_t);

@@ -163,6 +163,13 @@ void bias_act_dropout_fwd(const T* x, const T* bias, T* y, int64_t rows, int col
 template <typename T>
 void bias_act_dropout_bwd(const T* dy, const T* saved, const T* bias, T* dx, int64_t rows, int cols, int act, float p,
                           uint64_t seed, uint64_t offset, hipStream_t s);
+// Logit soft-capping y = cap * tanh(x / cap) (cap > 0) over `rows` rows of `cols` values, row r at r * ld of each
+// tensor; y may be x.  The backward reads the saved output: dx = dy * (1 - (y / cap)^2); dx may be dy.
+template <typename T>
+void softcap_fwd(const T* x, int64_t ld_x, T* y, int64_t ld_y, int64_t rows, int64_t cols, float cap, hipStream_t s);
+template <typename T>
+void softcap_bwd(const T* dy, int64_t ld_dy, const T* y, int64_t ld_y, T* dx, int64_t ld_dx, int64_t rows,
+                 int64_t cols, float cap, hipStream_t s);
 int colsum_parts(int64_t rows, int64_t cols);
 // Up to kColsumSegs equally shaped inputs whose stage-1 column sums run as one launch.
 constexpr int kColsumSegs = 16;
@@ -322,6 +329,10 @@ struct AttnArgs {
   // Sliding-window attention (bf16 attention.hip, causal only): query i sees the `window` keys (i - window, i];
   // 0 = no window.  Kept the LAST member: no other member's offset in the kernel-argument segment moves.
   int window = 0;
+  // Logit soft-capping (bf16 attention.hip's generic kernels): the scaled score s becomes softcap * tanh(s /
+  // softcap) before the masks and the softmax; 0 = no cap, else a finite float > 0.  Appended after `window` for
+  // the same reason.
+  float softcap = 0.f;
 };
 // K / V head of query head h: h / group as a scalar multiply by ceil(2^20 / group) and a shift instead of a
 // division.  Exact for every h when group == 1 (the 64-bit product is h * 2^20) and while h * group < 2^20

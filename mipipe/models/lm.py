@@ -21,6 +21,7 @@ from torch import Tensor, nn
 
 from .. import ops
 from ..ops.linear import mark_gemm_weight
+from ..ops.softcap import softcap_owned
 from .transformer import FeedForwardBlock, transformer_blocks
 
 __all__ = [
@@ -124,12 +125,27 @@ class Decoder(nn.Module):
     ``pad_to`` (256: the large GEMM tile) -- zero rows, zero bias -- so the logits
     GEMM runs on the MFMA tile kernel; ``forward`` returns the ``[..., :V]``
     view and the fused cross-entropy reads it in place (strided rows).
+
+    ``final_softcap=c`` (Gemma-2's ``final_logit_softcapping``) caps the logits
+    at ``c * tanh(y / c)``: ``ops.softcap`` on the padded GEMM output, before the
+    slice -- the pad columns stay exactly 0 (``tanh(0) = 0``), and so do the
+    pad columns of the gradient.  It overwrites the GEMM output
+    (``ops.softcap_owned``): ``ops.linear`` without an activation reads no output
+    in its backward, and the cap's backward needs the capped logits only, which
+    the cross-entropy saves anyway -- the cap holds no logits-sized tensor.
     """
 
-    def __init__(self, ntoken: int, d_model: int, *, pad_to: int = 256, device=None, dtype=None) -> None:
+    def __init__(self, ntoken: int, d_model: int, *, pad_to: int = 256, final_softcap: Optional[float] = None,
+                 device=None, dtype=None) -> None:
         super().__init__()
         fk = {"device": device, "dtype": dtype}
         self.ntoken = ntoken
+        if final_softcap is not None:
+            if (isinstance(final_softcap, bool) or not isinstance(final_softcap, (int, float))
+                    or not math.isfinite(final_softcap) or final_softcap <= 0):
+                raise ValueError(f"final_softcap must be a finite number > 0 or None, got {final_softcap!r}")
+            final_softcap = float(final_softcap)
+        self.final_softcap = final_softcap
         self.padded = (ntoken + pad_to - 1) // pad_to * pad_to
         self.weight = mark_gemm_weight(nn.Parameter(torch.empty(self.padded, d_model, **fk)))
         self.bias = nn.Parameter(torch.zeros(self.padded, **fk))
@@ -143,6 +159,8 @@ class Decoder(nn.Module):
 
     def forward(self, x: Tensor) -> Tensor:
         y = ops.linear(x, self.weight, self.bias)
+        if self.final_softcap is not None:
+            y = softcap_owned(y, self.final_softcap)  # y is this forward's own: nothing else reads it
         if self.padded == self.ntoken:
             return y
         if y.is_cuda and torch.is_grad_enabled() and y.requires_grad:
@@ -208,6 +226,8 @@ class LMConfig:
     positions: Optional[str] = None  # Encoder positions; None: "learned" if learned_positions else "sinusoidal"
     n_kv_heads: Optional[int] = None  # grouped-query attention: K/V heads (a divisor of nhead); None = nhead
     window: Optional[int] = None      # sliding-window attention: keys a query sees, its own included (causal only)
+    attn_softcap: Optional[float] = None   # attention scores capped at c * tanh(s / c) before the softmax (Gemma-2)
+    final_softcap: Optional[float] = None  # output logits capped the same way before the loss (Gemma-2)
     qk_norm: bool = False             # per-head RMSNorm on Q and K before the rotation (Qwen3): two [head_dim] weights
 
     def qkv_dim(self) -> int:
@@ -283,6 +303,16 @@ CONFIGS = {
                            norm_first=True, causal=True, scale_embedding=False, act_dropout=0.0, norm="rms",
                            bias=False, rope=True, rope_base=10000.0, positions="none", n_kv_heads=8, window=4096,
                            notes="Mistral 7B's block; the decoder is untied and keeps its (zero-initialised) bias"),
+    # mistral_tiny with Gemma-2's two soft caps (50 on the attention scores, 30 on the output logits).  No
+    # full-size Gemma-2 config: every Gemma-2 size has a head dim decoupled from d_model / nhead, a GeGLU MLP,
+    # post-norms and alternating local / global layers, none of which these blocks have.
+    "gemma2_tiny": LMConfig("gemma2_tiny", 2, 256, 4, 512, 1000, 192, dropout=0.0, activation="swiglu",
+                            norm_first=True, causal=True, scale_embedding=False, act_dropout=0.0, norm="rms",
+                            bias=False, rope=True, positions="none", n_kv_heads=2, window=48, attn_softcap=50.0,
+                            final_softcap=30.0,
+                            notes="mistral_tiny plus Gemma-2's soft caps: attention scores at 50, output logits at "
+                                  "30 (not a Gemma-2 size: those decouple the head dim from d_model / nhead and use "
+                                  "GeGLU, post-norms and alternating local / global layers)"),
     # llama_gqa_tiny with QK-norm: every Q and K head RMS-normalised before the rotation.
     "qwen3_tiny": LMConfig("qwen3_tiny", 2, 256, 4, 512, 1000, 64, dropout=0.0, activation="swiglu",
                            norm_first=True, causal=True, scale_embedding=False, act_dropout=0.0, norm="rms",
@@ -306,14 +336,15 @@ def build_lm_blocks(cfg: LMConfig, *, device=None, dtype=None) -> List[nn.Module
     blocks += transformer_blocks(cfg.num_layers, cfg.d_model, cfg.nhead, cfg.dim_feedforward, cfg.dropout,
                                  cfg.activation, norm_first=cfg.norm_first, causal=cfg.causal, norm=cfg.norm,
                                  bias=cfg.bias, rope=cfg.rope, rope_base=cfg.rope_base, n_kv_heads=cfg.n_kv_heads,
-                                 window=cfg.window, qk_norm=cfg.qk_norm, device=device, dtype=dtype)
+                                 window=cfg.window, qk_norm=cfg.qk_norm, attn_softcap=cfg.attn_softcap,
+                                 device=device, dtype=dtype)
     if cfg.act_dropout is not None:
         for b in blocks:
             if isinstance(b, FeedForwardBlock):
                 b.fc_in.dropout = cfg.act_dropout
     if cfg.norm_first:
         blocks.append(FinalNorm(cfg.d_model, norm=cfg.norm, device=device, dtype=dtype))
-    blocks.append(Decoder(cfg.vocab, cfg.d_model, device=device, dtype=dtype))
+    blocks.append(Decoder(cfg.vocab, cfg.d_model, final_softcap=cfg.final_softcap, device=device, dtype=dtype))
     return blocks
 
 
@@ -342,7 +373,8 @@ def lm_pipeline_units(blocks: List[nn.Module], *, split_decoder: bool = False) -
     from .vocab_split import split_decoder as _split
 
     units = pipeline_units(blocks)
-    if split_decoder and isinstance(units[-1], Decoder):
+    # a soft-capped decoder is not split: the vocabulary-split kernels fuse the row statistics and know no cap
+    if split_decoder and isinstance(units[-1], Decoder) and units[-1].final_softcap is None:
         head, tail = _split(units[-1])
         units = units[:-1] + [head, tail]
     return units

@@ -31,6 +31,8 @@ then of the ``Hkv`` V heads -- and query head ``h`` attends with K/V head
 ``h // (H / Hkv)`` (``ops.attention_gqa_packed``).  ``window=W`` (causal blocks
 only; ``None`` means none) is sliding-window attention: a query attends the
 last ``W`` keys, its own included (Mistral's ``sliding_window``).
+``attn_softcap=c`` (``None`` means none) caps the attention scores at ``c *
+tanh(s / c)`` before the softmax (Gemma-2's ``attn_logit_softcapping``).
 ``qk_norm=True`` (Qwen3) RMS-normalises every Q head and every K head over its
 ``D`` features before the rotation, with the learned ``[D]`` weights
 ``q_norm_weight`` and ``k_norm_weight`` of the attention core and the block's
@@ -134,10 +136,16 @@ class AttentionCore(nn.Module):
     def __init__(self, d_model: int, nhead: int, dropout: float, *, norm_first: bool, causal: bool,
                  layer_norm_eps: float, norm: str = "layer", bias: bool = True, rope: bool = False,
                  rope_base: float = 10000.0, n_kv_heads: Optional[int] = None, window: Optional[int] = None,
-                 qk_norm: bool = False, device=None, dtype=None) -> None:
+                 qk_norm: bool = False, attn_softcap: Optional[float] = None, device=None, dtype=None) -> None:
         super().__init__()
         fk = {"device": device, "dtype": dtype}
         self.d_model, self.nhead, self.head_dim = d_model, nhead, d_model // nhead
+        if attn_softcap is not None:
+            if (isinstance(attn_softcap, bool) or not isinstance(attn_softcap, (int, float))
+                    or not math.isfinite(attn_softcap) or attn_softcap <= 0):
+                raise ValueError(f"attn_softcap must be a finite number > 0 or None, got {attn_softcap!r}")
+            attn_softcap = float(attn_softcap)
+        self.attn_softcap = attn_softcap
         if window is not None:
             if isinstance(window, bool) or not isinstance(window, int) or window < 1:
                 raise ValueError(f"window must be an int >= 1 or None, got {window!r}")
@@ -220,10 +228,11 @@ class AttentionCore(nn.Module):
                                                 n_kv_heads=Hkv)
             if Hkv != H:
                 o = ops.attention_gqa_packed(qkv_n, Hkv, causal=self.causal, dropout_p=self.dropout,
-                                             training=self.training, window=self.window)
+                                             training=self.training, window=self.window,
+                                             softcap=self.attn_softcap)
             else:
                 o = ops.attention_packed(qkv_n, causal=self.causal, dropout_p=self.dropout, training=self.training,
-                                         window=self.window)
+                                         window=self.window, softcap=self.attn_softcap)
             return o.reshape(B, S, E), xr
         if Hkv != H:
             # grouped-query attention: [B, S, H + 2 Hkv, D], the K/V heads read in place by every query head
@@ -234,7 +243,8 @@ class AttentionCore(nn.Module):
             else:
                 qkv4 = qkv.view(B, S, H + 2 * Hkv, D)
             o = ops.attention_gqa_packed(qkv4, Hkv, causal=self.causal, dropout_p=self.dropout,
-                                         training=self.training, window=self.window)
+                                         training=self.training, window=self.window,
+                                             softcap=self.attn_softcap)
             return o.reshape(B, S, E), xr
         if self.rope:
             # Q and K rotated: in the projection's own output where no graph is recorded, else into a new tensor
@@ -243,7 +253,7 @@ class AttentionCore(nn.Module):
         else:
             qkv5 = qkv.view(B, S, 3, H, D)
         o = ops.attention_packed(qkv5, causal=self.causal, dropout_p=self.dropout, training=self.training,
-                                 window=self.window)
+                                 window=self.window, softcap=self.attn_softcap)
         return o.reshape(B, S, E), xr
 
     def flops_per_token(self, seq_len: int) -> float:
@@ -302,14 +312,15 @@ class SelfAttentionBlock(nn.Module):
     def __init__(self, d_model: int, nhead: int, dropout: float = 0.1, *, norm_first: bool = False,
                  causal: bool = False, layer_norm_eps: float = 1e-5, norm: str = "layer", bias: bool = True,
                  rope: bool = False, rope_base: float = 10000.0, n_kv_heads: Optional[int] = None,
-                 window: Optional[int] = None, qk_norm: bool = False, device=None, dtype=None) -> None:
+                 window: Optional[int] = None, qk_norm: bool = False, attn_softcap: Optional[float] = None,
+                 device=None, dtype=None) -> None:
         super().__init__()
         if d_model % nhead != 0:
             raise ValueError("d_model must be divisible by nhead")
         self.core = AttentionCore(d_model, nhead, dropout, norm_first=norm_first, causal=causal,
                                   layer_norm_eps=layer_norm_eps, norm=norm, bias=bias, rope=rope,
                                   rope_base=rope_base, n_kv_heads=n_kv_heads, window=window, qk_norm=qk_norm,
-                                  device=device, dtype=dtype)
+                                  attn_softcap=attn_softcap, device=device, dtype=dtype)
         self.out = AttentionOutput(d_model, dropout, norm_first=norm_first, layer_norm_eps=layer_norm_eps,
                                    norm=norm, bias=bias, device=device, dtype=dtype)
 
@@ -595,11 +606,13 @@ class TransformerEncoderLayer(nn.Sequential):
         n_kv_heads: Optional[int] = None,
         window: Optional[int] = None,
         qk_norm: bool = False,
+        attn_softcap: Optional[float] = None,
     ) -> None:
         super().__init__(
             SelfAttentionBlock(d_model, nhead, dropout, norm_first=norm_first, causal=causal,
                                layer_norm_eps=layer_norm_eps, norm=norm, bias=bias, rope=rope, rope_base=rope_base,
-                               n_kv_heads=n_kv_heads, window=window, qk_norm=qk_norm, device=device, dtype=dtype),
+                               n_kv_heads=n_kv_heads, window=window, qk_norm=qk_norm, attn_softcap=attn_softcap,
+                               device=device, dtype=dtype),
             FeedForwardBlock(d_model, dim_feedforward, dropout, activation, norm_first=norm_first,
                              layer_norm_eps=layer_norm_eps, norm=norm, bias=bias, device=device, dtype=dtype),
         )
@@ -645,6 +658,7 @@ def transformer_blocks(
     n_kv_heads: Optional[int] = None,
     window: Optional[int] = None,
     qk_norm: bool = False,
+    attn_softcap: Optional[float] = None,
     device=None,
     dtype=None,
 ) -> List[nn.Module]:
@@ -654,7 +668,7 @@ def transformer_blocks(
         layer = TransformerEncoderLayer(d_model, nhead, dim_feedforward, dropout, activation,
                                         norm_first=norm_first, causal=causal, norm=norm, bias=bias, rope=rope,
                                         rope_base=rope_base, n_kv_heads=n_kv_heads, window=window, qk_norm=qk_norm,
-                                        device=device, dtype=dtype)
+                                        attn_softcap=attn_softcap, device=device, dtype=dtype)
         blocks.extend(layer.children())
     return blocks
 

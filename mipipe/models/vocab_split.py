@@ -275,7 +275,11 @@ class DecoderTail(nn.Module):
 
 
 def split_decoder(dec: nn.Module) -> Tuple[DecoderHead, DecoderTail]:
-    """Head/tail holding copies of a :class:`~mipipe.models.lm.Decoder`'s rows."""
+    """Head/tail holding copies of a :class:`~mipipe.models.lm.Decoder`'s rows.  A decoder with a final soft
+    cap is refused: the head and tail kernels fuse the row statistics of the uncapped logits."""
+    if getattr(dec, "final_softcap", None) is not None:
+        raise ValueError(f"split_decoder: a decoder with final_softcap={dec.final_softcap} cannot be split along "
+                         "the vocabulary (the vocabulary-split kernels do not apply the cap)")
     v, e = dec.ntoken, dec.weight.shape[1]
     va = split_point(v)
     fk = {"device": dec.weight.device, "dtype": dec.weight.dtype}

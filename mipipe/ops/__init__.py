@@ -10,6 +10,7 @@ from .rmsnorm import add_dropout_rms_norm, rms_norm_fanout, rms_norm_reference
 from .linear import deferred_wgrad, flush_wgrad, linear, linear_fanout, linear_residual
 from .attention import attention, attention_gqa_packed, attention_packed, attention_reference
 from .activation import bias_act_dropout
+from .softcap import softcap, softcap_owned, softcap_reference
 from .swiglu import swiglu, swiglu_reference
 from .rope import rope_heads, rope_packed, rope_projection, rope_reference, rope_tables
 from .qknorm import qk_norm_rope_heads, qk_norm_rope_projection, qk_norm_rope_reference
@@ -33,6 +34,9 @@ __all__ = [
     "attention_gqa_packed",
     "attention_reference",
     "bias_act_dropout",
+    "softcap",
+    "softcap_owned",
+    "softcap_reference",
     "swiglu",
     "swiglu_reference",
     "rope_tables",

@@ -48,6 +48,21 @@ the band.  The padded shapes above stay native too: padded keys lie after
 every real query and padded features add 0.  fp32 sliding-window attention is
 not native: it, the CPU and the shapes ``_run_shape`` rejects use the eager
 math of :func:`attention_reference` with the band mask.
+
+Logit soft-capping: every entry point takes a keyword-only ``softcap=c`` (a
+finite number > 0; ``None`` is no cap and the code path it always was): the
+scaled scores become ``c * tanh(s / c)`` before the masks and the softmax --
+flash-attn's ``softcap``, Gemma-2's ``attn_logit_softcapping``.  A bf16 call on
+the GPU runs attention.hip's generic kernels (non-causal, causal, or causal
+with a window), whatever S and D; grouped-query heads are read in place and
+the dropout mask is the uncapped call's.  Causal end padding and head-dim
+padding stay native (padded features add 0 to the raw score, before the cap).
+A non-causal sequence of an unsupported length does not: the spare-feature key
+mask scores a padded key at ``-32768 * scale`` and the cap would bring that
+back to ``-c``, so that shape, fp32 and the CPU use :func:`attention_reference`.
+The kernels take ``tanh`` as ``1 - 2 / (1 + exp2(.))`` in fp32: its absolute
+error of about 2e-7 is an error of about ``c * 2e-7`` in the capped score, so
+it grows with ``c`` (nothing at 30 or 50; 1e-3 in the exponent at 5000).
 """
 from __future__ import annotations
 
@@ -80,14 +95,29 @@ def _check_window(window: Optional[int], causal: bool, S: int) -> Optional[int]:
     return None if window >= S else window
 
 
+def _check_softcap(softcap: Optional[float]) -> Optional[float]:
+    """``softcap`` validated: ``None`` (no cap) or a finite number > 0, returned as a float."""
+    if softcap is None:
+        return None
+    if isinstance(softcap, bool) or not isinstance(softcap, (int, float)):
+        raise ValueError(f"attention: softcap must be a finite number > 0 or None, got {softcap!r}")
+    if not math.isfinite(softcap) or softcap <= 0:
+        raise ValueError(f"attention: softcap must be finite and > 0 (None: no cap), got {softcap!r}")
+    return float(softcap)
+
+
 def attention_reference(q: Tensor, k: Tensor, v: Tensor, causal: bool, p: float, scale: Optional[float] = None,
-                        *, window: Optional[int] = None) -> Tensor:
+                        *, window: Optional[int] = None, softcap: Optional[float] = None) -> Tensor:
     """Eager fp32 math on ``[B, H, S, D]`` (CPU path and test oracle).  ``window``: query ``i`` sees the keys
-    ``i - window < j <= i`` only."""
+    ``i - window < j <= i`` only.  ``softcap``: the scaled scores become ``softcap * tanh(s / softcap)`` before
+    the masks."""
     d = q.shape[-1]
     scale = scale if scale is not None else 1.0 / math.sqrt(d)
     window = _check_window(window, bool(causal), q.shape[-2])
+    softcap = _check_softcap(softcap)
     s = torch.matmul(q.float(), k.float().transpose(-1, -2)) * scale
+    if softcap is not None:
+        s = softcap * torch.tanh(s / softcap)
     if causal:
         n, m = s.shape[-2], s.shape[-1]
         mask = torch.ones(n, m, dtype=torch.bool, device=s.device).triu(1 + m - n)
@@ -136,10 +166,10 @@ def clear_keep_words() -> None:
         _keep_bytes = 0
 
 
-def _attention_fwd(kern, q, k, v, causal, p, scale, kv_len, window=0):
+def _attention_fwd(kern, q, k, v, causal, p, scale, kv_len, window=0, softcap=0.0):
     global _keep_bytes
-    if window:  # the generic kernels: the mask is regenerated from Philox, there are no keep words
-        return kern.attention_fwd(q, k, v, causal, p, scale, kv_len, None, 0, 0, window)
+    if window or softcap:  # the generic kernels: the mask is regenerated from Philox, there are no keep words
+        return kern.attention_fwd(q, k, v, causal, p, scale, kv_len, None, 0, 0, window, softcap)
     reuse = _KEEP_REUSE and p > 0 and q.is_cuda and q.dtype == torch.bfloat16 and kv_len == 0
     words = key = None
     if reuse and is_recomputing():
@@ -171,13 +201,13 @@ class _AttentionPacked(torch.autograd.Function):
     backward produces the packed ``dqkv`` in one buffer."""
 
     @staticmethod
-    def forward(ctx, qkv, causal, p, scale, kv_len=0, window=0):  # type: ignore[override]
+    def forward(ctx, qkv, causal, p, scale, kv_len=0, window=0, softcap=0.0):  # type: ignore[override]
         kern = kernels_for(qkv)
         q, k, v = qkv.select(2, 0), qkv.select(2, 1), qkv.select(2, 2)
-        o, lse, seed, offset, bits = _attention_fwd(kern, q, k, v, causal, p, scale, kv_len, window)
+        o, lse, seed, offset, bits = _attention_fwd(kern, q, k, v, causal, p, scale, kv_len, window, softcap)
         ctx.save_for_backward(qkv, o, lse, bits)
         ctx.causal, ctx.p, ctx.scale, ctx.seed, ctx.offset, ctx.kv_len = causal, p, scale, seed, offset, kv_len
-        ctx.window = window
+        ctx.window, ctx.softcap = window, softcap
         return o
 
     @staticmethod
@@ -189,20 +219,20 @@ class _AttentionPacked(torch.autograd.Function):
         dqkv = torch.empty_like(qkv)
         kern.attention_bwd(do, qkv.select(2, 0), qkv.select(2, 1), qkv.select(2, 2), o, lse, ctx.causal, ctx.p,
                            ctx.scale, ctx.seed, ctx.offset, dqkv.select(2, 0), dqkv.select(2, 1), dqkv.select(2, 2),
-                           bits if bits.numel() else None, ctx.kv_len, ctx.window)
-        return dqkv, None, None, None, None, None
+                           bits if bits.numel() else None, ctx.kv_len, ctx.window, ctx.softcap)
+        return dqkv, None, None, None, None, None, None
 
 
 class _Attention(torch.autograd.Function):
     """Separate q, k, v as [B, S, H, D] views sharing one layout."""
 
     @staticmethod
-    def forward(ctx, q, k, v, causal, p, scale, kv_len=0, window=0):  # type: ignore[override]
+    def forward(ctx, q, k, v, causal, p, scale, kv_len=0, window=0, softcap=0.0):  # type: ignore[override]
         kern = kernels_for(q)
-        o, lse, seed, offset, bits = _attention_fwd(kern, q, k, v, causal, p, scale, kv_len, window)
+        o, lse, seed, offset, bits = _attention_fwd(kern, q, k, v, causal, p, scale, kv_len, window, softcap)
         ctx.save_for_backward(q, k, v, o, lse, bits)
         ctx.causal, ctx.p, ctx.scale, ctx.seed, ctx.offset, ctx.kv_len = causal, p, scale, seed, offset, kv_len
-        ctx.window = window
+        ctx.window, ctx.softcap = window, softcap
         return o
 
     @staticmethod
@@ -213,8 +243,8 @@ class _Attention(torch.autograd.Function):
             do = do.contiguous()
         dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
         kern.attention_bwd(do, q, k, v, o, lse, ctx.causal, ctx.p, ctx.scale, ctx.seed, ctx.offset, dq, dk, dv,
-                           bits if bits.numel() else None, ctx.kv_len, ctx.window)
-        return dq, dk, dv, None, None, None, None, None
+                           bits if bits.numel() else None, ctx.kv_len, ctx.window, ctx.softcap)
+        return dq, dk, dv, None, None, None, None, None, None
 
 
 class _AttentionGqaPacked(torch.autograd.Function):
@@ -223,14 +253,14 @@ class _AttentionGqaPacked(torch.autograd.Function):
     dK / dV into one packed ``dqkv`` of the same layout (the binding owns the per-query-head scratch)."""
 
     @staticmethod
-    def forward(ctx, qkv, n_kv, causal, p, scale, window=0):  # type: ignore[override]
+    def forward(ctx, qkv, n_kv, causal, p, scale, window=0, softcap=0.0):  # type: ignore[override]
         kern = kernels_for(qkv)
         H = qkv.shape[2] - 2 * n_kv
         q, k, v = qkv[:, :, :H], qkv[:, :, H:H + n_kv], qkv[:, :, H + n_kv:]
-        o, lse, seed, offset, bits = _attention_fwd(kern, q, k, v, causal, p, scale, 0, window)
+        o, lse, seed, offset, bits = _attention_fwd(kern, q, k, v, causal, p, scale, 0, window, softcap)
         ctx.save_for_backward(qkv, o, lse, bits)
         ctx.n_kv, ctx.causal, ctx.p, ctx.scale, ctx.seed, ctx.offset = n_kv, causal, p, scale, seed, offset
-        ctx.window = window
+        ctx.window, ctx.softcap = window, softcap
         return o
 
     @staticmethod
@@ -244,22 +274,28 @@ class _AttentionGqaPacked(torch.autograd.Function):
         dqkv = torch.empty_like(qkv)
         kern.attention_bwd(do, qkv[:, :, :H], qkv[:, :, H:H + n_kv], qkv[:, :, H + n_kv:], o, lse, ctx.causal, ctx.p,
                            ctx.scale, ctx.seed, ctx.offset, dqkv[:, :, :H], dqkv[:, :, H:H + n_kv],
-                           dqkv[:, :, H + n_kv:], bits if bits.numel() else None, 0, ctx.window)
-        return dqkv, None, None, None, None, None
+                           dqkv[:, :, H + n_kv:], bits if bits.numel() else None, 0, ctx.window, ctx.softcap)
+        return dqkv, None, None, None, None, None, None
 
 
 _noted = set()
 
 
-def _note_math_path(S: int, D: int, dtype, window: Optional[int] = None) -> None:
+def _note_math_path(S: int, D: int, dtype, window: Optional[int] = None, softcap: Optional[float] = None) -> None:
     """Shapes outside the kernels' tiling use the eager math path; say so once per shape."""
     key = (S, D, dtype) if window is None else (S, D, dtype, "window")
+    if softcap is not None:
+        key += ("softcap",)
     if key not in _noted:
         _noted.add(key)
         import warnings
 
         extra = "" if window is None else f" window={window}"
         tail = "" if window is None else ".  fp32 sliding-window attention is not native: the window runs on the bf16 kernels only"
+        if softcap is not None:
+            extra += f" softcap={softcap}"
+            tail += (".  Soft-capped attention is native in bf16 only, and not for a non-causal sequence of an "
+                     "unsupported length")
         warnings.warn(f"mipipe attention: S={S} D={D} {dtype}{extra} runs the eager math path (HIP kernels: bf16 "
                       "with S % 64 == 0, D in {64, 128, 256}; fp32 with S % 32 == 0, D in {64, 128})" + tail,
                       stacklevel=3)
@@ -321,33 +357,51 @@ def _run_shape(t: Tensor, S: int, D: int, causal: bool, scale: float) -> Optiona
     return None
 
 
-def _packed_window(qkv: Tensor, S: int, D: int, p: float, scale: float, window: int) -> Tensor:
-    """:func:`attention_packed` with a window ``< S`` (causal)."""
+def _generic_shape(t: Tensor, S: int, D: int, causal: bool, scale: float) -> Optional[Tuple[int, int]]:
+    """(sequence length, head dim) a windowed or soft-capped bf16 call runs at on the generic kernels, or None.
+    End padding of a causal sequence and feature padding only: a soft-capped non-causal sequence of an
+    unsupported length has no native form, because the spare-feature key mask of :func:`_run_shape` scores a
+    padded key at ``-32768 * scale`` and the cap would bring that back to ``-softcap``."""
+    if _gpu_ok(t, S, D):
+        return S, D
+    run = _run_shape(t, S, D, causal, scale)
+    if run is None or (not causal and run[0] != S):
+        return None
+    return run[0], run[1]
+
+
+def _packed_generic(qkv: Tensor, S: int, D: int, causal: bool, p: float, scale: float, window: Optional[int],
+                    softcap: Optional[float]) -> Tensor:
+    """:func:`attention_packed` with a window ``< S`` (causal) and / or a soft cap."""
     if _window_native(qkv):
-        if _gpu_ok(qkv, S, D):
-            return _AttentionPacked.apply(qkv.contiguous(), True, p, scale, 0, window)
-        run = _run_shape(qkv, S, D, True, scale)
-        if run is not None:  # causal bf16: end padding and feature padding only (no key bound)
-            sp, dp, _ = run
+        run = _generic_shape(qkv, S, D, causal, scale)
+        if run == (S, D):
+            return _AttentionPacked.apply(qkv.contiguous(), causal, p, scale, 0, window or 0, softcap or 0.0)
+        if run is not None:  # bf16: end padding (causal) and feature padding only (no key bound)
+            sp, dp = run
             padded = F.pad(qkv, (0, dp - D, 0, 0, 0, 0, 0, sp - S))
-            return _AttentionPacked.apply(padded, True, p, scale, 0, window)[:, :S, :, :D]
+            return _AttentionPacked.apply(padded, causal, p, scale, 0, window or 0, softcap or 0.0)[:, :S, :, :D]
     q, k, v = qkv.select(2, 0), qkv.select(2, 1), qkv.select(2, 2)
     if qkv.is_cuda:
-        _note_math_path(S, D, qkv.dtype, window)
-    o = attention_reference(q.transpose(1, 2), k.transpose(1, 2), v.transpose(1, 2), True, p, scale, window=window)
+        _note_math_path(S, D, qkv.dtype, window, softcap)
+    o = attention_reference(q.transpose(1, 2), k.transpose(1, 2), v.transpose(1, 2), causal, p, scale, window=window,
+                            softcap=softcap)
     return o.transpose(1, 2)
 
 
 def attention_packed(qkv: Tensor, causal: bool = False, dropout_p: float = 0.0, training: bool = True,
-                     scale: Optional[float] = None, *, window: Optional[int] = None) -> Tensor:
-    """``qkv [B, S, 3, H, D]`` -> ``o [B, S, H, D]``.  ``window``: sliding-window attention (module doc)."""
+                     scale: Optional[float] = None, *, window: Optional[int] = None,
+                     softcap: Optional[float] = None) -> Tensor:
+    """``qkv [B, S, 3, H, D]`` -> ``o [B, S, H, D]``.  ``window``: sliding-window attention, ``softcap``: logit
+    soft-capping (module doc)."""
     B, S, three, H, D = qkv.shape
     assert three == 3
     p = float(dropout_p) if training else 0.0
     scale = float(scale) if scale is not None else 1.0 / math.sqrt(D)
     window = _check_window(window, bool(causal), S)
-    if window is not None:
-        return _packed_window(qkv, S, D, p, scale, window)
+    softcap = _check_softcap(softcap)
+    if window is not None or softcap is not None:
+        return _packed_generic(qkv, S, D, bool(causal), p, scale, window, softcap)
     if qkv.is_cuda and _gpu_ok(qkv, S, D):
         return _AttentionPacked.apply(qkv.contiguous(), bool(causal), p, scale)
     run = _run_shape(qkv, S, D, bool(causal), scale) if qkv.is_cuda else None
@@ -384,9 +438,9 @@ def _expand_kv(qkv: Tensor, n_kv: int) -> Tensor:
 
 def attention_gqa_packed(qkv: Tensor, n_kv_heads: int, causal: bool = False, dropout_p: float = 0.0,
                          training: bool = True, scale: Optional[float] = None, *,
-                         window: Optional[int] = None) -> Tensor:
+                         window: Optional[int] = None, softcap: Optional[float] = None) -> Tensor:
     """``qkv [B, S, H + 2 Hkv, D]`` -> ``o [B, S, H, D]`` (grouped-query attention, ``Hkv = n_kv_heads``).
-    ``window``: sliding-window attention (module doc)."""
+    ``window``: sliding-window attention, ``softcap``: logit soft-capping (module doc)."""
     if qkv.dim() != 4:
         raise ValueError(f"attention_gqa_packed: qkv must be [B, S, H + 2 Hkv, D], got {tuple(qkv.shape)}")
     B, S, heads, D = qkv.shape
@@ -396,22 +450,27 @@ def attention_gqa_packed(qkv: Tensor, n_kv_heads: int, causal: bool = False, dro
         raise ValueError(f"attention_gqa_packed: {heads} packed heads do not split into H + 2 * {n_kv} with "
                          f"{n_kv} dividing H")
     window = _check_window(window, bool(causal), S)
+    softcap = _check_softcap(softcap)
     if n_kv == H:  # plain multi-head attention: the same bytes as [B, S, 3, H, D]
-        return attention_packed(qkv.reshape(B, S, 3, H, D), causal, dropout_p, training, scale, window=window)
+        return attention_packed(qkv.reshape(B, S, 3, H, D), causal, dropout_p, training, scale, window=window,
+                                softcap=softcap)
     if qkv.is_cuda and qkv.dtype == torch.bfloat16 and _gpu_ok(qkv, S, D):
         p = float(dropout_p) if training else 0.0
         scale = float(scale) if scale is not None else 1.0 / math.sqrt(D)
-        return _AttentionGqaPacked.apply(qkv.contiguous(), n_kv, bool(causal), p, scale, window or 0)
-    return attention_packed(_expand_kv(qkv, n_kv), causal, dropout_p, training, scale, window=window)
+        return _AttentionGqaPacked.apply(qkv.contiguous(), n_kv, bool(causal), p, scale, window or 0,
+                                         softcap or 0.0)
+    return attention_packed(_expand_kv(qkv, n_kv), causal, dropout_p, training, scale, window=window,
+                            softcap=softcap)
 
 
 def attention(
     q: Tensor, k: Tensor, v: Tensor, causal: bool = False, dropout_p: float = 0.0, training: bool = True,
-    scale: Optional[float] = None, *, window: Optional[int] = None,
+    scale: Optional[float] = None, *, window: Optional[int] = None, softcap: Optional[float] = None,
 ) -> Tensor:
     """``q, k, v [B, H, S, D]`` -> ``[B, H, S, D]``.  ``k`` and ``v`` may have fewer heads, ``Hkv | H``
     (grouped-query attention): separate tensors do not share q's strides, so their heads are repeated
-    (autograd sums each group's gradient).  ``window``: sliding-window attention (module doc)."""
+    (autograd sums each group's gradient).  ``window``: sliding-window attention, ``softcap``: logit
+    soft-capping (module doc)."""
     if k.shape[1] != q.shape[1]:
         if k.shape[1] != v.shape[1] or k.shape[1] <= 0 or q.shape[1] % k.shape[1] != 0:
             raise ValueError(f"attention: {k.shape[1]} / {v.shape[1]} K/V heads do not divide {q.shape[1]} query heads")
@@ -420,20 +479,23 @@ def attention(
     p = float(dropout_p) if training else 0.0
     scale = float(scale) if scale is not None else 1.0 / math.sqrt(q.shape[-1])
     window = _check_window(window, bool(causal), q.shape[2])
+    softcap = _check_softcap(softcap)
     if not q.is_cuda:
-        return attention_reference(q, k, v, causal, p, scale, window=window)
+        return attention_reference(q, k, v, causal, p, scale, window=window, softcap=softcap)
     S, D = q.shape[2], q.shape[3]
-    if window is not None:
-        run = (S, D, 0) if _gpu_ok(q, S, D) else _run_shape(q, S, D, True, scale)
-        if not _window_native(q) or run is None:
-            _note_math_path(S, D, q.dtype, window)
-            return attention_reference(q, k, v, True, p, scale, window=window)
-        sp, dp, _ = run  # causal bf16: end padding and feature padding only (no key bound)
+    if window is not None or softcap is not None:
+        causal = bool(causal)
+        run = _generic_shape(q, S, D, causal, scale) if _window_native(q) else None
+        if run is None:
+            _note_math_path(S, D, q.dtype, window, softcap)
+            return attention_reference(q, k, v, causal, p, scale, window=window, softcap=softcap)
+        sp, dp = run  # bf16: end padding (causal) and feature padding only (no key bound)
         pad = (lambda t: F.pad(t, (0, dp - D, 0, sp - S))) if (sp, dp) != (S, D) else (lambda t: t)  # noqa: E731
         qs, ks, vs = (pad(t).transpose(1, 2) for t in (q, k, v))
         if not (qs.stride() == ks.stride() == vs.stride()) or qs.stride(3) != 1:
             qs, ks, vs = (t.contiguous() for t in (qs, ks, vs))
-        return _Attention.apply(qs, ks, vs, True, p, scale, 0, window).transpose(1, 2)[:, :, :S, :D]
+        o = _Attention.apply(qs, ks, vs, causal, p, scale, 0, window or 0, softcap or 0.0)
+        return o.transpose(1, 2)[:, :, :S, :D]
     if not _gpu_ok(q, S, D):
         run = _run_shape(q, S, D, bool(causal), scale)
         if run is None:

@@ -50,8 +50,9 @@ __all__ = ["unit_kinds", "measure_unit_times", "unit_costs", "measure_engine_cos
 
 def unit_kinds(cfg: LMConfig, split_decoder: bool = False) -> List[str]:
     """Kind of every pipeline unit, in order (``mipipe.parallel.stage.unit_kind``)."""
-    from .stage import block_costs, unit_kind
+    from .stage import block_costs, split_allowed, unit_kind
 
+    split_decoder = split_decoder and split_allowed(cfg)  # a soft-capped decoder stays whole
     return [unit_kind(cfg, i, split_decoder) for i in range(len(block_costs(cfg, split_decoder)))]
 
 
@@ -114,14 +115,14 @@ def measure_unit_times(cfg: LMConfig, micro_batch: int, *, chunks: int = 4, devi
     from .. import ops
     from ..ops.linear import deferred_wgrad
     from ..optim import FlatAdam
-    from .stage import build_stage, stage_input_shape
+    from .stage import build_stage, split_allowed, stage_input_shape
 
     device = torch.device(device)
     start, stop = _timer(device)
     want = None if kinds is None else set(kinds)
     out: Dict[str, Tuple[float, float]] = {}
     S, V = cfg.seq_len, cfg.vocab
-    for split in (False, True):
+    for split in ((False, True) if split_allowed(cfg) else (False,)):
         plan = _single_unit_plan(cfg, split)
         kinds_here = unit_kinds(cfg, split)
         for idx, kind in enumerate(kinds_here):
@@ -283,7 +284,7 @@ def measure_engine_costs(cfg: LMConfig, micro_batch: int, chunks: int, checkpoin
     """``{kind: ms per micro-batch}`` in engine context (module docstring):
     checkpoint recompute, the deferred weight-gradient flush, the optimizer
     step and the host's issue overhead included as a pipeline rank pays them."""
-    from .stage import UNITS_PER_LAYER, block_costs
+    from .stage import UNITS_PER_LAYER, block_costs, split_allowed
 
     device = torch.device(device)
     if cfg.num_layers < 3:
@@ -309,6 +310,8 @@ def measure_engine_costs(cfg: LMConfig, micro_batch: int, chunks: int, checkpoin
         out["norm"], out["dec"] = end * share, end * (1 - share)
     else:
         out["dec"] = end
+    if not split_allowed(cfg):  # no dec_head / dec_tail units to plan with
+        return out
     ns = len(block_costs(cfg, True))
     tail = run(ns - 1, ns, True)
     head = max(run(ns - 2 - norm - L, ns - 1, True) - layer - out.get("norm", 0.0), 0.0)

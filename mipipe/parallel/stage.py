@@ -271,6 +271,12 @@ def _makespan_refined(costs: List[float], ranks: int, virtual: int, chunks: int,
     return bal
 
 
+def split_allowed(cfg: LMConfig) -> bool:
+    """Whether the decoder of ``cfg`` may be cut along the vocabulary: not under a final soft cap, which the
+    vocabulary-split kernels (they fuse the row statistics of the uncapped logits) do not apply."""
+    return cfg.final_softcap is None
+
+
 def plan_stages(cfg: LMConfig, stages: int, virtual: int = 1, chunks: int = 0, split_decoder: bool = False,
                 bwd_ratio: float = 2.0, costs: Optional[List[float]] = None,
                 objective: str = "makespan", seeds: Sequence[Sequence[int]] = ()) -> StagePlan:
@@ -291,7 +297,10 @@ def plan_stages(cfg: LMConfig, stages: int, virtual: int = 1, chunks: int = 0, s
     ``seeds``: further starting splits for the makespan refinement (e.g. the
     analytic-cost plan when planning with measured costs: coordinate descent
     from the cost-balanced starts can stall in a worse local optimum,
-    profiles/plan_table_r5.txt); invalid ones are ignored."""
+    profiles/plan_table_r5.txt); invalid ones are ignored.
+
+    ``split_decoder`` is dropped for a config whose decoder cannot be split (:func:`split_allowed`)."""
+    split_decoder = bool(split_decoder) and split_allowed(cfg)
     if costs is None:
         costs = block_costs(cfg, split_decoder)
     elif len(costs) != len(block_costs(cfg, split_decoder)):
@@ -470,8 +479,11 @@ def choose_virtual(cfg: LMConfig, stages: int, chunks: int, candidates: Optional
     for its extra boundaries.  ``cost_fn(split_decoder)``: per-unit costs in ms
     per micro-batch (measured, :mod:`mipipe.parallel.calibrate`) instead of
     the analytic FLOP model.  ``objective``: see :func:`plan_stages` (the
-    chunk count is chosen by simulated step time either way)."""
+    chunk count is chosen by simulated step time either way).  A config whose decoder cannot be
+    split (:func:`split_allowed`) is planned without the split whatever ``split_options`` says."""
     transfer, launch = boundary_terms(cfg, micro_batch, "ms" if cost_fn is not None else "flop")
+    if not split_allowed(cfg):  # the split is not on offer: every option plans the whole decoder
+        split_options = (False,)
 
     def sim(plan: StagePlan, v: int) -> float:
         return simulate_step([plan.stage_cost(g) for g in range(stages * v)], stages, v, chunks, bwd_ratio,
