@@ -254,6 +254,39 @@ std::tuple<Tensor, std::optional<Tensor>, Tensor, int64_t, int64_t> py_rmsnorm_f
   return {y, z, rstd, (int64_t)seed, (int64_t)offset};
 }
 
+// The sandwich norm y = res + RMSNorm(x) * gamma.  rstd (for rmsnorm_bwd on x) only with save.
+std::tuple<Tensor, std::optional<Tensor>> py_rmsnorm_residual_fwd(Tensor x, Tensor res, Tensor gamma, double eps,
+                                                                  bool save) {
+  check_cuda(x, "x");
+  check_cuda(res, "residual");
+  check_cuda(gamma, "gamma");
+  MP_CHECK(x.dim() >= 1, "rmsnorm_residual: x needs a hidden dimension");
+  const int64_t cols = x.size(-1);
+  MP_CHECK(cols > 0 && cols % 8 == 0, "rmsnorm_residual: hidden size must be a positive multiple of 8, got ", cols);
+  MP_CHECK(rms_max_vec((int)std::min<int64_t>(cols, 1 << 20)) > 0, "rmsnorm_residual: hidden size too large: ", cols);
+  const int64_t rows = x.numel() / cols;
+  MP_CHECK(rows <= INT32_MAX, "rmsnorm_residual: too many rows");
+  MP_CHECK(gamma.numel() == cols, "rmsnorm_residual: gamma size mismatch");
+  check_same(x, gamma, "x", "gamma");
+  check_same(x, res, "x", "residual");
+  MP_CHECK(res.sizes() == x.sizes(), "rmsnorm_residual: residual shape mismatch");
+  at::hip::HIPGuardMasqueradingAsCUDA guard(x.device());
+  auto y = at::empty_like(x);
+  std::optional<Tensor> rstd;
+  if (save) rstd = at::empty({rows}, x.options().dtype(at::kFloat));
+  if (rows == 0) return {y, rstd};
+  auto s = cur_stream(x);
+  dispatch_fb(x, "rmsnorm_residual_fwd", [&](auto* tag) {
+    using T = std::remove_pointer_t<decltype(tag)>;
+    RmsArgs<T> a;
+    a.x = cptr<T>(x); a.res = cptr<T>(res); a.gamma = cptr<T>(gamma);
+    a.y = ptr<T>(y); a.rstd = rstd ? ptr<float>(*rstd) : nullptr;
+    a.rows = (int)rows; a.cols = (int)cols; a.eps = (float)eps;
+    rmsnorm_residual_fwd<T>(a, s);
+  });
+  return {y, rstd};
+}
+
 // With acc_gamma (a fp32 main_grad view) dgamma is accumulated there and None is returned for it.
 std::tuple<Tensor, std::optional<Tensor>, std::optional<Tensor>> py_rmsnorm_bwd(
     Tensor dy, Tensor z, Tensor rstd, Tensor gamma, double p, int64_t seed, int64_t offset,
@@ -349,6 +382,46 @@ Tensor py_swiglu_bwd(Tensor dh, Tensor gu) {
   dispatch_fb(gu, "swiglu_bwd", [&](auto* tag) {
     using T = std::remove_pointer_t<decltype(tag)>;
     swiglu_bwd<T>(cptr<T>(dh), cptr<T>(gu), ptr<T>(dgu), rows, (int)F, s);
+  });
+  return dgu;
+}
+
+// GeGLU: the same checks, the tanh-GELU as the gate.
+Tensor py_geglu_fwd(Tensor gu) {
+  check_cuda(gu, "gu");
+  MP_CHECK(gu.dim() >= 1, "geglu: gu needs a feature dimension");
+  const int64_t two_f = gu.size(-1);
+  MP_CHECK(two_f > 0 && two_f % 16 == 0, "geglu: the last dim is 2F with F a multiple of 8, got ", two_f);
+  MP_CHECK(two_f / 2 <= INT32_MAX / 4, "geglu: F too large");
+  const int64_t F = two_f / 2, rows = gu.numel() / two_f;
+  at::hip::HIPGuardMasqueradingAsCUDA guard(gu.device());
+  auto shape = gu.sizes().vec();
+  shape.back() = F;
+  auto h = at::empty(shape, gu.options());
+  auto s = cur_stream(gu);
+  dispatch_fb(gu, "geglu_fwd", [&](auto* tag) {
+    using T = std::remove_pointer_t<decltype(tag)>;
+    geglu_fwd<T>(cptr<T>(gu), ptr<T>(h), rows, (int)F, s);
+  });
+  return h;
+}
+
+Tensor py_geglu_bwd(Tensor dh, Tensor gu) {
+  check_cuda(dh, "dh");
+  check_cuda(gu, "gu");
+  check_same(dh, gu, "dh", "gu");
+  MP_CHECK(gu.dim() >= 1 && dh.dim() >= 1, "geglu_bwd: tensors need a feature dimension");
+  const int64_t two_f = gu.size(-1);
+  MP_CHECK(two_f > 0 && two_f % 16 == 0, "geglu_bwd: the last dim of gu is 2F with F a multiple of 8, got ", two_f);
+  MP_CHECK(two_f / 2 <= INT32_MAX / 4, "geglu_bwd: F too large");
+  const int64_t F = two_f / 2, rows = gu.numel() / two_f;
+  MP_CHECK(dh.size(-1) == F && dh.numel() == rows * F, "geglu_bwd: dh must be [rows, F]");
+  at::hip::HIPGuardMasqueradingAsCUDA guard(gu.device());
+  auto dgu = at::empty_like(gu);
+  auto s = cur_stream(gu);
+  dispatch_fb(gu, "geglu_bwd", [&](auto* tag) {
+    using T = std::remove_pointer_t<decltype(tag)>;
+    geglu_bwd<T>(cptr<T>(dh), cptr<T>(gu), ptr<T>(dgu), rows, (int)F, s);
   });
   return dgu;
 }
@@ -1731,6 +1804,10 @@ PYBIND11_MODULE(_C, m) {
         py::arg("seed"), py::arg("offset"), py::arg("acc_gamma") = py::none(), py::arg("addend") = py::none());
   m.def("swiglu_fwd", &py_swiglu_fwd);
   m.def("swiglu_bwd", &py_swiglu_bwd);
+  m.def("geglu_fwd", &py_geglu_fwd);
+  m.def("geglu_bwd", &py_geglu_bwd);
+  m.def("rmsnorm_residual_fwd", &py_rmsnorm_residual_fwd, py::arg("x"), py::arg("res"), py::arg("gamma"),
+        py::arg("eps"), py::arg("save"));
   m.def("rope_packed", &py_rope_packed, py::arg("qkv"), py::arg("cos"), py::arg("sin"), py::arg("out") = py::none(),
         py::arg("pos0") = 0, py::arg("inverse") = false);
   m.def("rope_heads", &py_rope_heads, py::arg("x"), py::arg("cos"), py::arg("sin"), py::arg("out") = py::none(),

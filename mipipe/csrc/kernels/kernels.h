@@ -99,6 +99,9 @@ struct RmsBwdArgs {
 int rms_max_vec(int cols);
 int rms_bwd_parts(int rows, int cols);
 template <typename T> void rmsnorm_fwd(const RmsArgs<T>& a, hipStream_t s);
+// The sandwich norm: y = res + x * rsqrt(mean(x^2) + eps) * gamma (statistics from x alone; a.res required,
+// a.rstd may be null, a.p / a.z unused).  Its backward is rmsnorm_bwd on (dy, x, rstd) with p = 0.
+template <typename T> void rmsnorm_residual_fwd(const RmsArgs<T>& a, hipStream_t s);
 template <typename T> void rmsnorm_bwd(const RmsBwdArgs<T>& a, hipStream_t s);
 
 // ------------------------------------------------------------------ SwiGLU / RoPE (llama.hip)
@@ -108,6 +111,11 @@ void swiglu_fwd(const T* gu, T* h, int64_t rows, int F, hipStream_t s);
 // dgu [rows, 2F] = [dgate | dup] from dh [rows, F] and the forward's gu.
 template <typename T>
 void swiglu_bwd(const T* dh, const T* gu, T* dgu, int64_t rows, int F, hipStream_t s);
+// GeGLU, the same layout and contract: h = gelu_tanh(gate) * up (the tanh approximation of GELU).
+template <typename T>
+void geglu_fwd(const T* gu, T* h, int64_t rows, int F, hipStream_t s);
+template <typename T>
+void geglu_bwd(const T* dh, const T* gu, T* dgu, int64_t rows, int F, hipStream_t s);
 // Rotates Q and K of qkv [B, S, 3, H, D] (contiguous, D % 16 == 0) at positions pos0 + s, pairs
 // (i, i + D/2); cos / sin: fp32 [>= pos0 + S, D/2].  out == qkv rotates in place (V untouched),
 // otherwise V is copied.  inverse negates sin (the backward, on dqkv).

@@ -1,13 +1,17 @@
 // The LLaMA-style block's two element-wise kernels: the gated SiLU of the MLP
 // (SwiGLU) and rotary position embeddings on the packed QKV projection.
 //
-// Both are memory-bound: 16-byte vectors, grid-stride over 64-bit item
+// GeGLU (the Gemma-2 MLP's gate) is the same kernel body with the tanh-GELU in
+// place of SiLU.  All are memory-bound: 16-byte vectors, grid-stride over 64-bit item
 // indices, two items in flight per thread, fp32 arithmetic.
 //
 //   SwiGLU fwd:  h = silu(g) * u            gu [rows, 2F] = [g | u] per row
 //          bwd:  dg = dh u s (1 + g (1 - s)),  du = dh silu(g),  s = sigmoid(g)
 //                written as ONE dgu [rows, 2F] (it feeds W1's dgrad / wgrad
 //                GEMMs without a concatenation)
+//   GeGLU fwd:  h = gelu_tanh(g) * u = g s u,  s = 0.5 (1 + tanh(a)) = 1 / (1 + exp(-2a)),
+//               a = sqrt(2/pi) (g + 0.044715 g^3)   (no 1 + tanh: it cancels for g << 0)
+//          bwd:  dg = dh u (s + g s (1 - s) 2 sqrt(2/pi) (1 + 3 * 0.044715 g^2)),  du = dh g s
 //   RoPE:  (a, b) = (q_i, q_{i + D/2}) -> (a c - b s, b c + a s) on Q and K of
 //          qkv [B, S, 3, H, D] at position pos0 + s; cos / sin come from fp32
 //          host-built tables [>= pos0 + S, D/2] (no device trigonometry); V is
@@ -84,6 +88,75 @@ __global__ void __launch_bounds__(kThreads) swiglu_kernel(const T* __restrict__ 
           const float grad = g[j][i] == -INFINITY ? 0.f : s * (1.f + g[j][i] * (1.f - s));
           dg[i] = d[j][i] * u[j][i] * grad;
           du[i] = d[j][i] * silu;
+        }
+        T* dst = out + row[j] * 2 * F + c[j];
+        Io<T>::store8(dst, dg);
+        Io<T>::store8(dst + F, du);
+      }
+    }
+  }
+}
+
+// The tanh-GELU's s = 0.5 (1 + tanh(a)) in its cancellation-free form, gelu = g s
+// and gelu' of one gate value.  exp overflowing to inf gives s = 0, gelu = 0 and
+// gelu' = 0; where s (1 - s) is 0 the polynomial factor, which may be inf, is
+// not multiplied in.  A gate of -inf gives the limits 0 and 0 (g * s would be
+// -inf * 0), +inf gives gelu = inf, gelu' = 1.
+__device__ __forceinline__ void gelu_tanh_parts(float g, float& act, float& grad) {
+  constexpr float k0 = 0.7978845608028654f, k1 = 0.044715f;  // sqrt(2 / pi)
+  const float g2 = g * g;
+  const float a = k0 * g * (1.f + k1 * g2);
+  const float s = __builtin_amdgcn_rcpf(1.f + __expf(-2.f * a));
+  const float t = s * (1.f - s);
+  act = s == 0.f ? 0.f : g * s;
+  grad = t == 0.f ? s : s + g * t * (2.f * k0 * (1.f + 3.f * k1 * g2));
+}
+
+// swiglu_kernel with the tanh-GELU as the gate: a sibling, so that kernel stays as it is compiled.
+template <typename T, bool BWD>
+__global__ void __launch_bounds__(kThreads) geglu_kernel(const T* __restrict__ gu, const T* __restrict__ dh,
+                                                         T* __restrict__ out, int64_t rows, int F) {
+  const int fvec = F >> 3;
+  const int64_t nitems = rows * fvec;
+  const int64_t stride = (int64_t)gridDim.x * kThreads;
+  for (int64_t t0 = blockIdx.x * (int64_t)kThreads + threadIdx.x; t0 < nitems; t0 += 2 * stride) {
+    float g[2][8], u[2][8], d[2][8];
+    int64_t row[2];
+    int c[2];
+    bool on[2];
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      const int64_t t = t0 + j * stride;
+      on[j] = t < nitems;
+      if (on[j]) {
+        row[j] = t / fvec;
+        c[j] = (int)(t - row[j] * fvec) * 8;
+        const T* src = gu + row[j] * 2 * F + c[j];
+        Io<T>::load8(src, g[j]);
+        Io<T>::load8(src + F, u[j]);
+        if (BWD) Io<T>::load8(dh + row[j] * F + c[j], d[j]);
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      if (!on[j]) continue;
+      if (!BWD) {
+        float h[8];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+          float act, grad;
+          gelu_tanh_parts(g[j][i], act, grad);
+          h[i] = act * u[j][i];
+        }
+        Io<T>::store8(out + row[j] * F + c[j], h);
+      } else {
+        float dg[8], du[8];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+          float act, grad;
+          gelu_tanh_parts(g[j][i], act, grad);
+          dg[i] = d[j][i] * u[j][i] * grad;
+          du[i] = d[j][i] * act;
         }
         T* dst = out + row[j] * 2 * F + c[j];
         Io<T>::store8(dst, dg);
@@ -200,6 +273,22 @@ void swiglu_bwd(const T* dh, const T* gu, T* dgu, int64_t rows, int F, hipStream
 }
 
 template <typename T>
+void geglu_fwd(const T* gu, T* h, int64_t rows, int F, hipStream_t s) {
+  const int64_t nitems = rows * (F / 8);
+  if (nitems == 0) return;
+  hipLaunchKernelGGL((geglu_kernel<T, false>), dim3((unsigned)grid_for((nitems + 1) / 2)), dim3(kThreads), 0, s, gu,
+                     (const T*)nullptr, h, rows, F);
+}
+
+template <typename T>
+void geglu_bwd(const T* dh, const T* gu, T* dgu, int64_t rows, int F, hipStream_t s) {
+  const int64_t nitems = rows * (F / 8);
+  if (nitems == 0) return;
+  hipLaunchKernelGGL((geglu_kernel<T, true>), dim3((unsigned)grid_for((nitems + 1) / 2)), dim3(kThreads), 0, s, gu,
+                     dh, dgu, rows, F);
+}
+
+template <typename T>
 void rope_heads(const T* x, const float* cos_t, const float* sin_t, T* out, int64_t B, int S, int n_rot, int n_copy,
                 int D, int pos0, bool inverse, hipStream_t s) {
   const bool copy_v = out != x;
@@ -227,6 +316,10 @@ template void swiglu_fwd<float>(const float*, float*, int64_t, int, hipStream_t)
 template void swiglu_fwd<bf16_t>(const bf16_t*, bf16_t*, int64_t, int, hipStream_t);
 template void swiglu_bwd<float>(const float*, const float*, float*, int64_t, int, hipStream_t);
 template void swiglu_bwd<bf16_t>(const bf16_t*, const bf16_t*, bf16_t*, int64_t, int, hipStream_t);
+template void geglu_fwd<float>(const float*, float*, int64_t, int, hipStream_t);
+template void geglu_fwd<bf16_t>(const bf16_t*, bf16_t*, int64_t, int, hipStream_t);
+template void geglu_bwd<float>(const float*, const float*, float*, int64_t, int, hipStream_t);
+template void geglu_bwd<bf16_t>(const bf16_t*, const bf16_t*, bf16_t*, int64_t, int, hipStream_t);
 template void rope_packed<float>(const float*, const float*, const float*, float*, int64_t, int, int, int, int, bool, hipStream_t);
 template void rope_packed<bf16_t>(const bf16_t*, const float*, const float*, bf16_t*, int64_t, int, int, int, int, bool, hipStream_t);
 template void rope_heads<float>(const float*, const float*, const float*, float*, int64_t, int, int, int, int, int, bool, hipStream_t);

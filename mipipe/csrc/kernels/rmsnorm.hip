@@ -12,6 +12,11 @@
 // vectors per thread.  The dropout mask is never stored: backward regenerates
 // it from the same Philox (seed, offset).
 //
+// The sandwich norm of the Gemma-2 block (rmsnorm_residual_fwd) is a variant of
+// the same forward kernels: y = residual + x * rsqrt(mean(x^2) + eps) * gamma,
+// the statistics from x alone.  Its backward is the one below on (dy, x, rstd)
+// with p = 0; the residual's gradient is dy itself.
+//
 //   xhat = z rstd, gy = dy gamma, b = mean(gy xhat)
 //   dz = rstd (gy - xhat b) [+ addend],  dx = dz mask / (1 - p),  dgamma = sum_rows dy xhat
 //
@@ -35,69 +40,6 @@ __device__ __forceinline__ float block_sum_once(float a, float* scratch) {
   return scratch[0] + scratch[1] + scratch[2] + scratch[3];
 }
 
-template <typename T, int MAXV>
-__global__ void __launch_bounds__(kThreads) rms_fwd_kernel(
-    const T* __restrict__ x, const T* __restrict__ res, const T* __restrict__ gamma, T* __restrict__ y,
-    T* __restrict__ z, float* __restrict__ rstd_out, int cols, float eps, float p, uint32_t threshold, uint64_t seed,
-    uint64_t offset) {
-  static_assert(kThreads == 256, "block_sum_once folds 4 waves");
-  __shared__ float scratch[kThreads / 64];
-  const int row = blockIdx.x;
-  const size_t base = (size_t)row * cols;
-  const int nvec = cols >> 3;
-  const float scale = p > 0.f ? 1.f / (1.f - p) : 1.f;
-  float v[MAXV][8];
-  float s2 = 0.f;
-#pragma unroll
-  for (int k = 0; k < MAXV; ++k) {
-    const int vi = threadIdx.x + k * kThreads;
-    if (vi < nvec) {
-      const size_t e = base + (size_t)vi * 8;
-      Io<T>::load8(x + e, v[k]);
-      if (p > 0.f) {
-        const uint32_t keep = dropout_keep8(seed, offset, e, threshold);
-#pragma unroll
-        for (int i = 0; i < 8; ++i) v[k][i] = ((keep >> i) & 1) ? v[k][i] * scale : 0.f;
-      }
-      if (res != nullptr) {
-        float r[8];
-        Io<T>::load8(res + e, r);
-#pragma unroll
-        for (int i = 0; i < 8; ++i) v[k][i] += r[i];
-      }
-#pragma unroll
-      for (int i = 0; i < 8; ++i) s2 += v[k][i] * v[k][i];
-    }
-  }
-  const float rstd = rsqrtf(block_sum_once(s2, scratch) / (float)cols + eps);
-  if (threadIdx.x == 0) rstd_out[row] = rstd;
-#pragma unroll
-  for (int k = 0; k < MAXV; ++k) {
-    const int vi = threadIdx.x + k * kThreads;
-    if (vi < nvec) {
-      const size_t e = base + (size_t)vi * 8;
-      if (z != nullptr) Io<T>::store8(z + e, v[k]);
-      float g[8], o[8];
-      Io<T>::load8(gamma + vi * 8, g);
-#pragma unroll
-      for (int i = 0; i < 8; ++i) o[i] = v[k][i] * rstd * g[i];
-      Io<T>::store8(y + e, o);
-    }
-  }
-}
-
-// Row reduction over one 256-thread row group of a G-group block (every thread
-// of the block calls it: the barrier is block-wide).  Callers alternate two
-// scratch buffers by row parity, so one barrier per row is enough: a buffer is
-// written again two rows later, behind the next row's barrier, which a thread
-// reaches only after reading this row's sum.
-__device__ __forceinline__ float group_sum(float a, float (*scratch)[4], int grp, int t) {
-  a = wave_sum(a);
-  if ((t & 63) == 0) scratch[grp][t >> 6] = a;
-  __syncthreads();
-  return scratch[grp][0] + scratch[grp][1] + scratch[grp][2] + scratch[grp][3];
-}
-
 // 8 elements kept as loaded (bf16: 4 registers instead of 8), converted on use.
 template <typename T> struct Raw8;
 template <> struct Raw8<float> {
@@ -118,6 +60,78 @@ template <> struct Raw8<bf16_t> {
   __device__ __forceinline__ void load(const bf16_t* p) { v = *reinterpret_cast<const u16x8*>(p); }
   __device__ __forceinline__ float get(int i) const { return bf2f(v[i]); }
 };
+
+// POST (the sandwich norm, y = res + x rstd gamma): the statistics come from x
+// alone and the residual, loaded with x and kept as loaded, is added after the
+// scale; no dropout, no z, and rstd only where the caller wants it.
+template <typename T, int MAXV, bool POST>
+__global__ void __launch_bounds__(kThreads) rms_fwd_kernel(
+    const T* __restrict__ x, const T* __restrict__ res, const T* __restrict__ gamma, T* __restrict__ y,
+    T* __restrict__ z, float* __restrict__ rstd_out, int cols, float eps, float p, uint32_t threshold, uint64_t seed,
+    uint64_t offset) {
+  static_assert(kThreads == 256, "block_sum_once folds 4 waves");
+  __shared__ float scratch[kThreads / 64];
+  const int row = blockIdx.x;
+  const size_t base = (size_t)row * cols;
+  const int nvec = cols >> 3;
+  const float scale = p > 0.f ? 1.f / (1.f - p) : 1.f;
+  float v[MAXV][8];
+  float s2 = 0.f;
+  Raw8<T> rr[POST ? MAXV : 1];
+#pragma unroll
+  for (int k = 0; k < MAXV; ++k) {
+    const int vi = threadIdx.x + k * kThreads;
+    if (vi < nvec) {
+      const size_t e = base + (size_t)vi * 8;
+      Io<T>::load8(x + e, v[k]);
+      if constexpr (POST) rr[k].load(res + e);
+      if (!POST && p > 0.f) {
+        const uint32_t keep = dropout_keep8(seed, offset, e, threshold);
+#pragma unroll
+        for (int i = 0; i < 8; ++i) v[k][i] = ((keep >> i) & 1) ? v[k][i] * scale : 0.f;
+      }
+      if (!POST && res != nullptr) {
+        float r[8];
+        Io<T>::load8(res + e, r);
+#pragma unroll
+        for (int i = 0; i < 8; ++i) v[k][i] += r[i];
+      }
+#pragma unroll
+      for (int i = 0; i < 8; ++i) s2 += v[k][i] * v[k][i];
+    }
+  }
+  const float rstd = rsqrtf(block_sum_once(s2, scratch) / (float)cols + eps);
+  if (threadIdx.x == 0 && (!POST || rstd_out != nullptr)) rstd_out[row] = rstd;
+#pragma unroll
+  for (int k = 0; k < MAXV; ++k) {
+    const int vi = threadIdx.x + k * kThreads;
+    if (vi < nvec) {
+      const size_t e = base + (size_t)vi * 8;
+      if (!POST && z != nullptr) Io<T>::store8(z + e, v[k]);
+      float g[8], o[8];
+      Io<T>::load8(gamma + vi * 8, g);
+#pragma unroll
+      for (int i = 0; i < 8; ++i) o[i] = v[k][i] * rstd * g[i];
+      if constexpr (POST) {
+#pragma unroll
+        for (int i = 0; i < 8; ++i) o[i] += rr[k].get(i);
+      }
+      Io<T>::store8(y + e, o);
+    }
+  }
+}
+
+// Row reduction over one 256-thread row group of a G-group block (every thread
+// of the block calls it: the barrier is block-wide).  Callers alternate two
+// scratch buffers by row parity, so one barrier per row is enough: a buffer is
+// written again two rows later, behind the next row's barrier, which a thread
+// reaches only after reading this row's sum.
+__device__ __forceinline__ float group_sum(float a, float (*scratch)[4], int grp, int t) {
+  a = wave_sum(a);
+  if ((t & 63) == 0) scratch[grp][t >> 6] = a;
+  __syncthreads();
+  return scratch[grp][0] + scratch[grp][1] + scratch[grp][2] + scratch[grp][3];
+}
 
 // G row groups of 256 threads per block, each on its own row, the block's rows
 // strided over the grid; the groups' dgamma partials are folded through LDS so
@@ -261,7 +275,7 @@ __global__ void __launch_bounds__(kThreads * G) rms_bwd_kernel(
 constexpr int kRowWaves = 8;
 constexpr int kRowNV = 4;
 
-template <typename T>
+template <typename T, bool POST>
 __global__ void __launch_bounds__(64 * kRowWaves) rms_fwd_rows_kernel(
     const T* __restrict__ x, const T* __restrict__ res, const T* __restrict__ gamma, T* __restrict__ y,
     T* __restrict__ z, float* __restrict__ rstd_out, int rows, int cols, float eps, float p, uint32_t threshold,
@@ -274,6 +288,7 @@ __global__ void __launch_bounds__(64 * kRowWaves) rms_fwd_rows_kernel(
   const float scale = p > 0.f ? 1.f / (1.f - p) : 1.f;
   float v[kRowNV][8];
   float s2 = 0.f;
+  Raw8<T> rr[POST ? kRowNV : 1];
 #pragma unroll
   for (int k = 0; k < kRowNV; ++k) {
     const int vi = lane + 64 * k;
@@ -282,12 +297,13 @@ __global__ void __launch_bounds__(64 * kRowWaves) rms_fwd_rows_kernel(
     if (vi < nvec) {
       const size_t e = base + (size_t)vi * 8;
       Io<T>::load8(x + e, v[k]);
-      if (p > 0.f) {
+      if constexpr (POST) rr[k].load(res + e);
+      if (!POST && p > 0.f) {
         const uint32_t keep = dropout_keep8(seed, offset, e, threshold);
 #pragma unroll
         for (int i = 0; i < 8; ++i) v[k][i] = ((keep >> i) & 1) ? v[k][i] * scale : 0.f;
       }
-      if (res != nullptr) {
+      if (!POST && res != nullptr) {
         float r[8];
         Io<T>::load8(res + e, r);
 #pragma unroll
@@ -298,17 +314,21 @@ __global__ void __launch_bounds__(64 * kRowWaves) rms_fwd_rows_kernel(
     }
   }
   const float rstd = rsqrtf(wave_sum(s2) / (float)cols + eps);
-  if (lane == 0) rstd_out[row] = rstd;
+  if (lane == 0 && (!POST || rstd_out != nullptr)) rstd_out[row] = rstd;
 #pragma unroll
   for (int k = 0; k < kRowNV; ++k) {
     const int vi = lane + 64 * k;
     if (vi < nvec) {
       const size_t e = base + (size_t)vi * 8;
-      if (z != nullptr) Io<T>::store8(z + e, v[k]);
+      if (!POST && z != nullptr) Io<T>::store8(z + e, v[k]);
       float g[8], o[8];
       Io<T>::load8(gamma + vi * 8, g);
 #pragma unroll
       for (int i = 0; i < 8; ++i) o[i] = v[k][i] * rstd * g[i];
+      if constexpr (POST) {
+#pragma unroll
+        for (int i = 0; i < 8; ++i) o[i] += rr[k].get(i);
+      }
       Io<T>::store8(y + e, o);
     }
   }
@@ -408,9 +428,9 @@ __global__ void __launch_bounds__(64 * kRowWaves) rms_bwd_rows_kernel(
 
 bool rms_rows_variant(int cols) { return cols <= 64 * kRowNV * 8; }
 
-template <typename T, int MAXV>
+template <typename T, int MAXV, bool POST>
 void launch_fwd(const RmsArgs<T>& a, hipStream_t s) {
-  hipLaunchKernelGGL((rms_fwd_kernel<T, MAXV>), dim3(a.rows), dim3(kThreads), 0, s, a.x, a.res, a.gamma, a.y, a.z,
+  hipLaunchKernelGGL((rms_fwd_kernel<T, MAXV, POST>), dim3(a.rows), dim3(kThreads), 0, s, a.x, a.res, a.gamma, a.y, a.z,
                      a.rstd, a.cols, a.eps, a.p, dropout_threshold(a.p), a.seed, a.offset);
 }
 
@@ -441,21 +461,32 @@ int rms_bwd_parts(int rows, int cols) {
   return rows < cap ? (rows < 1 ? 1 : rows) : cap;
 }
 
-template <typename T>
-void rmsnorm_fwd(const RmsArgs<T>& a, hipStream_t s) {
+template <typename T, bool POST>
+void rmsnorm_fwd_impl(const RmsArgs<T>& a, hipStream_t s) {
   if (a.rows <= 0) return;
   if (rms_rows_variant(a.cols)) {
-    hipLaunchKernelGGL((rms_fwd_rows_kernel<T>), dim3((a.rows + kRowWaves - 1) / kRowWaves), dim3(64 * kRowWaves), 0,
+    hipLaunchKernelGGL((rms_fwd_rows_kernel<T, POST>), dim3((a.rows + kRowWaves - 1) / kRowWaves), dim3(64 * kRowWaves), 0,
                        s, a.x, a.res, a.gamma, a.y, a.z, a.rstd, a.rows, a.cols, a.eps, a.p, dropout_threshold(a.p),
                        a.seed, a.offset);
     return;
   }
   switch (rms_max_vec(a.cols)) {
-    case 2: launch_fwd<T, 2>(a, s); break;
-    case 4: launch_fwd<T, 4>(a, s); break;
-    case 8: launch_fwd<T, 8>(a, s); break;
+    case 2: launch_fwd<T, 2, POST>(a, s); break;
+    case 4: launch_fwd<T, 4, POST>(a, s); break;
+    case 8: launch_fwd<T, 8, POST>(a, s); break;
     default: break;
   }
+}
+
+template <typename T>
+void rmsnorm_fwd(const RmsArgs<T>& a, hipStream_t s) {
+  rmsnorm_fwd_impl<T, false>(a, s);
+}
+
+// y = res + x rstd gamma: a.res is required, a.rstd may be null, a.p and a.z are not used.
+template <typename T>
+void rmsnorm_residual_fwd(const RmsArgs<T>& a, hipStream_t s) {
+  rmsnorm_fwd_impl<T, true>(a, s);
 }
 
 template <typename T>
@@ -478,6 +509,8 @@ void rmsnorm_bwd(const RmsBwdArgs<T>& a, hipStream_t s) {
 
 template void rmsnorm_fwd<float>(const RmsArgs<float>&, hipStream_t);
 template void rmsnorm_fwd<bf16_t>(const RmsArgs<bf16_t>&, hipStream_t);
+template void rmsnorm_residual_fwd<float>(const RmsArgs<float>&, hipStream_t);
+template void rmsnorm_residual_fwd<bf16_t>(const RmsArgs<bf16_t>&, hipStream_t);
 template void rmsnorm_bwd<float>(const RmsBwdArgs<float>&, hipStream_t);
 template void rmsnorm_bwd<bf16_t>(const RmsBwdArgs<bf16_t>&, hipStream_t);
 

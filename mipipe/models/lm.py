@@ -22,7 +22,7 @@ from torch import Tensor, nn
 from .. import ops
 from ..ops.linear import mark_gemm_weight
 from ..ops.softcap import softcap_owned
-from .transformer import FeedForwardBlock, transformer_blocks
+from .transformer import GATED_ACTS, FeedForwardBlock, check_global_every, layer_window, transformer_blocks
 
 __all__ = [
     "Encoder",
@@ -228,12 +228,31 @@ class LMConfig:
     window: Optional[int] = None      # sliding-window attention: keys a query sees, its own included (causal only)
     attn_softcap: Optional[float] = None   # attention scores capped at c * tanh(s / c) before the softmax (Gemma-2)
     final_softcap: Optional[float] = None  # output logits capped the same way before the loss (Gemma-2)
+    # Gemma-2 block options (activation="geglu" is the fourth)
+    sandwich_norm: bool = False       # x + RMSNorm(branch) * w: a second norm on each branch, before the residual add
+    head_dim: Optional[int] = None    # head width; None = d_model // nhead
+    attn_scale: Optional[float] = None  # score scale; None = head_dim ** -0.5 (Gemma-2: query_pre_attn_scalar ** -0.5)
+    global_every: Optional[int] = None  # layer i is global (no window) when (i + 1) % n == 0; needs window
     qk_norm: bool = False             # per-head RMSNorm on Q and K before the rotation (Qwen3): two [head_dim] weights
+
+    def __post_init__(self) -> None:
+        check_global_every(self.global_every, self.window)
+
+    def head_width(self) -> int:
+        return self.d_model // self.nhead if self.head_dim is None else self.head_dim
+
+    def attn_dim(self) -> int:
+        """Width of the attention output before ``out_proj``: ``H D`` (``d_model`` unless ``head_dim`` is set)."""
+        return self.nhead * self.head_width()
 
     def qkv_dim(self) -> int:
         """Width of the QKV projection: ``(H + 2 Hkv) D`` (``3 d_model`` without grouped-query attention)."""
         hkv = self.nhead if self.n_kv_heads is None else self.n_kv_heads
-        return (self.nhead + 2 * hkv) * (self.d_model // self.nhead)
+        return (self.nhead + 2 * hkv) * self.head_width()
+
+    def layer_window(self, i: int) -> Optional[int]:
+        """The window of layer ``i`` (0-based): ``None`` for a global layer under ``global_every``."""
+        return layer_window(self.window, self.global_every, i)
 
     def encoder_positions(self) -> str:
         return self.positions if self.positions is not None else ("learned" if self.learned_positions else "sinusoidal")
@@ -242,13 +261,15 @@ class LMConfig:
         """Parameter count of the model :func:`build_lm_blocks` builds, without the zero rows that
         pad the decoder's vocabulary to a multiple of 256 (an implementation detail of its GEMM)."""
         e, f, v = self.d_model, self.dim_feedforward, self.vocab
-        f1 = 2 * f if self.activation == "swiglu" else f   # the gated first GEMM
+        f1 = 2 * f if self.activation in GATED_ACTS else f   # the gated first GEMM
         nb = 1 if self.bias else 0
         norm = e * (2 if self.norm == "layer" else 1)
         qkv = self.qkv_dim()
-        layer = (qkv + e) * e + 2 * norm + f1 * e + e * f + nb * (qkv + e + f1 + e)
+        layer = (qkv + self.attn_dim()) * e + 2 * norm + f1 * e + e * f + nb * (qkv + e + f1 + e)
         if self.qk_norm:
-            layer += 2 * (e // self.nhead)
+            layer += 2 * self.head_width()
+        if self.sandwich_norm:
+            layer += 2 * e   # the two post-norm weights
         total = self.num_layers * layer + v * e
         if self.encoder_positions() == "learned":
             total += max(self.seq_len, 1024) * e
@@ -256,6 +277,15 @@ class LMConfig:
             total += norm
         return total + (v * e + v)
 
+
+# What every Gemma-2 config shares: pre-norm RMSNorm with a second norm on each branch, GeGLU, rotary positions
+# (base 10000), no biases, no dropout, every second layer global, soft caps 50 / 30, the embedding scaled by sqrt(E).
+_GEMMA2 = dict(dropout=0.0, activation="geglu", norm_first=True, causal=True, scale_embedding=True, act_dropout=0.0,
+               norm="rms", bias=False, rope=True, rope_base=10000.0, positions="none", global_every=2,
+               sandwich_norm=True, attn_softcap=50.0, final_softcap=30.0)
+_GEMMA2_NOTE = ("Not Gemma-2's: the decoder is untied and keeps its (zero-initialised) bias, the norms' eps is 1e-5 "
+                "rather than 1e-6 (the block's layer_norm_eps is not a config field), and the norm weights are "
+                "plain w rather than 1 + w")
 
 CONFIGS = {
     # BASELINE.json config #2/#3: 12-layer TransformerEncoder d_model=4096 nhead=16.
@@ -303,16 +333,15 @@ CONFIGS = {
                            norm_first=True, causal=True, scale_embedding=False, act_dropout=0.0, norm="rms",
                            bias=False, rope=True, rope_base=10000.0, positions="none", n_kv_heads=8, window=4096,
                            notes="Mistral 7B's block; the decoder is untied and keeps its (zero-initialised) bias"),
-    # mistral_tiny with Gemma-2's two soft caps (50 on the attention scores, 30 on the output logits).  No
-    # full-size Gemma-2 config: every Gemma-2 size has a head dim decoupled from d_model / nhead, a GeGLU MLP,
-    # post-norms and alternating local / global layers, none of which these blocks have.
+    # mistral_tiny with Gemma-2's two soft caps (50 on the attention scores, 30 on the output logits); the rest of
+    # the Gemma-2 block is in gemma2_block_tiny below.
     "gemma2_tiny": LMConfig("gemma2_tiny", 2, 256, 4, 512, 1000, 192, dropout=0.0, activation="swiglu",
                             norm_first=True, causal=True, scale_embedding=False, act_dropout=0.0, norm="rms",
                             bias=False, rope=True, positions="none", n_kv_heads=2, window=48, attn_softcap=50.0,
                             final_softcap=30.0,
                             notes="mistral_tiny plus Gemma-2's soft caps: attention scores at 50, output logits at "
-                                  "30 (not a Gemma-2 size: those decouple the head dim from d_model / nhead and use "
-                                  "GeGLU, post-norms and alternating local / global layers)"),
+                                  "30 (the Gemma-2 block itself -- head dim of its own, GeGLU, sandwich norms, local / "
+                                  "global layers -- is gemma2_block_tiny)"),
     # llama_gqa_tiny with QK-norm: every Q and K head RMS-normalised before the rotation.
     "qwen3_tiny": LMConfig("qwen3_tiny", 2, 256, 4, 512, 1000, 64, dropout=0.0, activation="swiglu",
                            norm_first=True, causal=True, scale_embedding=False, act_dropout=0.0, norm="rms",
@@ -323,6 +352,20 @@ CONFIGS = {
                          norm_first=True, causal=True, scale_embedding=False, act_dropout=0.0, norm="rms",
                          bias=False, rope=True, rope_base=1000000.0, positions="none", n_kv_heads=8, qk_norm=True,
                          notes="Qwen3 8B's block; the decoder is untied and keeps its (zero-initialised) bias"),
+    # The Gemma-2 block at test size: heads of 128 on d_model 256 (A = 512 != E), GeGLU, sandwich norms, layers 0 and
+    # 2 local (48 keys) and 1 and 3 global, both soft caps, the embedding scaled by sqrt(E).  attn_scale is
+    # (d_model / nhead) ** -0.5 as in the 27B model, not 128 ** -0.5, so a dropped argument shows.
+    "gemma2_block_tiny": LMConfig("gemma2_block_tiny", 4, 256, 4, 512, 1000, 192, **_GEMMA2, n_kv_heads=2,
+                                  head_dim=128, window=48, attn_scale=0.125,
+                                  notes="tiny Gemma-2 block for tests.  " + _GEMMA2_NOTE),
+    # Gemma-2 2B / 9B / 27B: 256,000 tokens, 8192 positions, every second layer global, the others a 4096-key window.
+    "gemma2_2b": LMConfig("gemma2_2b", 26, 2304, 8, 9216, 256000, 8192, **_GEMMA2, n_kv_heads=4, head_dim=256,
+                          window=4096, notes="Gemma-2 2B's block.  " + _GEMMA2_NOTE),
+    "gemma2_9b": LMConfig("gemma2_9b", 42, 3584, 16, 14336, 256000, 8192, **_GEMMA2, n_kv_heads=8, head_dim=256,
+                          window=4096, notes="Gemma-2 9B's block.  " + _GEMMA2_NOTE),
+    # 27B: query_pre_attn_scalar is d_model / nhead = 144, not the head dim 128
+    "gemma2_27b": LMConfig("gemma2_27b", 46, 4608, 32, 36864, 256000, 8192, **_GEMMA2, n_kv_heads=16, head_dim=128,
+                           window=4096, attn_scale=144 ** -0.5, notes="Gemma-2 27B's block.  " + _GEMMA2_NOTE),
 }
 
 
@@ -337,7 +380,8 @@ def build_lm_blocks(cfg: LMConfig, *, device=None, dtype=None) -> List[nn.Module
                                  cfg.activation, norm_first=cfg.norm_first, causal=cfg.causal, norm=cfg.norm,
                                  bias=cfg.bias, rope=cfg.rope, rope_base=cfg.rope_base, n_kv_heads=cfg.n_kv_heads,
                                  window=cfg.window, qk_norm=cfg.qk_norm, attn_softcap=cfg.attn_softcap,
-                                 device=device, dtype=dtype)
+                                 sandwich_norm=cfg.sandwich_norm, head_dim=cfg.head_dim, attn_scale=cfg.attn_scale,
+                                 global_every=cfg.global_every, device=device, dtype=dtype)
     if cfg.act_dropout is not None:
         for b in blocks:
             if isinstance(b, FeedForwardBlock):

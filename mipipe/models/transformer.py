@@ -38,6 +38,22 @@ tanh(s / c)`` before the softmax (Gemma-2's ``attn_logit_softcapping``).
 ``q_norm_weight`` and ``k_norm_weight`` of the attention core and the block's
 ``layer_norm_eps`` (``ops.qk_norm_rope_projection``: one kernel with the
 rotation, or the norm alone with ``rope=False``).
+
+Four more options make the halves a Gemma-2 block.  ``activation="geglu"`` is
+``"swiglu"`` with the tanh-GELU as the gate (``ops.geglu``; the same ``[2F, E]``
+weight, gate rows first).  ``sandwich_norm=True`` (pre-norm RMSNorm blocks
+without residual dropout only) normalises each branch again before the residual
+add: the output halves compute ``x + RMSNorm(W o + b) * post_norm_weight``
+(``ops.rms_norm_residual``) with a ``[E]`` weight of their own, so their GEMM
+runs as a plain ``ops.linear`` instead of with the add in its epilogue.
+``head_dim=D`` (``None`` means ``d_model // nhead``) gives the heads a width of
+their own: with ``A = nhead * D`` the QKV projection is ``[(H + 2 Hkv) D, E]``,
+the core returns ``o [B, S, A]`` and ``out_proj_weight`` is ``[E, A]``; a packed
+core whose ``A != E`` hands ``x`` and ``o`` on block-concatenated as ``[.., E +
+A]``.  ``attn_scale`` (``None`` means ``1 / sqrt(D)``) is the score scale
+(Gemma-2's ``query_pre_attn_scalar ** -0.5``).  ``transformer_blocks`` also takes
+``global_every=n``: layer ``i`` with ``(i + 1) % n == 0`` is a global layer, built
+without the window.
 """
 from __future__ import annotations
 
@@ -80,6 +96,14 @@ def _folds(fc_in, training: bool) -> bool:
 
 
 NORMS = ("layer", "rms")
+GATED_ACTS = ("swiglu", "geglu")  # linear1 is [2F, E], gate rows first; the gate is a kernel of its own
+
+
+def _check_sandwich(sandwich_norm: bool, norm_first: bool, norm: str, dropout: float) -> bool:
+    if sandwich_norm and not (norm_first and norm == "rms" and dropout == 0.0):
+        raise ValueError("sandwich_norm needs norm_first=True, norm='rms' and a residual dropout of 0, got "
+                         f"norm_first={norm_first}, norm={norm!r}, dropout={dropout}")
+    return bool(sandwich_norm)
 
 
 def _init_norm(mod: nn.Module, d_model: int, norm: str, fk: dict) -> None:
@@ -123,6 +147,7 @@ __all__ = [
     "PackedFeedForwardOut",
     "TransformerEncoderLayer",
     "transformer_blocks",
+    "layer_window",
     "block_flops",
 ]
 
@@ -130,16 +155,29 @@ __all__ = [
 class AttentionCore(nn.Module):
     """QKV projection + scaled-dot-product attention (pre-norm: LN first).
 
-    ``x [B, S, E] -> o [B, S, E]`` (attention output before ``out_proj``).
+    ``x [B, S, E] -> o [B, S, A]`` (attention output before ``out_proj``), ``A = nhead * head_dim``
+    (``E`` unless ``head_dim`` is given).
     """
 
     def __init__(self, d_model: int, nhead: int, dropout: float, *, norm_first: bool, causal: bool,
                  layer_norm_eps: float, norm: str = "layer", bias: bool = True, rope: bool = False,
                  rope_base: float = 10000.0, n_kv_heads: Optional[int] = None, window: Optional[int] = None,
-                 qk_norm: bool = False, attn_softcap: Optional[float] = None, device=None, dtype=None) -> None:
+                 qk_norm: bool = False, attn_softcap: Optional[float] = None, head_dim: Optional[int] = None,
+                 attn_scale: Optional[float] = None, device=None, dtype=None) -> None:
         super().__init__()
         fk = {"device": device, "dtype": dtype}
-        self.d_model, self.nhead, self.head_dim = d_model, nhead, d_model // nhead
+        if head_dim is None:
+            head_dim = d_model // nhead
+        elif isinstance(head_dim, bool) or not isinstance(head_dim, int) or head_dim < 1:
+            raise ValueError(f"head_dim must be an int >= 1 or None, got {head_dim!r}")
+        self.d_model, self.nhead, self.head_dim = d_model, nhead, head_dim
+        self.attn_dim = nhead * head_dim  # width of o: d_model unless head_dim is given
+        if attn_scale is not None:
+            if (isinstance(attn_scale, bool) or not isinstance(attn_scale, (int, float))
+                    or not math.isfinite(attn_scale) or attn_scale <= 0):
+                raise ValueError(f"attn_scale must be a finite number > 0 or None, got {attn_scale!r}")
+            attn_scale = float(attn_scale)
+        self.attn_scale = attn_scale  # None: the ops' own 1 / sqrt(head_dim)
         if attn_softcap is not None:
             if (isinstance(attn_softcap, bool) or not isinstance(attn_softcap, (int, float))
                     or not math.isfinite(attn_softcap) or attn_softcap <= 0):
@@ -205,8 +243,8 @@ class AttentionCore(nn.Module):
         ``fanout`` the first consumer of ``x`` (LN1 for pre-norm, the QKV
         projection for post-norm) also returns it, so the residual gradient is
         added inside that op's backward kernel (no autograd add pass)."""
-        B, S, E = x.shape
-        H, D = self.nhead, self.head_dim
+        B, S, _ = x.shape
+        H, D, E = self.nhead, self.head_dim, self.attn_dim  # E: the width of o
         xr = x
         if self.norm_first:
             if fanout:
@@ -228,11 +266,11 @@ class AttentionCore(nn.Module):
                                                 n_kv_heads=Hkv)
             if Hkv != H:
                 o = ops.attention_gqa_packed(qkv_n, Hkv, causal=self.causal, dropout_p=self.dropout,
-                                             training=self.training, window=self.window,
+                                             training=self.training, scale=self.attn_scale, window=self.window,
                                              softcap=self.attn_softcap)
             else:
                 o = ops.attention_packed(qkv_n, causal=self.causal, dropout_p=self.dropout, training=self.training,
-                                         window=self.window, softcap=self.attn_softcap)
+                                         scale=self.attn_scale, window=self.window, softcap=self.attn_softcap)
             return o.reshape(B, S, E), xr
         if Hkv != H:
             # grouped-query attention: [B, S, H + 2 Hkv, D], the K/V heads read in place by every query head
@@ -243,8 +281,8 @@ class AttentionCore(nn.Module):
             else:
                 qkv4 = qkv.view(B, S, H + 2 * Hkv, D)
             o = ops.attention_gqa_packed(qkv4, Hkv, causal=self.causal, dropout_p=self.dropout,
-                                         training=self.training, window=self.window,
-                                             softcap=self.attn_softcap)
+                                         training=self.training, scale=self.attn_scale, window=self.window,
+                                         softcap=self.attn_softcap)
             return o.reshape(B, S, E), xr
         if self.rope:
             # Q and K rotated: in the projection's own output where no graph is recorded, else into a new tensor
@@ -253,7 +291,7 @@ class AttentionCore(nn.Module):
         else:
             qkv5 = qkv.view(B, S, 3, H, D)
         o = ops.attention_packed(qkv5, causal=self.causal, dropout_p=self.dropout, training=self.training,
-                                 window=self.window, softcap=self.attn_softcap)
+                                 scale=self.attn_scale, window=self.window, softcap=self.attn_softcap)
         return o.reshape(B, S, E), xr
 
     def flops_per_token(self, seq_len: int) -> float:
@@ -265,41 +303,54 @@ class AttentionCore(nn.Module):
             keys = (w * (w + 1) / 2 + (seq_len - w) * w) / seq_len
         else:
             keys = seq_len * (0.5 if self.causal else 1.0)
-        return 2 * self.qkv_dim * e + 4 * keys * e
+        return 2 * self.qkv_dim * e + 4 * keys * self.attn_dim
 
 
 class AttentionOutput(nn.Module):
-    """``out_proj`` + dropout + residual (+ LayerNorm for post-norm): ``(x, o) -> y``."""
+    """``out_proj`` + dropout + residual (+ LayerNorm for post-norm): ``(x, o) -> y``.
+
+    ``attn_dim``: the width of ``o`` (``d_model`` unless the core has a head dim of its own).
+    ``sandwich_norm``: ``y = x + RMSNorm(out_proj(o)) * post_norm_weight``."""
 
     def __init__(self, d_model: int, dropout: float, *, norm_first: bool, layer_norm_eps: float,
-                 norm: str = "layer", bias: bool = True, device=None, dtype=None) -> None:
+                 norm: str = "layer", bias: bool = True, attn_dim: Optional[int] = None, sandwich_norm: bool = False,
+                 device=None, dtype=None) -> None:
         super().__init__()
         fk = {"device": device, "dtype": dtype}
         self.d_model, self.dropout, self.norm_first, self.eps = d_model, dropout, norm_first, layer_norm_eps
         self.norm = norm
-        self.out_proj_weight = mark_gemm_weight(nn.Parameter(torch.empty(d_model, d_model, **fk)))
+        self.attn_dim = d_model if attn_dim is None else int(attn_dim)
+        self.sandwich_norm = _check_sandwich(sandwich_norm, norm_first, norm, dropout)
+        self.out_proj_weight = mark_gemm_weight(nn.Parameter(torch.empty(d_model, self.attn_dim, **fk)))
         self.out_proj_bias = nn.Parameter(torch.empty(d_model, **fk)) if bias else None
         if not norm_first:
             _init_norm(self, d_model, norm, fk)
+        if self.sandwich_norm:  # not a GEMM weight: the norm's backward writes its gradient
+            self.post_norm_weight = nn.Parameter(torch.empty(d_model, **fk))
         self.reset_parameters()
 
     def reset_parameters(self) -> None:
-        bound = 1.0 / math.sqrt(self.d_model)
+        bound = 1.0 / math.sqrt(self.attn_dim)
         nn.init.uniform_(self.out_proj_weight, -bound, bound)
         if self.out_proj_bias is not None:
             nn.init.zeros_(self.out_proj_bias)
         if not self.norm_first:
             _reset_norm(self)
+        if self.sandwich_norm:
+            nn.init.ones_(self.post_norm_weight)
 
     def forward(self, x: Tensor, o: Tensor) -> Tensor:
         p = self.dropout if self.training else 0.0
+        if self.sandwich_norm:
+            a = ops.linear(o, self.out_proj_weight, self.out_proj_bias)
+            return ops.rms_norm_residual(a, x, self.post_norm_weight, self.eps)
         if self.norm_first:
             return ops.linear_residual(o, self.out_proj_weight, self.out_proj_bias, x, p, self.training)
         a = ops.linear(o, self.out_proj_weight, self.out_proj_bias)
         return _norm(self, a, x, p)
 
     def flops_per_token(self, seq_len: int) -> float:
-        return 2 * self.d_model * self.d_model
+        return 2 * self.d_model * self.attn_dim
 
 
 class SelfAttentionBlock(nn.Module):
@@ -313,16 +364,20 @@ class SelfAttentionBlock(nn.Module):
                  causal: bool = False, layer_norm_eps: float = 1e-5, norm: str = "layer", bias: bool = True,
                  rope: bool = False, rope_base: float = 10000.0, n_kv_heads: Optional[int] = None,
                  window: Optional[int] = None, qk_norm: bool = False, attn_softcap: Optional[float] = None,
+                 sandwich_norm: bool = False, head_dim: Optional[int] = None, attn_scale: Optional[float] = None,
                  device=None, dtype=None) -> None:
         super().__init__()
-        if d_model % nhead != 0:
+        if head_dim is None and d_model % nhead != 0:
             raise ValueError("d_model must be divisible by nhead")
+        _check_sandwich(sandwich_norm, norm_first, norm, dropout)
         self.core = AttentionCore(d_model, nhead, dropout, norm_first=norm_first, causal=causal,
                                   layer_norm_eps=layer_norm_eps, norm=norm, bias=bias, rope=rope,
                                   rope_base=rope_base, n_kv_heads=n_kv_heads, window=window, qk_norm=qk_norm,
-                                  attn_softcap=attn_softcap, device=device, dtype=dtype)
+                                  attn_softcap=attn_softcap, head_dim=head_dim, attn_scale=attn_scale,
+                                  device=device, dtype=dtype)
         self.out = AttentionOutput(d_model, dropout, norm_first=norm_first, layer_norm_eps=layer_norm_eps,
-                                   norm=norm, bias=bias, device=device, dtype=dtype)
+                                   norm=norm, bias=bias, attn_dim=self.core.attn_dim, sandwich_norm=sandwich_norm,
+                                   device=device, dtype=dtype)
 
     def reset_parameters(self) -> None:
         self.core.reset_parameters()
@@ -371,7 +426,9 @@ def unpack(packed: Tensor, lead, widths):
 
 class PackedAttentionCore(nn.Module):
     """Pipeline unit: ``x -> stack(x, core(x))`` so a stage boundary can fall
-    between the attention core and its output projection."""
+    between the attention core and its output projection.  A core whose ``o`` is
+    not ``d_model`` wide (``head_dim``) packs ``[.., E + A]``, x then o
+    block-concatenated (see :class:`_Unpack`)."""
 
     def __init__(self, core: AttentionCore) -> None:
         super().__init__()
@@ -383,14 +440,16 @@ class PackedAttentionCore(nn.Module):
     def forward(self, x: Tensor) -> Tensor:
         # x's residual-branch gradient comes back through the QKV dgrad epilogue (fan-out)
         o, xr = self.core.forward_fanout(x, FANOUT)
-        return torch.stack((xr, o))
+        if o.shape[-1] == xr.shape[-1]:
+            return torch.stack((xr, o))
+        return torch.cat((xr.reshape(-1), o.reshape(-1))).view(*x.shape[:-1], x.shape[-1] + o.shape[-1])
 
     def flops_per_token(self, seq_len: int) -> float:
         return self.core.flops_per_token(seq_len)
 
 
 class PackedAttentionOutput(nn.Module):
-    """Pipeline unit: ``stack(x, o) -> out(x, o)``."""
+    """Pipeline unit: ``stack(x, o) -> out(x, o)`` (``cat(x, o)`` of widths ``(E, A)`` when ``A != E``)."""
 
     def __init__(self, out: AttentionOutput) -> None:
         super().__init__()
@@ -400,8 +459,11 @@ class PackedAttentionOutput(nn.Module):
         self.out.reset_parameters()
 
     def forward(self, packed: Tensor) -> Tensor:
-        e = packed.shape[-1]
-        x, o = unpack(packed, packed.shape[1:-1], (e, e))
+        e, a = self.out.d_model, self.out.attn_dim
+        if a != e:
+            x, o = unpack(packed, packed.shape[:-1], (e, a))
+        else:
+            x, o = unpack(packed, packed.shape[1:-1], (e, e))
         return self.out(x, o)
 
     def flops_per_token(self, seq_len: int) -> float:
@@ -418,8 +480,8 @@ class FeedForwardIn(nn.Module):
         self.d_model, self.dim_feedforward = d_model, dim_feedforward
         self.dropout, self.activation, self.norm_first, self.eps = dropout, activation, norm_first, layer_norm_eps
         self.norm = norm
-        # "swiglu": the gate projection (rows [0, F)) and the up projection (rows [F, 2F)) in ONE weight
-        width = 2 * dim_feedforward if activation == "swiglu" else dim_feedforward
+        # "swiglu" / "geglu": the gate projection (rows [0, F)) and the up projection (rows [F, 2F)) in ONE weight
+        width = 2 * dim_feedforward if activation in GATED_ACTS else dim_feedforward
         self.linear1_weight = mark_gemm_weight(nn.Parameter(torch.empty(width, d_model, **fk)))
         self.linear1_bias = nn.Parameter(torch.empty(width, **fk)) if bias else None
         if norm_first:
@@ -442,15 +504,16 @@ class FeedForwardIn(nn.Module):
         only consumer applies the activation backward (:class:`ActFold`)."""
         p = self.dropout if self.training else 0.0
         w, b, act = self.linear1_weight, self.linear1_bias, self.activation
-        if act == "swiglu":
+        if act in GATED_ACTS:
             if p > 0.0:
-                raise ValueError("activation='swiglu' has no dropout between the gate and linear2: set "
+                raise ValueError(f"activation={act!r} has no dropout between the gate and linear2: set "
                                  "act_dropout=0.0 (FeedForwardIn.dropout)")
+            gate = ops.swiglu if act == "swiglu" else ops.geglu
             if self.norm_first:
                 xn, xr = _norm_fanout(self, x) if fanout else (_norm(self, x, None, 0.0), x)
-                return ops.swiglu(ops.linear(xn, w, b)), xr
+                return gate(ops.linear(xn, w, b)), xr
             gu, xr = ops.linear_fanout(x, w, b) if fanout else (ops.linear(x, w, b), x)
-            return ops.swiglu(gu), xr
+            return gate(gu), xr
         if self.norm_first:
             if fanout:
                 xn, xr = _norm_fanout(self, x)
@@ -466,10 +529,12 @@ class FeedForwardIn(nn.Module):
 
 
 class FeedForwardOut(nn.Module):
-    """Second half: ``LN2(x + drop(W2 h + b2))`` (pre-norm: ``x + drop(W2 h + b2)``)."""
+    """Second half: ``LN2(x + drop(W2 h + b2))`` (pre-norm: ``x + drop(W2 h + b2)``;
+    ``sandwich_norm``: ``x + RMSNorm(W2 h + b2) * post_norm_weight``)."""
 
     def __init__(self, d_model: int, dim_feedforward: int, dropout: float, *, norm_first: bool, layer_norm_eps: float,
-                 norm: str = "layer", bias: bool = True, device=None, dtype=None) -> None:
+                 norm: str = "layer", bias: bool = True, sandwich_norm: bool = False, device=None,
+                 dtype=None) -> None:
         super().__init__()
         fk = {"device": device, "dtype": dtype}
         self.d_model, self.dim_feedforward = d_model, dim_feedforward
@@ -479,6 +544,9 @@ class FeedForwardOut(nn.Module):
         self.linear2_bias = nn.Parameter(torch.empty(d_model, **fk)) if bias else None
         if not norm_first:
             _init_norm(self, d_model, norm, fk)
+        self.sandwich_norm = _check_sandwich(sandwich_norm, norm_first, norm, dropout)
+        if self.sandwich_norm:  # not a GEMM weight: the norm's backward writes its gradient
+            self.post_norm_weight = nn.Parameter(torch.empty(d_model, **fk))
         self.reset_parameters()
 
     def reset_parameters(self) -> None:
@@ -488,9 +556,14 @@ class FeedForwardOut(nn.Module):
             nn.init.uniform_(self.linear2_bias, -bound, bound)
         if not self.norm_first:
             _reset_norm(self)
+        if self.sandwich_norm:
+            nn.init.ones_(self.post_norm_weight)
 
     def forward(self, x: Tensor, h: Tensor, fold: Optional[ActFold] = None) -> Tensor:
         p = self.dropout if self.training else 0.0
+        if self.sandwich_norm:
+            h = ops.linear(h, self.linear2_weight, self.linear2_bias, act_fold_in=fold)
+            return ops.rms_norm_residual(h, x, self.post_norm_weight, self.eps)
         if self.norm_first:
             return ops.linear_residual(h, self.linear2_weight, self.linear2_bias, x, p, self.training,
                                        act_fold_in=fold)
@@ -516,6 +589,7 @@ class FeedForwardBlock(nn.Module):
         layer_norm_eps: float = 1e-5,
         norm: str = "layer",
         bias: bool = True,
+        sandwich_norm: bool = False,
         device=None,
         dtype=None,
     ) -> None:
@@ -525,8 +599,8 @@ class FeedForwardBlock(nn.Module):
         self.fc_in = FeedForwardIn(d_model, dim_feedforward, dropout, activation, norm_first=norm_first,
                                    layer_norm_eps=layer_norm_eps, norm=norm, bias=bias, device=device, dtype=dtype)
         self.fc_out = FeedForwardOut(d_model, dim_feedforward, dropout, norm_first=norm_first,
-                                     layer_norm_eps=layer_norm_eps, norm=norm, bias=bias, device=device,
-                                     dtype=dtype)
+                                     layer_norm_eps=layer_norm_eps, norm=norm, bias=bias,
+                                     sandwich_norm=sandwich_norm, device=device, dtype=dtype)
 
     def reset_parameters(self) -> None:
         self.fc_in.reset_parameters()
@@ -607,14 +681,19 @@ class TransformerEncoderLayer(nn.Sequential):
         window: Optional[int] = None,
         qk_norm: bool = False,
         attn_softcap: Optional[float] = None,
+        sandwich_norm: bool = False,
+        head_dim: Optional[int] = None,
+        attn_scale: Optional[float] = None,
     ) -> None:
         super().__init__(
             SelfAttentionBlock(d_model, nhead, dropout, norm_first=norm_first, causal=causal,
                                layer_norm_eps=layer_norm_eps, norm=norm, bias=bias, rope=rope, rope_base=rope_base,
                                n_kv_heads=n_kv_heads, window=window, qk_norm=qk_norm, attn_softcap=attn_softcap,
+                               sandwich_norm=sandwich_norm, head_dim=head_dim, attn_scale=attn_scale,
                                device=device, dtype=dtype),
             FeedForwardBlock(d_model, dim_feedforward, dropout, activation, norm_first=norm_first,
-                             layer_norm_eps=layer_norm_eps, norm=norm, bias=bias, device=device, dtype=dtype),
+                             layer_norm_eps=layer_norm_eps, norm=norm, bias=bias, sandwich_norm=sandwich_norm,
+                             device=device, dtype=dtype),
         )
 
     @torch.no_grad()
@@ -641,6 +720,22 @@ class TransformerEncoderLayer(nn.Sequential):
         return self
 
 
+def check_global_every(global_every: Optional[int], window: Optional[int]) -> None:
+    if global_every is None:
+        return
+    if isinstance(global_every, bool) or not isinstance(global_every, int) or global_every < 2:
+        raise ValueError(f"global_every must be an int >= 2 or None, got {global_every!r}")
+    if window is None:
+        raise ValueError("global_every (local / global layers) needs a window for the local layers")
+
+
+def layer_window(window: Optional[int], global_every: Optional[int], i: int) -> Optional[int]:
+    """The window of layer ``i`` (0-based): none for a global layer, ``(i + 1) % global_every == 0``."""
+    if global_every is not None and (i + 1) % global_every == 0:
+        return None
+    return window
+
+
 def transformer_blocks(
     num_layers: int,
     d_model: int,
@@ -659,16 +754,26 @@ def transformer_blocks(
     window: Optional[int] = None,
     qk_norm: bool = False,
     attn_softcap: Optional[float] = None,
+    sandwich_norm: bool = False,
+    head_dim: Optional[int] = None,
+    attn_scale: Optional[float] = None,
+    global_every: Optional[int] = None,
     device=None,
     dtype=None,
 ) -> List[nn.Module]:
-    """``2 * num_layers`` single-tensor blocks (attention, MLP, attention, ...)."""
+    """``2 * num_layers`` single-tensor blocks (attention, MLP, attention, ...).
+
+    ``global_every=n`` (needs ``window``): layer ``i`` (0-based) with ``(i + 1) % n == 0`` is a global layer,
+    built with ``window=None``; every other layer gets the window (:func:`layer_window`)."""
+    check_global_every(global_every, window)
     blocks: List[nn.Module] = []
-    for _ in range(num_layers):
+    for i in range(num_layers):
         layer = TransformerEncoderLayer(d_model, nhead, dim_feedforward, dropout, activation,
                                         norm_first=norm_first, causal=causal, norm=norm, bias=bias, rope=rope,
-                                        rope_base=rope_base, n_kv_heads=n_kv_heads, window=window, qk_norm=qk_norm,
-                                        attn_softcap=attn_softcap, device=device, dtype=dtype)
+                                        rope_base=rope_base, n_kv_heads=n_kv_heads,
+                                        window=layer_window(window, global_every, i), qk_norm=qk_norm,
+                                        attn_softcap=attn_softcap, sandwich_norm=sandwich_norm, head_dim=head_dim,
+                                        attn_scale=attn_scale, device=device, dtype=dtype)
         blocks.extend(layer.children())
     return blocks
 

@@ -6,12 +6,14 @@ CPU tensors (plumbing tests).  GPU tensors never fall back to eager PyTorch:
 a missing extension raises (``mipipe._native_loader.kernels``).
 """
 from .layernorm import add_dropout_layer_norm, layer_norm_fanout, layer_norm_reference
-from .rmsnorm import add_dropout_rms_norm, rms_norm_fanout, rms_norm_reference
+from .rmsnorm import (add_dropout_rms_norm, rms_norm_fanout, rms_norm_reference, rms_norm_residual,
+                      rms_norm_residual_reference)
 from .linear import deferred_wgrad, flush_wgrad, linear, linear_fanout, linear_residual
 from .attention import attention, attention_gqa_packed, attention_packed, attention_reference
 from .activation import bias_act_dropout
 from .softcap import softcap, softcap_owned, softcap_reference
 from .swiglu import swiglu, swiglu_reference
+from .geglu import geglu, geglu_reference
 from .rope import rope_heads, rope_packed, rope_projection, rope_reference, rope_tables
 from .qknorm import qk_norm_rope_heads, qk_norm_rope_projection, qk_norm_rope_reference
 from .loss import cross_entropy
@@ -24,6 +26,8 @@ __all__ = [
     "add_dropout_rms_norm",
     "rms_norm_fanout",
     "rms_norm_reference",
+    "rms_norm_residual",
+    "rms_norm_residual_reference",
     "linear",
     "linear_fanout",
     "linear_residual",
@@ -39,6 +43,8 @@ __all__ = [
     "softcap_reference",
     "swiglu",
     "swiglu_reference",
+    "geglu",
+    "geglu_reference",
     "rope_tables",
     "rope_packed",
     "rope_projection",

@@ -5,6 +5,13 @@ the LLaMA-style block's norm, with the contract of :mod:`mipipe.ops.layernorm`
 (no mean, no bias).  GPU tensors always go to the HIP kernel (a missing
 extension raises); CPU tensors use the eager reference so CPU-only tests
 exercise the same module code.
+
+``rms_norm_residual`` is the sandwich norm of the Gemma-2 block, the norm on
+the branch instead of on the sum: ``y = residual + x * rsqrt(mean(x^2) + eps) *
+weight`` -- a variant of the same forward kernels (one pass: ``x``, ``residual``
+and ``weight`` read, ``y`` and ``rstd`` written) and, for ``x`` and ``weight``,
+the same backward kernels on the saved ``x``; the residual's gradient is the
+output's, the same tensor.
 """
 from __future__ import annotations
 
@@ -17,7 +24,8 @@ from torch import Tensor
 from ._util import kernels_for
 from .linear import accumulable
 
-__all__ = ["add_dropout_rms_norm", "rms_norm_fanout", "rms_norm_reference"]
+__all__ = ["add_dropout_rms_norm", "rms_norm_fanout", "rms_norm_reference", "rms_norm_residual",
+           "rms_norm_residual_reference"]
 
 
 def rms_norm_reference(x: Tensor, residual: Optional[Tensor], weight: Tensor, eps: float, p: float,
@@ -96,3 +104,43 @@ def rms_norm_fanout(x: Tensor, weight: Tensor, eps: float = 1e-5):
     if not x.is_cuda or not torch.is_grad_enabled() or not x.requires_grad:
         return add_dropout_rms_norm(x, None, weight, eps, 0.0, True), x
     return _AddDropoutRmsNorm.apply(x, None, weight, float(eps), 0.0, True)
+
+
+def rms_norm_residual_reference(x: Tensor, residual: Tensor, weight: Tensor, eps: float) -> Tensor:
+    """Eager ``residual + RMSNorm(x) * weight``: fp32 at least, one rounding at the end."""
+    xf = x.float() if x.dtype in (torch.bfloat16, torch.float16) else x
+    y = residual.to(xf.dtype) + xf * torch.rsqrt(xf.pow(2).mean(-1, keepdim=True) + eps) * weight.to(xf.dtype)
+    return y.to(x.dtype)
+
+
+class _RmsNormResidual(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, residual, weight, eps, save=True):  # type: ignore[override]
+        ctx.set_materialize_grads(False)
+        xc = x.contiguous()
+        # rstd is written only for a backward; x (the GEMM's output) is saved as it is
+        y, rstd = kernels_for(x).rmsnorm_residual_fwd(xc, residual.contiguous(), weight, eps, save)
+        if save:
+            ctx.save_for_backward(xc, rstd, weight)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):  # type: ignore[override]
+        if dy is None:
+            return None, None, None, None, None
+        x, rstd, weight = ctx.saved_tensors
+        dx = dgamma = None
+        if ctx.needs_input_grad[0] or ctx.needs_input_grad[2]:
+            # dgamma accumulates straight into the fp32 main_grad buffer when there is one
+            dx, _, dgamma = kernels_for(dy).rmsnorm_bwd(dy.contiguous(), x, rstd, weight, 0.0, 0, 0,
+                                                        accumulable(weight), None)
+        return dx, dy, dgamma, None, None
+
+
+def rms_norm_residual(x: Tensor, residual: Tensor, weight: Tensor, eps: float = 1e-5) -> Tensor:
+    """``residual + RMSNorm(x) * weight``, the statistics from ``x`` alone (no dropout)."""
+    if x.shape != residual.shape:
+        raise ValueError(f"rms_norm_residual: x {tuple(x.shape)} and residual {tuple(residual.shape)} differ")
+    if not x.is_cuda:
+        return rms_norm_residual_reference(x, residual, weight, eps)
+    return _RmsNormResidual.apply(x, residual, weight, float(eps), torch.is_grad_enabled())

@@ -284,13 +284,13 @@ def measure_engine_costs(cfg: LMConfig, micro_batch: int, chunks: int, checkpoin
     """``{kind: ms per micro-batch}`` in engine context (module docstring):
     checkpoint recompute, the deferred weight-gradient flush, the optimizer
     step and the host's issue overhead included as a pipeline rank pays them."""
-    from .stage import UNITS_PER_LAYER, block_costs, split_allowed
+    from .stage import UNITS_PER_LAYER, block_costs, split_allowed, unit_kind
 
     device = torch.device(device)
     if cfg.num_layers < 3:
         raise ValueError("engine-context calibration needs >= 3 layers")
     iso = measure_unit_times(cfg, micro_batch, chunks=min(chunks, 4), device=device, dtype=dtype,
-                             kinds=LAYER_KINDS + ("norm", "dec", "dec_head", "dec_tail"))
+                             kinds=LAYER_KINDS + ("core_global", "norm", "dec", "dec_head", "dec_tail"))
     rec = {"never": 0.0, "except_last": (chunks - 1) / chunks, "always": 1.0}[checkpoint]
     iso_cost = {k: f * (1.0 + rec) + b for k, (f, b) in iso.items()}
     per = lambda ms: ms / chunks  # noqa: E731  -- per micro-batch
@@ -298,13 +298,22 @@ def measure_engine_costs(cfg: LMConfig, micro_batch: int, chunks: int, checkpoin
                                                         device=device, dtype=dtype, steps=steps))
     L = UNITS_PER_LAYER
     layer = run(1, 1 + 2 * L) / 2.0
-    out = {"enc": max(run(0, 1 + L) - layer, 0.0)}
-    tot = sum(iso_cost[k] for k in LAYER_KINDS)
-    for k in LAYER_KINDS:
-        out[k] = layer * iso_cost[k] / tot
-    norm = 1 if cfg.norm_first else 0
     n = len(block_costs(cfg, False))
-    end = max(run(n - 1 - norm - L, n) - layer, 0.0)  # norm + decoder
+    norm = 1 if cfg.norm_first else 0
+    if cfg.global_every is None:
+        first = last = layer
+        tot = sum(iso_cost[k] for k in LAYER_KINDS)
+        out = {k: layer * iso_cost[k] / tot for k in LAYER_KINDS}
+    else:
+        # local / global layers: the two timed layers (0 and 1) are shared out over their own kinds, and the
+        # layers next to the encoder and the decoder are priced as what they are
+        kinds_of = lambda i: (unit_kind(cfg, 1 + L * i),) + LAYER_KINDS[1:]  # noqa: E731
+        scale = 2.0 * layer / sum(iso_cost[k] for i in (0, 1) for k in kinds_of(i))
+        out = {k: scale * iso_cost[k] for k in LAYER_KINDS + ("core_global",)}
+        first = sum(out[k] for k in kinds_of(0))
+        last = sum(out[k] for k in kinds_of(cfg.num_layers - 1))
+    out["enc"] = max(run(0, 1 + L) - first, 0.0)
+    end = max(run(n - 1 - norm - L, n) - last, 0.0)  # norm + decoder
     if norm:
         share = iso_cost["norm"] / (iso_cost["norm"] + iso_cost["dec"])
         out["norm"], out["dec"] = end * share, end * (1 - share)
@@ -314,7 +323,7 @@ def measure_engine_costs(cfg: LMConfig, micro_batch: int, chunks: int, checkpoin
         return out
     ns = len(block_costs(cfg, True))
     tail = run(ns - 1, ns, True)
-    head = max(run(ns - 2 - norm - L, ns - 1, True) - layer - out.get("norm", 0.0), 0.0)
+    head = max(run(ns - 2 - norm - L, ns - 1, True) - last - out.get("norm", 0.0), 0.0)
     out["dec_head"], out["dec_tail"] = head, tail
     return out
 

@@ -17,7 +17,7 @@ from torch import nn
 
 from ..balance import balance_cost
 from ..models.lm import LMConfig, TargetSequential, build_lm_blocks, lm_pipeline_units
-from ..models.transformer import merge_units
+from ..models.transformer import GATED_ACTS, merge_units
 from ..models.vocab_split import STAT_SLOTS, split_point
 from ..ops.linear import mark_gemm_weight
 
@@ -62,14 +62,16 @@ def block_costs(cfg: LMConfig, split_decoder: bool = False) -> List[float]:
     ``[Encoder, (attn core, attn out, mlp in, mlp out) x L, (final norm), Decoder]``
     (see ``mipipe.models.transformer.pipeline_units``)."""
     e, f, s, v = cfg.d_model, cfg.dim_feedforward, cfg.seq_len, cfg.vocab
-    # mean number of keys a query sees (AttentionCore.flops_per_token): a sliding window w < s bounds it
-    w = cfg.window
-    keys = (w * (w + 1) / 2 + (s - w) * w) / s if w is not None and w < s else s * (0.5 if cfg.causal else 1.0)
-    # the QKV projection is (H + 2 Hkv) D wide: 3 e without grouped-query attention
-    qkv = cfg.qkv_dim()
-    core = 3.0 * (2 * qkv * e + 4 * keys * e) + 3.0 * 10 * e
-    out = 3.0 * (2 * e * e) + 3.0 * 10 * e  # + LN/dropout traffic
-    if cfg.activation == "swiglu":  # the gated first GEMM is 2F wide, and the gate is a pass of its own
+
+    def core_cost(w: Optional[int]) -> float:
+        # mean number of keys a query sees (AttentionCore.flops_per_token): a sliding window w < s bounds it
+        keys = (w * (w + 1) / 2 + (s - w) * w) / s if w is not None and w < s else s * (0.5 if cfg.causal else 1.0)
+        # the QKV projection is (H + 2 Hkv) D wide (3 e without grouped-query attention), the scores and the
+        # weighted sum H D = A wide (e unless the head dim is the config's own)
+        return 3.0 * (2 * cfg.qkv_dim() * e + 4 * keys * cfg.attn_dim()) + 3.0 * 10 * e
+
+    out = 3.0 * (2 * e * cfg.attn_dim()) + 3.0 * 10 * e  # + LN/dropout traffic
+    if cfg.activation in GATED_ACTS:  # the gated first GEMM is 2F wide, and the gate is a pass of its own
         mlp_in = 3.0 * (2 * e * 2 * f) + 3.0 * 10 * f
     else:
         mlp_in = 3.0 * (2 * e * f) + 3.0 * 5 * f
@@ -77,8 +79,8 @@ def block_costs(cfg: LMConfig, split_decoder: bool = False) -> List[float]:
     enc = 3.0 * 40 * e  # gather + scatter-add traffic, expressed in FLOP-equivalents
     dec = 3.0 * (2 * e * v) + 3.0 * 4 * v  # GEMM + cross-entropy passes
     costs = [enc]
-    for _ in range(cfg.num_layers):
-        costs += [core, out, mlp_in, mlp_out]
+    for i in range(cfg.num_layers):  # a global layer's core (global_every) is priced without the window
+        costs += [core_cost(cfg.layer_window(i)), out, mlp_in, mlp_out]
     if cfg.norm_first:
         costs.append(3.0 * 10 * e)
     if split_decoder:
@@ -373,16 +375,21 @@ def _unload_busiest(plan: StagePlan, costs: List[float], chunks: int, bwd_ratio:
 
 
 UNITS_PER_LAYER = 4  # attention core, attention output, mlp in, mlp out
+CORE_KINDS = ("core", "core_global")  # the packed attention cores: local (or every layer's) and global
 
 
 def unit_kind(cfg: LMConfig, index: int, split_decoder: bool = False) -> str:
     """``enc`` / ``core`` / ``out`` / ``mlp_in`` / ``mlp_out`` / ``norm`` / ``dec``
-    (``dec_head`` / ``dec_tail`` when the decoder is split)."""
+    (``dec_head`` / ``dec_tail`` when the decoder is split).  Under ``cfg.global_every`` the core of a
+    global layer is ``core_global``: it attends every key, so it is measured and priced on its own."""
     if index == 0:
         return "enc"
     body = UNITS_PER_LAYER * cfg.num_layers
     if index <= body:
-        return ("core", "out", "mlp_in", "mlp_out")[(index - 1) % UNITS_PER_LAYER]
+        layer, part = divmod(index - 1, UNITS_PER_LAYER)
+        if part == 0 and cfg.global_every is not None and cfg.layer_window(layer) is None:
+            return "core_global"
+        return ("core", "out", "mlp_in", "mlp_out")[part]
     rest = index - body - 1 - (1 if cfg.norm_first else 0)
     if rest < 0:
         return "norm"
@@ -393,18 +400,20 @@ def unit_kind(cfg: LMConfig, index: int, split_decoder: bool = False) -> str:
 
 def unit_is_packed_core(cfg: LMConfig, index: int) -> bool:
     """True if pipeline unit ``index`` is an attention core (packed output)."""
-    return unit_kind(cfg, index) == "core"
+    return unit_kind(cfg, index) in CORE_KINDS
 
 
 def stage_input_shape(cfg: LMConfig, plan: StagePlan, vstage: int, micro_batch: int) -> Tuple[int, ...]:
     """Shape of the activation virtual stage ``vstage`` receives: ``[2, mb, S, E]``
-    after a packed attention core, ``[mb, S, E + F]`` after a packed MLP input
-    half, else ``[mb, S, E]``."""
+    after a packed attention core (``[mb, S, E + A]`` when its heads are ``A != E``
+    wide in all), ``[mb, S, E + F]`` after a packed MLP input half, else ``[mb, S, E]``."""
     base = (micro_batch, cfg.seq_len, cfg.d_model)
     if vstage == 0:
         return base
     kind = unit_kind(cfg, plan.slice(vstage).start - 1, plan.split_decoder)
-    if kind == "core":
+    if kind in CORE_KINDS:
+        if cfg.attn_dim() != cfg.d_model:
+            return (micro_batch, cfg.seq_len, cfg.d_model + cfg.attn_dim())
         return (2,) + base
     if kind == "mlp_in":
         return (micro_batch, cfg.seq_len, cfg.d_model + cfg.dim_feedforward)
