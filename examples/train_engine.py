@@ -18,6 +18,12 @@ Data: a local text file (``--train-file``: basic_english tokens, batchified as
 ``main.py:92-113``) or a synthetic Zipf stream (no network).  Each step takes
 the next ``seq_len + 1`` rows of the batchified stream; replica ``d`` trains on
 its slice of the batch columns, micro-batches are consecutive column groups.
+
+``--doc-eos ID``: sequence packing with document masks.  Token ``ID`` ends a
+document; each batch's bounds (``utils.data.document_bounds``) go to every
+rank's ``engine.step(..., doc_bounds=...)``, so a token attends inside its own
+document only, and the target of each document's last token -- the next
+document's first -- is left out of the loss.
 """
 from __future__ import annotations
 
@@ -63,6 +69,8 @@ def parse(argv=None):
     ap.add_argument("--save-dir", default=None, help="write one training-state file per pipeline rank at the end")
     ap.add_argument("--resume-dir", default=None, help="continue from --save-dir files (same pp and model)")
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--doc-eos", type=int, default=None, metavar="ID",
+                    help="token id that ends a document: mask attention across documents (causal models)")
     return ap.parse_args(argv)
 
 
@@ -106,7 +114,11 @@ def main(argv=None) -> int:
         mine = win[groups.replica * m * mb:(groups.replica + 1) * m * mb]
         xs = [mine[j * mb:(j + 1) * mb, :S].to(device) for j in range(m)]
         ts = [mine[j * mb:(j + 1) * mb, 1:].contiguous().to(device) for j in range(m)]
-        return xs, ts
+        if args.doc_eos is None:
+            return xs, ts, None
+        # every rank builds the bounds (each stage's attention needs them); tensor ops on the device, no sync
+        ts = [D.mask_boundary_targets(t, x, args.doc_eos) for x, t in zip(xs, ts)]
+        return xs, ts, [D.document_bounds(x, args.doc_eos) for x in xs]
 
     # ---- this rank's stage (same initial weights in every replica)
     plan = plan_stages(cfg, pp, 1, m)
@@ -127,12 +139,12 @@ def main(argv=None) -> int:
     reporter = rank == world - 1  # last stage of the last replica
     t0 = time.perf_counter()
     for step in range(start, args.steps):
-        xs, ts = batch(step)
+        xs, ts, docs = batch(step)
         opt.zero_grad()
         if dpg is not None:
             dpg.begin()
         try:
-            st = engine.step(xs if groups.stage == 0 else None, ts)
+            st = engine.step(xs if groups.stage == 0 else None, ts, doc_bounds=docs)
         except BaseException:
             if dpg is not None:
                 dpg.abort()  # unhook the gradient buckets from the weight-gradient flush

@@ -232,7 +232,21 @@ class Recompute(torch.autograd.Function):
 
 
 def checkpoint(function: Callable[..., Any], input: Union[Tensor, Tuple[Any, ...]]):
-    """Checkpoints ``function(input)`` outside a pipeline (upstream helper)."""
+    """Checkpoints ``function(input)`` outside a pipeline (upstream helper).
+
+    The calling thread's document bounds (``ops.use_documents``) are part of the
+    forward: the recompute runs on autograd's thread, which does not see the
+    thread-local, so it re-enters the bounds the first forward ran under."""
+    from .ops.attention import current_documents, use_documents  # (ops.attention imports this module)
+
+    docs = current_documents()
+    if docs is not None:
+        inner = function
+
+        def function(*args):  # noqa: F811
+            with use_documents(docs):
+                return inner(*args)
+
     batch = Batch(input)
     chk = Checkpointing(function, batch)
     batch = chk.checkpoint()

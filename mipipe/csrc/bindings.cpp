@@ -1519,6 +1519,26 @@ float attn_softcap(const char* who, double softcap, const Tensor& q) {
   return c;
 }
 
+// Document-masked attention: `doc_bounds` int32 [B, 2, S] on q's device, contiguous (row 0: first token of each
+// token's document, row 1: one past its last), causal bf16 only and always on attention.hip's generic kernels.
+// Argument checks only: the values are the caller's contract (ops.check_doc_bounds), and the kernels clamp what
+// they take from them.
+void attn_docs(AttnArgs& a, const char* who, const std::optional<Tensor>& doc_bounds, bool causal, const Tensor& q) {
+  if (!doc_bounds || !doc_bounds->defined()) return;
+  const Tensor& d = *doc_bounds;
+  MP_CHECK(causal, who, ": doc_bounds needs causal attention");
+  MP_CHECK(q.scalar_type() == at::kBFloat16, who, ": document-masked attention runs on the bf16 kernels only, got ",
+           q.scalar_type());
+  MP_CHECK(d.scalar_type() == at::kInt, who, ": doc_bounds must be int32, got ", d.scalar_type());
+  MP_CHECK(d.dim() == 3 && d.size(0) == a.B && d.size(1) == 2 && d.size(2) == a.S, who,
+           ": doc_bounds must be [B, 2, S] = [", a.B, ", 2, ", a.S, "]");
+  MP_CHECK(d.device() == q.device(), who, ": doc_bounds must be on q's device");
+  MP_CHECK(d.is_contiguous(), who, ": doc_bounds must be contiguous");
+  MP_CHECK(reinterpret_cast<uintptr_t>(d.data_ptr()) % 16 == 0, who, ": doc_bounds must be 16-byte aligned");
+  a.doc_start = static_cast<const int32_t*>(d.data_ptr());
+  a.doc_end = a.doc_start + a.S;
+}
+
 // Returns (o, lse, seed, offset, dropout keep bits): the bits tensor (int32
 // [B*H, S/32, S]) is non-empty only for the long-sequence kernels with p > 0
 // and must be handed back to attention_bwd.  A windowed call (0 < window < S) or a soft-capped one returns none.
@@ -1527,9 +1547,11 @@ float attn_softcap(const char* who, double softcap, const Tensor& q) {
 std::tuple<Tensor, Tensor, int64_t, int64_t, Tensor> py_attention_fwd(Tensor q, Tensor k, Tensor v, bool causal,
                                                                       double p, double scale, int64_t kv_len,
                                                                       std::optional<Tensor> words, int64_t words_seed,
-                                                                      int64_t words_offset, int64_t window, double softcap) {
+                                                                      int64_t words_offset, int64_t window, double softcap,
+                                                                      std::optional<Tensor> doc_bounds) {
   AttnArgs a;
   fill_qkv(a, q, k, v);
+  attn_docs(a, "attention", doc_bounds, causal, q);
   a.window = attn_window("attention", window, causal, q, a.S);
   a.softcap = attn_softcap("attention", softcap, q);
   MP_CHECK(p >= 0.0 && p < 1.0, "attention: bad dropout p");
@@ -1547,7 +1569,7 @@ std::tuple<Tensor, Tensor, int64_t, int64_t, Tensor> py_attention_fwd(Tensor q, 
   Tensor bits = at::empty({0}, q.options().dtype(at::kInt));
   if (q.scalar_type() == at::kFloat) {
     attention_f32_fwd(a, cur_stream(q));
-  } else if (a.window == 0 && a.softcap == 0.f && use_long(q, a.S, a.D)) {
+  } else if (a.window == 0 && a.softcap == 0.f && a.doc_start == nullptr && use_long(q, a.S, a.D)) {
     bool reuse = false;
     if (p > 0.0) {
       const std::vector<int64_t> shape = {(int64_t)a.B * a.H, a.S / 32, a.S};
@@ -1567,9 +1589,11 @@ std::tuple<Tensor, Tensor, int64_t, int64_t, Tensor> py_attention_fwd(Tensor q, 
 
 void py_attention_bwd(Tensor dout, Tensor q, Tensor k, Tensor v, Tensor o, Tensor lse, bool causal, double p,
                       double scale, int64_t seed, int64_t offset, Tensor dq, Tensor dk, Tensor dv,
-                      std::optional<Tensor> bits, int64_t kv_len, int64_t window, double softcap) {
+                      std::optional<Tensor> bits, int64_t kv_len, int64_t window, double softcap,
+                      std::optional<Tensor> doc_bounds) {
   AttnArgs a;
   fill_qkv(a, q, k, v);
+  attn_docs(a, "attention_bwd", doc_bounds, causal, q);
   a.window = attn_window("attention_bwd", window, causal, q, a.S);
   a.softcap = attn_softcap("attention_bwd", softcap, q);
   MP_CHECK(kv_len == 0 || (q.scalar_type() == at::kFloat && kv_len > 0 && kv_len <= a.S),
@@ -1613,7 +1637,7 @@ void py_attention_bwd(Tensor dout, Tensor q, Tensor k, Tensor v, Tensor o, Tenso
   a.scale = (float)scale; a.p = (float)p; a.seed = (uint64_t)seed; a.offset = (uint64_t)offset; a.causal = causal;
   if (q.scalar_type() == at::kFloat) {
     attention_f32_bwd(a, cur_stream(q));
-  } else if (a.window == 0 && a.softcap == 0.f && use_long(q, a.S, a.D)) {
+  } else if (a.window == 0 && a.softcap == 0.f && a.doc_start == nullptr && use_long(q, a.S, a.D)) {
     if (p > 0.0) {
       MP_CHECK(bits && bits->is_cuda() && bits->scalar_type() == at::kInt &&
                    bits->numel() == (int64_t)a.B * a.H * (a.S / 32) * a.S,
@@ -1847,11 +1871,12 @@ PYBIND11_MODULE(_C, m) {
   m.def("attention_f32_supported", [](int64_t S, int64_t D) { return attention_f32_supported((int)S, (int)D); });
   m.def("attention_fwd", &py_attention_fwd, py::arg("q"), py::arg("k"), py::arg("v"), py::arg("causal"), py::arg("p"),
         py::arg("scale"), py::arg("kv_len") = 0, py::arg("words") = py::none(), py::arg("words_seed") = 0,
-        py::arg("words_offset") = 0, py::arg("window") = 0, py::arg("softcap") = 0.0);
+        py::arg("words_offset") = 0, py::arg("window") = 0, py::arg("softcap") = 0.0,
+        py::arg("doc_bounds") = py::none());
   m.def("attention_bwd", &py_attention_bwd, py::arg("dout"), py::arg("q"), py::arg("k"), py::arg("v"), py::arg("o"),
         py::arg("lse"), py::arg("causal"), py::arg("p"), py::arg("scale"), py::arg("seed"), py::arg("offset"),
         py::arg("dq"), py::arg("dk"), py::arg("dv"), py::arg("bits") = py::none(), py::arg("kv_len") = 0,
-        py::arg("window") = 0, py::arg("softcap") = 0.0);
+        py::arg("window") = 0, py::arg("softcap") = 0.0, py::arg("doc_bounds") = py::none());
   m.def("attention_long_supported", [](int64_t S, int64_t D) { return attention_long_supported((int)S, (int)D); });
   m.def("attention_long_set_fused_rng", &attention_long_set_fused_rng,
         "long-sequence attention: make the dropout keep words inside the forward kernel (true, default) or in a "

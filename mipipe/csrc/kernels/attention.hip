@@ -201,6 +201,28 @@ __device__ __forceinline__ float softcap_r(float raw, float cap_in) {
   return __builtin_amdgcn_rcpf(1.f + __builtin_amdgcn_exp2f(raw * cap_in));
 }
 
+// ------------------------------------------------------------------ document masks
+// DOCS (only with CAUSAL): packed sequences.  Query i sees the keys [lo(i), i], lo(i) = max(i - a.window + 1,
+// doc_start[i]); key j is seen by the queries [j, hi(j)), hi(j) = min(j + a.window, doc_end[j]).  The window is
+// merged at run time (the host passes a.window = S when there is none), so DOCS does not multiply with WINDOW.
+// doc_start and doc_end are non-decreasing along a row, so a tile's first query row has the tile's smallest
+// lower edge and a tile's last key the largest upper edge: the tile-loop bounds are one uniform load per block.
+// They come from a tensor, so both are clamped to the range the causal loop visits -- a malformed tensor gives
+// wrong numbers, never an access outside q, k, v, lse or delta.
+__device__ __forceinline__ int doc_tbeg(const AttnArgs& a, int b, int q0, int qt) {
+  const int lo = max(q0 - a.window + 1, a.doc_start[(int64_t)b * 2 * a.S + q0]);
+  return min(max(lo, 0) / kRows, qt);  // first key tile row q0 sees, in [0, qt]
+}
+__device__ __forceinline__ int doc_nq(const AttnArgs& a, int b, int k0, int kt) {
+  const int hi = min(k0 + kRows - 1 + a.window, a.doc_end[(int64_t)b * 2 * a.S + k0 + kRows - 1]);
+  // one past the last query tile, in [kt + 1, S / 64]
+  return min(max((max(hi, 1) - 1) / kRows + 1, kt + 1), a.S / kRows);
+}
+// The bounds of a lane's four rows row0 .. row0 + 3 (row0 % 4 == 0) in one 16-byte load.
+__device__ __forceinline__ int4 doc_rows4(const int32_t* bounds, const AttnArgs& a, int b, int row0) {
+  return *reinterpret_cast<const int4*>(bounds + (int64_t)b * 2 * a.S + row0);
+}
+
 // ------------------------------------------------------------------ forward
 // SOFTCAP: the capped score (softcap_r) replaces the scaled one; lse is the log-sum-exp of the capped scores.
 // WINDOW (only with CAUSAL): sliding-window attention, query i sees the a.window keys (i - a.window, i].  The
@@ -208,9 +230,12 @@ __device__ __forceinline__ float softcap_r(float raw, float cap_in) {
 // at 0; the tiles wholly below the band are never loaded.  A later row of the query tile can find the first
 // visited tile wholly masked: its running max stays -inf there and the m == -inf guards below give alpha = 0 and
 // p = 0, as they do for a fresh row, so exp2 never sees (-inf) - (-inf).
-template <int D, bool CAUSAL, bool WINDOW = false, bool SOFTCAP = false>
+// DOCS (only with CAUSAL, see above): the loop starts at the tile of lo(q0); the mask is key < lo(row).  The same
+// guards cover a later row whose document starts after the first visited tile.
+template <int D, bool CAUSAL, bool WINDOW = false, bool SOFTCAP = false, bool DOCS = false>
 __global__ void __launch_bounds__(kThreads, D == 256 ? 1 : 2) attn_fwd_kernel(AttnArgs a) {
   static_assert(!WINDOW || CAUSAL, "the sliding window is a band of the causal mask");
+  static_assert(!DOCS || (CAUSAL && !WINDOW), "documents mask the causal triangle and merge the window at run time");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   char* kimg = smem;
   char* vimg = smem + Img<D>::kBytes;
@@ -248,8 +273,17 @@ __global__ void __launch_bounds__(kThreads, D == 256 ? 1 : 2) attn_fwd_kernel(At
   const float pscale = a.p > 0.f ? 1.f / (1.f - a.p) : 1.f;
   const int qrow0 = q0 + wave * 16 + 4 * (lane >> 4);  // this lane's rows qrow0 .. +3
   const int ntiles = CAUSAL ? qt + 1 : a.S / kRows;
-  const int tbeg = WINDOW ? max(0, q0 - a.window + 1) / kRows : 0;  // first tile with a key row q0 sees
+  const int tbeg = DOCS ? doc_tbeg(a, b, q0, qt)
+                        : (WINDOW ? max(0, q0 - a.window + 1) / kRows : 0);  // first tile with a key row q0 sees
   const int wrow0 = WINDOW ? qrow0 - a.window : 0;                  // row qrow0 + r sees keys > wrow0 + r
+  int dlo[4] = {0, 0, 0, 0};                                        // DOCS: row qrow0 + r sees keys >= dlo[r]
+  if constexpr (DOCS) {
+    const int4 st = doc_rows4(a.doc_start, a, b, qrow0);
+    dlo[0] = max(qrow0 - a.window + 1, st.x);
+    dlo[1] = max(qrow0 - a.window + 2, st.y);
+    dlo[2] = max(qrow0 - a.window + 3, st.z);
+    dlo[3] = max(qrow0 - a.window + 4, st.w);
+  }
   const float cap_in = SOFTCAP ? 2.f * sl2 / a.softcap : 0.f;       // raw score -> exponent of e (softcap_r)
   const float cap_l2 = SOFTCAP ? a.softcap * kLog2e : 0.f;          // t -> capped score, log2 domain
 
@@ -297,6 +331,7 @@ __global__ void __launch_bounds__(kThreads, D == 256 ? 1 : 2) attn_fwd_kernel(At
         else x = sacc[j][r] * sl2;
         if (CAUSAL && key > qrow0 + r) x = -INFINITY;
         if (WINDOW && key <= wrow0 + r) x = -INFINITY;
+        if (DOCS && key < dlo[r]) x = -INFINITY;
         sv[j][r] = x;
         tmax[r] = fmaxf(tmax[r], x);
       }
@@ -605,10 +640,11 @@ __global__ void __launch_bounds__(kThreads) attn_delta_mfma_kernel(AttnArgs a) {
 }
 
 // ------------------------------------------------------------------ dQ
-// WINDOW: the forward's key-tile range and band mask (see attn_fwd_kernel).
-template <int D, bool CAUSAL, bool WINDOW = false, bool SOFTCAP = false>
+// WINDOW, DOCS: the forward's key-tile range and band / document mask (see attn_fwd_kernel).
+template <int D, bool CAUSAL, bool WINDOW = false, bool SOFTCAP = false, bool DOCS = false>
 __global__ void __launch_bounds__(kThreads, D == 256 ? 1 : 2) attn_dq_kernel(AttnArgs a) {
   static_assert(!WINDOW || CAUSAL, "the sliding window is a band of the causal mask");
+  static_assert(!DOCS || (CAUSAL && !WINDOW), "documents mask the causal triangle and merge the window at run time");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   char* kimg = smem;
   char* vimg = smem + Img<D>::kBytes;
@@ -647,8 +683,17 @@ __global__ void __launch_bounds__(kThreads, D == 256 ? 1 : 2) attn_dq_kernel(Att
   const float sl2 = a.scale * kLog2e;
   const float pscale = a.p > 0.f ? 1.f / (1.f - a.p) : 1.f;
   const int ntiles = CAUSAL ? qt + 1 : a.S / kRows;
-  const int tbeg = WINDOW ? max(0, q0 - a.window + 1) / kRows : 0;  // first tile with a key row q0 sees
+  const int tbeg = DOCS ? doc_tbeg(a, b, q0, qt)
+                        : (WINDOW ? max(0, q0 - a.window + 1) / kRows : 0);  // first tile with a key row q0 sees
   const int wrow0 = WINDOW ? qrow0 - a.window : 0;                  // row qrow0 + r sees keys > wrow0 + r
+  int dlo[4] = {0, 0, 0, 0};                                        // DOCS: row qrow0 + r sees keys >= dlo[r]
+  if constexpr (DOCS) {
+    const int4 st = doc_rows4(a.doc_start, a, b, qrow0);
+    dlo[0] = max(qrow0 - a.window + 1, st.x);
+    dlo[1] = max(qrow0 - a.window + 2, st.y);
+    dlo[2] = max(qrow0 - a.window + 3, st.z);
+    dlo[3] = max(qrow0 - a.window + 4, st.w);
+  }
   const float cap_in = SOFTCAP ? 2.f * sl2 / a.softcap : 0.f;       // as in attn_fwd_kernel
   const float cap_l2 = SOFTCAP ? a.softcap * kLog2e : 0.f;
 
@@ -704,6 +749,7 @@ __global__ void __launch_bounds__(kThreads, D == 256 ? 1 : 2) attn_dq_kernel(Att
         }
         if (CAUSAL && key > qrow0 + r) pr = 0.f;
         if (WINDOW && key <= wrow0 + r) pr = 0.f;
+        if (DOCS && key < dlo[r]) pr = 0.f;
         float dp = pacc[j][r];
         if (a.p > 0.f) dp = w[r] >= a.threshold ? dp * pscale : 0.f;
         ds[j][r] = pr * (dp - dl[r]);
@@ -866,9 +912,12 @@ __global__ void __launch_bounds__(kThreads, 2) attn_dq_wide_kernel(AttnArgs a) {
 // ------------------------------------------------------------------ dK, dV
 // WINDOW (only with CAUSAL): key j is seen by the queries [j, j + a.window), so the query-tile loop ends at the
 // tile of query k0 + 63 + a.window - 1 instead of at the sequence's last one.
-template <int D, bool CAUSAL, bool WINDOW = false, bool SOFTCAP = false>
+// DOCS (only with CAUSAL): key j is seen by the queries [j, hi(j)); the loop ends at the tile of hi(k0 + 63) - 1
+// and the mask is q >= hi(key).
+template <int D, bool CAUSAL, bool WINDOW = false, bool SOFTCAP = false, bool DOCS = false>
 __global__ void __launch_bounds__(kThreads, D >= 128 ? 1 : 2) attn_dkdv_kernel(AttnArgs a) {
   static_assert(!WINDOW || CAUSAL, "the sliding window is a band of the causal mask");
+  static_assert(!DOCS || (CAUSAL && !WINDOW), "documents mask the causal triangle and merge the window at run time");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   char* qimg = smem;
   char* dimg = smem + Img<D>::kBytes;
@@ -903,8 +952,17 @@ __global__ void __launch_bounds__(kThreads, D >= 128 ? 1 : 2) attn_dkdv_kernel(A
   const float pscale = a.p > 0.f ? 1.f / (1.f - a.p) : 1.f;
   const int first = CAUSAL ? kt : 0;
   // one past the last query tile: the loop end, computed once (the window is not read again)
-  const int nq = WINDOW ? min(a.S / kRows, (k0 + kRows - 1 + a.window - 1) / kRows + 1) : a.S / kRows;
+  const int nq = DOCS ? doc_nq(a, b, k0, kt)
+                      : (WINDOW ? min(a.S / kRows, (k0 + kRows - 1 + a.window - 1) / kRows + 1) : a.S / kRows);
   const int wkey0 = WINDOW ? key0 + a.window : 0;  // key key0 + r is seen by the queries < wkey0 + r
+  int dhi[4] = {0, 0, 0, 0};                       // DOCS: key key0 + r is seen by the queries < dhi[r]
+  if constexpr (DOCS) {
+    const int4 en = doc_rows4(a.doc_end, a, b, key0);
+    dhi[0] = min(key0 + a.window, en.x);
+    dhi[1] = min(key0 + 1 + a.window, en.y);
+    dhi[2] = min(key0 + 2 + a.window, en.z);
+    dhi[3] = min(key0 + 3 + a.window, en.w);
+  }
   const float cap_in = SOFTCAP ? 2.f * sl2 / a.softcap : 0.f;  // as in attn_fwd_kernel
   const float cap_l2 = SOFTCAP ? a.softcap * kLog2e : 0.f;
 
@@ -984,6 +1042,7 @@ __global__ void __launch_bounds__(kThreads, D >= 128 ? 1 : 2) attn_dkdv_kernel(A
         }
         if (CAUSAL && key > q) pr = 0.f;
         if (WINDOW && q >= wkey0 + r) pr = 0.f;
+        if (DOCS && q >= dhi[r]) pr = 0.f;
         float dp = pacc[j][r];
         float pdrop = pr;
         if (a.p > 0.f) {
@@ -1550,6 +1609,55 @@ void run_bwd_softcap(const AttnArgs& a, hipStream_t s) {
   hipLaunchKernelGGL((attn_dq_kernel<D, CAUSAL, WINDOW, true>), grid, dim3(kThreads), sm, s, a);
 }
 
+// Document masks (a.doc_start set, causal): always the generic 64-row kernels too, with or without a cap; the
+// window is merged at run time (a.window = S when there is none).  delta from attn_delta_mfma_kernel, as under a
+// window: a one-token document gives dS = 0 exactly.
+template <int D, bool SOFTCAP>
+void run_fwd_docs(const AttnArgs& a, hipStream_t s) {
+  const size_t sm = fwd_smem<D>();
+  static bool once = false;
+  if (!once) { set_smem(attn_fwd_kernel<D, true, false, SOFTCAP, true>, sm); once = true; }
+  hipLaunchKernelGGL((attn_fwd_kernel<D, true, false, SOFTCAP, true>), dim3(a.S / kRows, a.B * a.H), dim3(kThreads),
+                     sm, s, a);
+}
+
+template <int D, bool SOFTCAP>
+void run_bwd_docs(const AttnArgs& a, hipStream_t s) {
+  const size_t sm = fwd_smem<D>(), sm2 = dkdv_smem<D>();
+  static bool once = false;
+  if (!once) {
+    set_smem(attn_dq_kernel<D, true, false, SOFTCAP, true>, sm);
+    set_smem(attn_dkdv_kernel<D, true, false, SOFTCAP, true>, sm2);
+    once = true;
+  }
+  const dim3 grid(a.S / kRows, a.B * a.H);
+  hipLaunchKernelGGL((attn_delta_mfma_kernel<D>), grid, dim3(kThreads), 0, s, a);
+  hipLaunchKernelGGL((attn_dkdv_kernel<D, true, false, SOFTCAP, true>), grid, dim3(kThreads), sm2, s, a);
+  hipLaunchKernelGGL((attn_dq_kernel<D, true, false, SOFTCAP, true>), grid, dim3(kThreads), sm, s, a);
+}
+
+template <int D>
+void fwd_docs(const AttnArgs& a, hipStream_t s) {
+  if (a.softcap > 0.f) run_fwd_docs<D, true>(a, s);
+  else run_fwd_docs<D, false>(a, s);
+}
+
+template <int D>
+void bwd_docs(const AttnArgs& a, hipStream_t s) {
+  if (a.softcap > 0.f) run_bwd_docs<D, true>(a, s);
+  else run_bwd_docs<D, false>(a, s);
+}
+
+// Documents need the causal mask and both bounds; the kernels take "no window" as a window of S.
+bool normalise_docs(AttnArgs& a) {
+  if (a.doc_start == nullptr || a.doc_end == nullptr || !a.causal) {
+    a.doc_start = a.doc_end = nullptr;
+    return false;
+  }
+  if (a.window <= 0) a.window = a.S;
+  return true;
+}
+
 template <int D>
 void fwd_softcap(const AttnArgs& a, hipStream_t s) {
   if (a.window > 0) run_fwd_softcap<D, true, true>(a, s);
@@ -1574,6 +1682,12 @@ void attention_fwd(const AttnArgs& ai, hipStream_t s) {
   AttnArgs a = attn_resolved(ai);
   a.threshold = dropout_threshold(a.p);
   normalise_window(a);
+  if (normalise_docs(a)) {
+    if (a.D == 64) fwd_docs<64>(a, s);
+    else if (a.D == 128) fwd_docs<128>(a, s);
+    else fwd_docs<256>(a, s);
+    return;
+  }
   if (a.softcap > 0.f) {
     if (a.D == 64) fwd_softcap<64>(a, s);
     else if (a.D == 128) fwd_softcap<128>(a, s);
@@ -1601,6 +1715,12 @@ void attention_bwd(const AttnArgs& ai, hipStream_t s) {
   AttnArgs a = attn_resolved(ai);
   a.threshold = dropout_threshold(a.p);
   normalise_window(a);
+  if (normalise_docs(a)) {
+    if (a.D == 64) bwd_docs<64>(a, s);
+    else if (a.D == 128) bwd_docs<128>(a, s);
+    else bwd_docs<256>(a, s);
+    return;
+  }
   if (a.softcap > 0.f) {
     if (a.D == 64) bwd_softcap<64>(a, s);
     else if (a.D == 128) bwd_softcap<128>(a, s);

@@ -341,6 +341,12 @@ struct AttnArgs {
   // softcap) before the masks and the softmax; 0 = no cap, else a finite float > 0.  Appended after `window` for
   // the same reason.
   float softcap = 0.f;
+  // Document-masked attention (bf16 attention.hip's generic kernels, causal only): rows 0 and 1 of one int32
+  // [B, 2, S] tensor, so batch b's S entries start at doc_start / doc_end + b * 2 * S.  Query i sees the keys
+  // [doc_start[i], i] (and inside the window, if any); key j is seen by the queries [j, doc_end[j]).  Both are
+  // non-decreasing along a row.  nullptr = no documents.  Appended after `softcap` for the same reason.
+  const int32_t* doc_start = nullptr;
+  const int32_t* doc_end = nullptr;
 };
 // K / V head of query head h: h / group as a scalar multiply by ceil(2^20 / group) and a shift instead of a
 // division.  Exact for every h when group == 1 (the 64-bit product is h * 2^20) and while h * group < 2^20

@@ -238,6 +238,21 @@ class AttentionCore(nn.Module):
     def forward(self, x: Tensor) -> Tensor:
         return self.forward_fanout(x, fanout=False)[0]
 
+    def _documents(self, B: int, S: int) -> Optional[Tensor]:
+        """The calling thread's document bounds (``ops.use_documents``) for a ``[B, S, E]`` input, or None: a
+        packed batch's tokens attend inside their own document only.  No parameter or config field: without a
+        context nothing changes."""
+        docs = ops.current_documents()
+        if docs is None:
+            return None
+        if not self.causal:
+            raise ValueError("AttentionCore: document bounds are set (ops.use_documents) but this core is not "
+                             "causal; bidirectional document masks are not supported")
+        if tuple(docs.shape) != (B, 2, S):
+            raise ValueError(f"AttentionCore: document bounds {tuple(docs.shape)} do not match the input's "
+                             f"[B, 2, S] = [{B}, 2, {S}]")
+        return docs
+
     def forward_fanout(self, x: Tensor, fanout: bool = True):
         """``(o, x')``: ``x'`` is the block input for the residual branch.  With
         ``fanout`` the first consumer of ``x`` (LN1 for pre-norm, the QKV
@@ -245,6 +260,7 @@ class AttentionCore(nn.Module):
         added inside that op's backward kernel (no autograd add pass)."""
         B, S, _ = x.shape
         H, D, E = self.nhead, self.head_dim, self.attn_dim  # E: the width of o
+        docs = self._documents(B, S)
         xr = x
         if self.norm_first:
             if fanout:
@@ -267,10 +283,11 @@ class AttentionCore(nn.Module):
             if Hkv != H:
                 o = ops.attention_gqa_packed(qkv_n, Hkv, causal=self.causal, dropout_p=self.dropout,
                                              training=self.training, scale=self.attn_scale, window=self.window,
-                                             softcap=self.attn_softcap)
+                                             softcap=self.attn_softcap, doc_bounds=docs)
             else:
                 o = ops.attention_packed(qkv_n, causal=self.causal, dropout_p=self.dropout, training=self.training,
-                                         scale=self.attn_scale, window=self.window, softcap=self.attn_softcap)
+                                         scale=self.attn_scale, window=self.window, softcap=self.attn_softcap,
+                                         doc_bounds=docs)
             return o.reshape(B, S, E), xr
         if Hkv != H:
             # grouped-query attention: [B, S, H + 2 Hkv, D], the K/V heads read in place by every query head
@@ -282,7 +299,7 @@ class AttentionCore(nn.Module):
                 qkv4 = qkv.view(B, S, H + 2 * Hkv, D)
             o = ops.attention_gqa_packed(qkv4, Hkv, causal=self.causal, dropout_p=self.dropout,
                                          training=self.training, scale=self.attn_scale, window=self.window,
-                                         softcap=self.attn_softcap)
+                                         softcap=self.attn_softcap, doc_bounds=docs)
             return o.reshape(B, S, E), xr
         if self.rope:
             # Q and K rotated: in the projection's own output where no graph is recorded, else into a new tensor
@@ -291,10 +308,13 @@ class AttentionCore(nn.Module):
         else:
             qkv5 = qkv.view(B, S, 3, H, D)
         o = ops.attention_packed(qkv5, causal=self.causal, dropout_p=self.dropout, training=self.training,
-                                 scale=self.attn_scale, window=self.window, softcap=self.attn_softcap)
+                                 scale=self.attn_scale, window=self.window, softcap=self.attn_softcap,
+                                 doc_bounds=docs)
         return o.reshape(B, S, E), xr
 
     def flops_per_token(self, seq_len: int) -> float:
+        """Document bounds (``ops.use_documents``) are per batch and not known here: a packed row is priced as
+        causal, an upper bound on what the kernels run (so is ``block_costs``, which sums these)."""
         e = self.d_model
         # mean number of keys a query sees: all, half of them under the causal mask (the kernels skip the tiles
         # above the diagonal), and under a window w < seq_len the first w rows' 1 .. w and w for every later row

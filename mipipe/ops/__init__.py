@@ -9,7 +9,8 @@ from .layernorm import add_dropout_layer_norm, layer_norm_fanout, layer_norm_ref
 from .rmsnorm import (add_dropout_rms_norm, rms_norm_fanout, rms_norm_reference, rms_norm_residual,
                       rms_norm_residual_reference)
 from .linear import deferred_wgrad, flush_wgrad, linear, linear_fanout, linear_residual
-from .attention import attention, attention_gqa_packed, attention_packed, attention_reference
+from .attention import (attention, attention_gqa_packed, attention_packed, attention_reference, check_doc_bounds,
+                        current_documents, use_documents)
 from .activation import bias_act_dropout
 from .softcap import softcap, softcap_owned, softcap_reference
 from .swiglu import swiglu, swiglu_reference
@@ -37,6 +38,9 @@ __all__ = [
     "attention_packed",
     "attention_gqa_packed",
     "attention_reference",
+    "check_doc_bounds",
+    "use_documents",
+    "current_documents",
     "bias_act_dropout",
     "softcap",
     "softcap_owned",

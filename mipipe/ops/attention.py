@@ -63,6 +63,19 @@ back to ``-c``, so that shape, fp32 and the CPU use :func:`attention_reference`.
 The kernels take ``tanh`` as ``1 - 2 / (1 + exp2(.))`` in fp32: its absolute
 error of about 2e-7 is an error of about ``c * 2e-7`` in the capped score, so
 it grows with ``c`` (nothing at 30 or 50; 1e-3 in the exponent at 5000).
+
+Document masks (packed sequences): every entry point takes a keyword-only ``doc_bounds`` -- int32 ``[B, 2, S]``,
+``[b, 0, i]`` the index of the first token of token ``i``'s document and ``[b, 1, i]`` one past its last
+(``utils.data.document_bounds``), with ``causal=True``: query ``i`` attends key ``j`` iff ``start[i] <= j <= i``
+(and ``j > i - W`` under a window).  ``None`` is the code path it always was.  A bf16 call on the GPU runs
+attention.hip's generic kernels with the window merged at run time; they skip the key tiles before a query
+tile's first document and the query tiles after a key tile's last one, grouped-query heads are read in place
+and the dropout mask is the causal call's restricted to the visible keys.  Causal end padding and head-dim
+padding stay native (the pad tokens become one trailing document); fp32, the CPU and the shapes that cannot be
+padded use :func:`attention_reference` with the document mask.  The contract on the values (``start[i] <= i <
+end[i]``, both rows non-decreasing) is the caller's: :func:`check_doc_bounds` validates it on the host, with a
+sync, and is never called on the hot path; the kernels clamp the loop bounds they take from the tensor.
+:func:`use_documents` sets the bounds for the calling thread (``AttentionCore`` reads them).
 """
 from __future__ import annotations
 
@@ -70,6 +83,7 @@ import math
 import os
 import threading
 from collections import OrderedDict
+from contextlib import contextmanager
 from typing import Optional, Tuple
 
 import torch
@@ -79,7 +93,8 @@ from torch import Tensor
 from ..checkpoint import is_recomputing, recompute_expected
 from ._util import kernels_for
 
-__all__ = ["attention", "attention_packed", "attention_gqa_packed", "attention_reference", "clear_keep_words"]
+__all__ = ["attention", "attention_packed", "attention_gqa_packed", "attention_reference", "clear_keep_words",
+           "check_doc_bounds", "use_documents", "current_documents"]
 
 
 def _check_window(window: Optional[int], causal: bool, S: int) -> Optional[int]:
@@ -106,15 +121,72 @@ def _check_softcap(softcap: Optional[float]) -> Optional[float]:
     return float(softcap)
 
 
+def _check_docs(doc_bounds: Optional[Tensor], causal: bool, B: int, S: int) -> Optional[Tensor]:
+    """``doc_bounds`` validated by what the host knows without a sync: causal only, int32, ``[B, 2, S]``."""
+    if doc_bounds is None:
+        return None
+    if not causal:
+        raise ValueError("attention: doc_bounds needs causal=True (bidirectional document masks are not supported)")
+    if not isinstance(doc_bounds, Tensor) or doc_bounds.dtype != torch.int32:
+        raise ValueError("attention: doc_bounds must be an int32 tensor, got "
+                         f"{getattr(doc_bounds, 'dtype', doc_bounds)!r}")
+    if tuple(doc_bounds.shape) != (B, 2, S):
+        raise ValueError(f"attention: doc_bounds must be [B, 2, S] = [{B}, 2, {S}], got {tuple(doc_bounds.shape)}")
+    return doc_bounds
+
+
+def check_doc_bounds(bounds: Tensor) -> None:
+    """Validates a ``doc_bounds`` tensor's contract on the host: int32 ``[B, 2, S]``, ``start[i] <= i < end[i]
+    <= S``, ``start >= 0`` and both rows non-decreasing.  It reads the values (a device sync): an explicit call
+    for data pipelines and tests, never made by the ops."""
+    if not isinstance(bounds, Tensor) or bounds.dtype != torch.int32 or bounds.dim() != 3 or bounds.shape[1] != 2:
+        raise ValueError("check_doc_bounds: bounds must be an int32 tensor [B, 2, S]")
+    S = bounds.shape[2]
+    start, end = bounds[:, 0].long(), bounds[:, 1].long()
+    idx = torch.arange(S, device=bounds.device)
+    ok = (start >= 0) & (start <= idx) & (idx < end) & (end <= S)
+    if not bool(ok.all()):
+        raise ValueError("check_doc_bounds: need 0 <= start[i] <= i < end[i] <= S for every token")
+    if S > 1 and not bool(((start[:, 1:] >= start[:, :-1]) & (end[:, 1:] >= end[:, :-1])).all()):
+        raise ValueError("check_doc_bounds: start and end must be non-decreasing along a row")
+    # constant on a document: every token of [start[i], end[i]) carries the same pair
+    if not bool(((start.gather(1, end - 1) == start) & (end.gather(1, start) == end)).all()):
+        raise ValueError("check_doc_bounds: start and end must be constant on a document")
+
+
+_documents = threading.local()
+
+
+def current_documents() -> Optional[Tensor]:
+    """The ``doc_bounds`` :func:`use_documents` set for the calling thread, or None."""
+    return getattr(_documents, "bounds", None)
+
+
+@contextmanager
+def use_documents(bounds: Optional[Tensor]):
+    """Sets ``bounds`` (int32 ``[B, 2, S]``, or None) as the calling thread's document bounds for the block:
+    every causal ``AttentionCore`` that runs inside passes them to its attention op.  Thread-local, so worker
+    threads started inside do not see it."""
+    prev = current_documents()
+    _documents.bounds = bounds
+    try:
+        yield bounds
+    finally:
+        _documents.bounds = prev
+
+
 def attention_reference(q: Tensor, k: Tensor, v: Tensor, causal: bool, p: float, scale: Optional[float] = None,
-                        *, window: Optional[int] = None, softcap: Optional[float] = None) -> Tensor:
+                        *, window: Optional[int] = None, softcap: Optional[float] = None,
+                        doc_bounds: Optional[Tensor] = None) -> Tensor:
     """Eager fp32 math on ``[B, H, S, D]`` (CPU path and test oracle).  ``window``: query ``i`` sees the keys
     ``i - window < j <= i`` only.  ``softcap``: the scaled scores become ``softcap * tanh(s / softcap)`` before
-    the masks."""
+    the masks.  ``doc_bounds`` (int32 ``[B, 2, S]``): query ``i`` sees the keys ``j >= doc_bounds[b, 0, i]``
+    only."""
     d = q.shape[-1]
     scale = scale if scale is not None else 1.0 / math.sqrt(d)
     window = _check_window(window, bool(causal), q.shape[-2])
     softcap = _check_softcap(softcap)
+    docs = _check_docs(doc_bounds, bool(causal), q.shape[0], q.shape[-2])
     s = torch.matmul(q.float(), k.float().transpose(-1, -2)) * scale
     if softcap is not None:
         s = softcap * torch.tanh(s / softcap)
@@ -124,6 +196,10 @@ def attention_reference(q: Tensor, k: Tensor, v: Tensor, causal: bool, p: float,
         if window is not None:  # keys at or below the band's lower edge: j <= i - window
             mask |= torch.ones(n, m, dtype=torch.bool, device=s.device).tril(m - n - window)
         s = s.masked_fill(mask, float("-inf"))
+        if docs is not None:  # keys before the query's document: j < start[b, i]
+            start = docs[:, 0].to(s.device)
+            keys = torch.arange(m, device=s.device)
+            s = s.masked_fill((keys[None, None, :] < start[:, :, None])[:, None], float("-inf"))
     pr = torch.softmax(s, dim=-1)
     if p > 0:
         pr = F.dropout(pr, p, True)
@@ -166,8 +242,10 @@ def clear_keep_words() -> None:
         _keep_bytes = 0
 
 
-def _attention_fwd(kern, q, k, v, causal, p, scale, kv_len, window=0, softcap=0.0):
+def _attention_fwd(kern, q, k, v, causal, p, scale, kv_len, window=0, softcap=0.0, docs=None):
     global _keep_bytes
+    if docs is not None:  # the generic kernels, as below
+        return kern.attention_fwd(q, k, v, causal, p, scale, kv_len, None, 0, 0, window, softcap, docs)
     if window or softcap:  # the generic kernels: the mask is regenerated from Philox, there are no keep words
         return kern.attention_fwd(q, k, v, causal, p, scale, kv_len, None, 0, 0, window, softcap)
     reuse = _KEEP_REUSE and p > 0 and q.is_cuda and q.dtype == torch.bfloat16 and kv_len == 0
@@ -201,50 +279,50 @@ class _AttentionPacked(torch.autograd.Function):
     backward produces the packed ``dqkv`` in one buffer."""
 
     @staticmethod
-    def forward(ctx, qkv, causal, p, scale, kv_len=0, window=0, softcap=0.0):  # type: ignore[override]
+    def forward(ctx, qkv, causal, p, scale, kv_len=0, window=0, softcap=0.0, docs=None):  # type: ignore[override]
         kern = kernels_for(qkv)
         q, k, v = qkv.select(2, 0), qkv.select(2, 1), qkv.select(2, 2)
-        o, lse, seed, offset, bits = _attention_fwd(kern, q, k, v, causal, p, scale, kv_len, window, softcap)
-        ctx.save_for_backward(qkv, o, lse, bits)
+        o, lse, seed, offset, bits = _attention_fwd(kern, q, k, v, causal, p, scale, kv_len, window, softcap, docs)
+        ctx.save_for_backward(qkv, o, lse, bits, docs)
         ctx.causal, ctx.p, ctx.scale, ctx.seed, ctx.offset, ctx.kv_len = causal, p, scale, seed, offset, kv_len
         ctx.window, ctx.softcap = window, softcap
         return o
 
     @staticmethod
     def backward(ctx, do):  # type: ignore[override]
-        qkv, o, lse, bits = ctx.saved_tensors
+        qkv, o, lse, bits, docs = ctx.saved_tensors
         kern = kernels_for(do)
         if do.stride() != o.stride():
             do = do.contiguous()
         dqkv = torch.empty_like(qkv)
         kern.attention_bwd(do, qkv.select(2, 0), qkv.select(2, 1), qkv.select(2, 2), o, lse, ctx.causal, ctx.p,
                            ctx.scale, ctx.seed, ctx.offset, dqkv.select(2, 0), dqkv.select(2, 1), dqkv.select(2, 2),
-                           bits if bits.numel() else None, ctx.kv_len, ctx.window, ctx.softcap)
-        return dqkv, None, None, None, None, None, None
+                           bits if bits.numel() else None, ctx.kv_len, ctx.window, ctx.softcap, docs)
+        return dqkv, None, None, None, None, None, None, None
 
 
 class _Attention(torch.autograd.Function):
     """Separate q, k, v as [B, S, H, D] views sharing one layout."""
 
     @staticmethod
-    def forward(ctx, q, k, v, causal, p, scale, kv_len=0, window=0, softcap=0.0):  # type: ignore[override]
+    def forward(ctx, q, k, v, causal, p, scale, kv_len=0, window=0, softcap=0.0, docs=None):  # type: ignore[override]
         kern = kernels_for(q)
-        o, lse, seed, offset, bits = _attention_fwd(kern, q, k, v, causal, p, scale, kv_len, window, softcap)
-        ctx.save_for_backward(q, k, v, o, lse, bits)
+        o, lse, seed, offset, bits = _attention_fwd(kern, q, k, v, causal, p, scale, kv_len, window, softcap, docs)
+        ctx.save_for_backward(q, k, v, o, lse, bits, docs)
         ctx.causal, ctx.p, ctx.scale, ctx.seed, ctx.offset, ctx.kv_len = causal, p, scale, seed, offset, kv_len
         ctx.window, ctx.softcap = window, softcap
         return o
 
     @staticmethod
     def backward(ctx, do):  # type: ignore[override]
-        q, k, v, o, lse, bits = ctx.saved_tensors
+        q, k, v, o, lse, bits, docs = ctx.saved_tensors
         kern = kernels_for(do)
         if do.stride() != o.stride():
             do = do.contiguous()
         dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
         kern.attention_bwd(do, q, k, v, o, lse, ctx.causal, ctx.p, ctx.scale, ctx.seed, ctx.offset, dq, dk, dv,
-                           bits if bits.numel() else None, ctx.kv_len, ctx.window, ctx.softcap)
-        return dq, dk, dv, None, None, None, None, None, None
+                           bits if bits.numel() else None, ctx.kv_len, ctx.window, ctx.softcap, docs)
+        return dq, dk, dv, None, None, None, None, None, None, None
 
 
 class _AttentionGqaPacked(torch.autograd.Function):
@@ -253,19 +331,19 @@ class _AttentionGqaPacked(torch.autograd.Function):
     dK / dV into one packed ``dqkv`` of the same layout (the binding owns the per-query-head scratch)."""
 
     @staticmethod
-    def forward(ctx, qkv, n_kv, causal, p, scale, window=0, softcap=0.0):  # type: ignore[override]
+    def forward(ctx, qkv, n_kv, causal, p, scale, window=0, softcap=0.0, docs=None):  # type: ignore[override]
         kern = kernels_for(qkv)
         H = qkv.shape[2] - 2 * n_kv
         q, k, v = qkv[:, :, :H], qkv[:, :, H:H + n_kv], qkv[:, :, H + n_kv:]
-        o, lse, seed, offset, bits = _attention_fwd(kern, q, k, v, causal, p, scale, 0, window, softcap)
-        ctx.save_for_backward(qkv, o, lse, bits)
+        o, lse, seed, offset, bits = _attention_fwd(kern, q, k, v, causal, p, scale, 0, window, softcap, docs)
+        ctx.save_for_backward(qkv, o, lse, bits, docs)
         ctx.n_kv, ctx.causal, ctx.p, ctx.scale, ctx.seed, ctx.offset = n_kv, causal, p, scale, seed, offset
         ctx.window, ctx.softcap = window, softcap
         return o
 
     @staticmethod
     def backward(ctx, do):  # type: ignore[override]
-        qkv, o, lse, bits = ctx.saved_tensors
+        qkv, o, lse, bits, docs = ctx.saved_tensors
         kern = kernels_for(do)
         if do.stride() != o.stride():
             do = do.contiguous()
@@ -274,18 +352,21 @@ class _AttentionGqaPacked(torch.autograd.Function):
         dqkv = torch.empty_like(qkv)
         kern.attention_bwd(do, qkv[:, :, :H], qkv[:, :, H:H + n_kv], qkv[:, :, H + n_kv:], o, lse, ctx.causal, ctx.p,
                            ctx.scale, ctx.seed, ctx.offset, dqkv[:, :, :H], dqkv[:, :, H:H + n_kv],
-                           dqkv[:, :, H + n_kv:], bits if bits.numel() else None, 0, ctx.window, ctx.softcap)
-        return dqkv, None, None, None, None, None, None
+                           dqkv[:, :, H + n_kv:], bits if bits.numel() else None, 0, ctx.window, ctx.softcap, docs)
+        return dqkv, None, None, None, None, None, None, None
 
 
 _noted = set()
 
 
-def _note_math_path(S: int, D: int, dtype, window: Optional[int] = None, softcap: Optional[float] = None) -> None:
+def _note_math_path(S: int, D: int, dtype, window: Optional[int] = None, softcap: Optional[float] = None,
+                    docs: bool = False) -> None:
     """Shapes outside the kernels' tiling use the eager math path; say so once per shape."""
     key = (S, D, dtype) if window is None else (S, D, dtype, "window")
     if softcap is not None:
         key += ("softcap",)
+    if docs:
+        key += ("documents",)
     if key not in _noted:
         _noted.add(key)
         import warnings
@@ -296,6 +377,9 @@ def _note_math_path(S: int, D: int, dtype, window: Optional[int] = None, softcap
             extra += f" softcap={softcap}"
             tail += (".  Soft-capped attention is native in bf16 only, and not for a non-causal sequence of an "
                      "unsupported length")
+        if docs:
+            extra += " doc_bounds"
+            tail += ".  Document-masked attention is native in bf16 only"
         warnings.warn(f"mipipe attention: S={S} D={D} {dtype}{extra} runs the eager math path (HIP kernels: bf16 "
                       "with S % 64 == 0, D in {64, 128, 256}; fp32 with S % 32 == 0, D in {64, 128})" + tail,
                       stacklevel=3)
@@ -370,38 +454,54 @@ def _generic_shape(t: Tensor, S: int, D: int, causal: bool, scale: float) -> Opt
     return run[0], run[1]
 
 
+def _pad_docs(docs: Tensor, S: int, sp: int) -> Tensor:
+    """``docs [B, 2, S]`` for a sequence end-padded to ``sp``: the pad tokens ``[S, sp)`` are one trailing
+    document (no real query sees them under the causal mask anyway).  Tensor ops only, no sync."""
+    if sp == S:
+        return docs.contiguous()
+    out = docs.new_empty(docs.shape[0], 2, sp)
+    out[:, :, :S] = docs
+    out[:, 0, S:] = S
+    out[:, 1, S:] = sp
+    return out
+
+
 def _packed_generic(qkv: Tensor, S: int, D: int, causal: bool, p: float, scale: float, window: Optional[int],
-                    softcap: Optional[float]) -> Tensor:
-    """:func:`attention_packed` with a window ``< S`` (causal) and / or a soft cap."""
+                    softcap: Optional[float], docs: Optional[Tensor] = None) -> Tensor:
+    """:func:`attention_packed` with a window ``< S`` (causal), a soft cap and / or document bounds."""
     if _window_native(qkv):
         run = _generic_shape(qkv, S, D, causal, scale)
+        if docs is not None and run is not None:
+            docs = _pad_docs(docs.to(qkv.device), S, run[0])
         if run == (S, D):
-            return _AttentionPacked.apply(qkv.contiguous(), causal, p, scale, 0, window or 0, softcap or 0.0)
+            return _AttentionPacked.apply(qkv.contiguous(), causal, p, scale, 0, window or 0, softcap or 0.0, docs)
         if run is not None:  # bf16: end padding (causal) and feature padding only (no key bound)
             sp, dp = run
             padded = F.pad(qkv, (0, dp - D, 0, 0, 0, 0, 0, sp - S))
-            return _AttentionPacked.apply(padded, causal, p, scale, 0, window or 0, softcap or 0.0)[:, :S, :, :D]
+            return _AttentionPacked.apply(padded, causal, p, scale, 0, window or 0, softcap or 0.0,
+                                          docs)[:, :S, :, :D]
     q, k, v = qkv.select(2, 0), qkv.select(2, 1), qkv.select(2, 2)
     if qkv.is_cuda:
-        _note_math_path(S, D, qkv.dtype, window, softcap)
+        _note_math_path(S, D, qkv.dtype, window, softcap, docs is not None)
     o = attention_reference(q.transpose(1, 2), k.transpose(1, 2), v.transpose(1, 2), causal, p, scale, window=window,
-                            softcap=softcap)
+                            softcap=softcap, doc_bounds=docs)
     return o.transpose(1, 2)
 
 
 def attention_packed(qkv: Tensor, causal: bool = False, dropout_p: float = 0.0, training: bool = True,
                      scale: Optional[float] = None, *, window: Optional[int] = None,
-                     softcap: Optional[float] = None) -> Tensor:
+                     softcap: Optional[float] = None, doc_bounds: Optional[Tensor] = None) -> Tensor:
     """``qkv [B, S, 3, H, D]`` -> ``o [B, S, H, D]``.  ``window``: sliding-window attention, ``softcap``: logit
-    soft-capping (module doc)."""
+    soft-capping, ``doc_bounds``: document masks (module doc)."""
     B, S, three, H, D = qkv.shape
     assert three == 3
     p = float(dropout_p) if training else 0.0
     scale = float(scale) if scale is not None else 1.0 / math.sqrt(D)
     window = _check_window(window, bool(causal), S)
     softcap = _check_softcap(softcap)
-    if window is not None or softcap is not None:
-        return _packed_generic(qkv, S, D, bool(causal), p, scale, window, softcap)
+    docs = _check_docs(doc_bounds, bool(causal), B, S)
+    if window is not None or softcap is not None or docs is not None:
+        return _packed_generic(qkv, S, D, bool(causal), p, scale, window, softcap, docs)
     if qkv.is_cuda and _gpu_ok(qkv, S, D):
         return _AttentionPacked.apply(qkv.contiguous(), bool(causal), p, scale)
     run = _run_shape(qkv, S, D, bool(causal), scale) if qkv.is_cuda else None
@@ -438,9 +538,11 @@ def _expand_kv(qkv: Tensor, n_kv: int) -> Tensor:
 
 def attention_gqa_packed(qkv: Tensor, n_kv_heads: int, causal: bool = False, dropout_p: float = 0.0,
                          training: bool = True, scale: Optional[float] = None, *,
-                         window: Optional[int] = None, softcap: Optional[float] = None) -> Tensor:
+                         window: Optional[int] = None, softcap: Optional[float] = None,
+                         doc_bounds: Optional[Tensor] = None) -> Tensor:
     """``qkv [B, S, H + 2 Hkv, D]`` -> ``o [B, S, H, D]`` (grouped-query attention, ``Hkv = n_kv_heads``).
-    ``window``: sliding-window attention, ``softcap``: logit soft-capping (module doc)."""
+    ``window``: sliding-window attention, ``softcap``: logit soft-capping, ``doc_bounds``: document masks
+    (module doc)."""
     if qkv.dim() != 4:
         raise ValueError(f"attention_gqa_packed: qkv must be [B, S, H + 2 Hkv, D], got {tuple(qkv.shape)}")
     B, S, heads, D = qkv.shape
@@ -451,26 +553,31 @@ def attention_gqa_packed(qkv: Tensor, n_kv_heads: int, causal: bool = False, dro
                          f"{n_kv} dividing H")
     window = _check_window(window, bool(causal), S)
     softcap = _check_softcap(softcap)
+    docs = _check_docs(doc_bounds, bool(causal), B, S)
     if n_kv == H:  # plain multi-head attention: the same bytes as [B, S, 3, H, D]
         return attention_packed(qkv.reshape(B, S, 3, H, D), causal, dropout_p, training, scale, window=window,
-                                softcap=softcap)
+                                softcap=softcap, doc_bounds=docs)
     if qkv.is_cuda and qkv.dtype == torch.bfloat16 and _gpu_ok(qkv, S, D):
         p = float(dropout_p) if training else 0.0
         scale = float(scale) if scale is not None else 1.0 / math.sqrt(D)
+        if docs is not None:
+            return _AttentionGqaPacked.apply(qkv.contiguous(), n_kv, bool(causal), p, scale, window or 0,
+                                             softcap or 0.0, docs.to(qkv.device).contiguous())
         return _AttentionGqaPacked.apply(qkv.contiguous(), n_kv, bool(causal), p, scale, window or 0,
                                          softcap or 0.0)
     return attention_packed(_expand_kv(qkv, n_kv), causal, dropout_p, training, scale, window=window,
-                            softcap=softcap)
+                            softcap=softcap, doc_bounds=docs)
 
 
 def attention(
     q: Tensor, k: Tensor, v: Tensor, causal: bool = False, dropout_p: float = 0.0, training: bool = True,
     scale: Optional[float] = None, *, window: Optional[int] = None, softcap: Optional[float] = None,
+    doc_bounds: Optional[Tensor] = None,
 ) -> Tensor:
     """``q, k, v [B, H, S, D]`` -> ``[B, H, S, D]``.  ``k`` and ``v`` may have fewer heads, ``Hkv | H``
     (grouped-query attention): separate tensors do not share q's strides, so their heads are repeated
     (autograd sums each group's gradient).  ``window``: sliding-window attention, ``softcap``: logit
-    soft-capping (module doc)."""
+    soft-capping, ``doc_bounds``: document masks (module doc)."""
     if k.shape[1] != q.shape[1]:
         if k.shape[1] != v.shape[1] or k.shape[1] <= 0 or q.shape[1] % k.shape[1] != 0:
             raise ValueError(f"attention: {k.shape[1]} / {v.shape[1]} K/V heads do not divide {q.shape[1]} query heads")
@@ -480,21 +587,24 @@ def attention(
     scale = float(scale) if scale is not None else 1.0 / math.sqrt(q.shape[-1])
     window = _check_window(window, bool(causal), q.shape[2])
     softcap = _check_softcap(softcap)
+    docs = _check_docs(doc_bounds, bool(causal), q.shape[0], q.shape[2])
     if not q.is_cuda:
-        return attention_reference(q, k, v, causal, p, scale, window=window, softcap=softcap)
+        return attention_reference(q, k, v, causal, p, scale, window=window, softcap=softcap, doc_bounds=docs)
     S, D = q.shape[2], q.shape[3]
-    if window is not None or softcap is not None:
+    if window is not None or softcap is not None or docs is not None:
         causal = bool(causal)
         run = _generic_shape(q, S, D, causal, scale) if _window_native(q) else None
         if run is None:
-            _note_math_path(S, D, q.dtype, window, softcap)
-            return attention_reference(q, k, v, causal, p, scale, window=window, softcap=softcap)
+            _note_math_path(S, D, q.dtype, window, softcap, docs is not None)
+            return attention_reference(q, k, v, causal, p, scale, window=window, softcap=softcap, doc_bounds=docs)
         sp, dp = run  # bf16: end padding (causal) and feature padding only (no key bound)
+        if docs is not None:
+            docs = _pad_docs(docs.to(q.device), S, sp)
         pad = (lambda t: F.pad(t, (0, dp - D, 0, sp - S))) if (sp, dp) != (S, D) else (lambda t: t)  # noqa: E731
         qs, ks, vs = (pad(t).transpose(1, 2) for t in (q, k, v))
         if not (qs.stride() == ks.stride() == vs.stride()) or qs.stride(3) != 1:
             qs, ks, vs = (t.contiguous() for t in (qs, ks, vs))
-        o = _Attention.apply(qs, ks, vs, causal, p, scale, 0, window or 0, softcap or 0.0)
+        o = _Attention.apply(qs, ks, vs, causal, p, scale, 0, window or 0, softcap or 0.0, docs)
         return o.transpose(1, 2)[:, :, :S, :D]
     if not _gpu_ok(q, S, D):
         run = _run_shape(q, S, D, bool(causal), scale)

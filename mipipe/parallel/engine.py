@@ -369,8 +369,14 @@ class PipelineEngine:
         return torch.empty(self.act_shapes[c], dtype=self.act_dtype, device=self.device)
 
     @staticmethod
-    def _run(mod: nn.Module, x: Tensor, targets, i: int, tracker: Optional[EngineSkipTracker] = None) -> Tensor:
-        """Chunk forward; chunks that want the targets (vocabulary-split decoder) get them."""
+    def _run(mod: nn.Module, x: Tensor, targets, i: int, tracker: Optional[EngineSkipTracker] = None,
+             docs=None) -> Tensor:
+        """Chunk forward; chunks that want the targets (vocabulary-split decoder) get them.  ``docs``: the
+        step's per-micro-batch document bounds, set around the chunk for its causal attention cores
+        (``ops.use_documents``) -- the first forward and the checkpoint recompute alike."""
+        if docs is not None:
+            with ops.use_documents(docs[i]):
+                return PipelineEngine._run(mod, x, targets, i, tracker)
         if tracker is not None:
             with use_skip_tracker(tracker):
                 return PipelineEngine._run(mod, x, targets, i)
@@ -404,8 +410,14 @@ class PipelineEngine:
         return torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
 
     # ------------------------------------------------------------------ step
-    def step(self, inputs: Optional[Sequence[Tensor]] = None, targets: Optional[Sequence[Tensor]] = None) -> StepStats:
+    def step(self, inputs: Optional[Sequence[Tensor]] = None, targets: Optional[Sequence[Tensor]] = None, *,
+             doc_bounds: Optional[Sequence[Tensor]] = None) -> StepStats:
         """Forward + backward of one mini-batch given as per-micro-batch lists.
+
+        ``doc_bounds`` (packed sequences): ``chunks`` int32 ``[mb, 2, S]`` tensors
+        (``utils.data.document_bounds``), passed on EVERY rank -- each stage's
+        causal attention cores mask across documents.  ``None`` leaves the step
+        as it is.
 
         Every action is a roctx range (``F vs<s> mb<i>``, ``B ...``,
         ``recompute ...``, ``wait recv act/grad ...``, ``post recvs``, ``wgrad
@@ -414,9 +426,10 @@ class PipelineEngine:
         rank and micro-batch (``tools/engine_timeline.py``).
         """
         with label_range("engine step"):
-            return self._step(inputs, targets)
+            return self._step(inputs, targets, doc_bounds)
 
-    def _step(self, inputs: Optional[Sequence[Tensor]] = None, targets: Optional[Sequence[Tensor]] = None) -> StepStats:
+    def _step(self, inputs: Optional[Sequence[Tensor]] = None, targets: Optional[Sequence[Tensor]] = None,
+              docs: Optional[Sequence[Tensor]] = None) -> StepStats:
         """Forward + backward of one mini-batch given as per-micro-batch lists.
 
         ``inputs`` (rank owning virtual stage 0) and ``targets`` (rank owning
@@ -426,6 +439,8 @@ class PipelineEngine:
         optimizer.  Returns the mean loss on the last stage.
         """
         m, v, n = self.chunks, self.virtual, self.world
+        if docs is not None and len(docs) != m:
+            raise ValueError(f"doc_bounds must hold one tensor per micro-batch ({m}), got {len(docs)}")
         training = self.modules[0].training and torch.is_grad_enabled()
         stop = checkpoint_stop_for(self.checkpoint, m) if self.modules[0].training else 0
         stats = StepStats()
@@ -547,9 +562,9 @@ class PipelineEngine:
             if training and i < stop:
                 rng[c][i] = _RNGState(self.device)
                 with torch.no_grad(), enable_checkpointing():
-                    y = self._run(mod, x, targets, i, tracker)
+                    y = self._run(mod, x, targets, i, tracker, docs)
             else:
-                y = self._run(mod, x, targets, i, tracker)
+                y = self._run(mod, x, targets, i, tracker, docs)
             if last and (self.loss_fn is not None or getattr(mod, "fused_loss", False)):
                 loss = self._loss(mod, y, targets, i)
                 losses.append(loss.detach())
@@ -600,7 +615,7 @@ class PipelineEngine:
                     if st.dev is not None:
                         torch.cuda.set_rng_state(st.dev, self.device)
                     with torch.enable_grad(), enable_recomputing():
-                        y = self._run(mod, x, targets, i, tracker)
+                        y = self._run(mod, x, targets, i, tracker, docs)
                         if last and (self.loss_fn is not None or getattr(mod, "fused_loss", False)):
                             y = self._loss(mod, y, targets, i)
                 if tracker is not None:

@@ -29,6 +29,9 @@ __all__ = [
     "iter_batches",
     "synthetic_corpus",
     "read_lines",
+    "document_bounds",
+    "document_bounds_from_lengths",
+    "mask_boundary_targets",
     "WIKITEXT2_VOCAB",
 ]
 
@@ -144,3 +147,52 @@ def synthetic_corpus(num_tokens: int, vocab_size: int = WIKITEXT2_VOCAB, seed: i
     probs = 1.0 / ranks
     probs /= probs.sum()
     return torch.multinomial(probs, num_tokens, replacement=True, generator=g)
+
+
+# ---------------------------------------------------------------- packed sequences
+# A packed row holds several documents; ``ops.attention(..., doc_bounds=...)`` keeps a token from attending
+# across them.  One int32 tensor ``[B, 2, S]`` describes a batch: ``[b, 0, i]`` is the index of the first token
+# of token i's document, ``[b, 1, i]`` one past its last (``start[i] <= i < end[i]``, both non-decreasing and
+# constant on a document).
+
+
+def document_bounds(tokens: Tensor, eos_id: int) -> Tensor:
+    """``tokens [B, S]`` -> int32 bounds ``[B, 2, S]``.  A document ends at and includes its EOS token and the
+    next one starts after it; a row's first and last documents are cut by the row.  Tensor ops only (a cummax
+    and a flipped cummin), on the tokens' device, without a host sync."""
+    if tokens.dim() != 2:
+        raise ValueError(f"document_bounds: tokens must be [B, S], got {tuple(tokens.shape)}")
+    B, S = tokens.shape
+    idx = torch.arange(S, device=tokens.device).expand(B, S)
+    eos = tokens == eos_id
+    first = torch.ones_like(eos)
+    first[:, 1:] = eos[:, :-1]          # token i opens a document: i == 0 or token i - 1 is an EOS
+    last = eos.clone()
+    last[:, S - 1:] = True              # token i closes one: an EOS or the row's end
+    start = torch.where(first, idx, torch.zeros_like(idx)).cummax(dim=1).values
+    end = torch.where(last, idx + 1, torch.full_like(idx, S)).flip(1).cummin(dim=1).values.flip(1)
+    return torch.stack((start, end), dim=1).to(torch.int32).contiguous()
+
+
+def document_bounds_from_lengths(lengths, S: int, device: Optional[torch.device] = None) -> Tensor:
+    """Bounds ``[B, 2, S]`` from document lengths: one list of ints (B = 1) or a list of B lists, each summing
+    to ``S``.  For tests and callers that know the lengths."""
+    rows = [lengths] if len(lengths) == 0 or isinstance(lengths[0], int) else lengths
+    out = torch.empty(len(rows), 2, S, dtype=torch.int32)
+    for b, row in enumerate(rows):
+        if any(n < 1 for n in row) or sum(row) != S:
+            raise ValueError(f"document_bounds_from_lengths: lengths {list(row)} must be >= 1 and sum to S={S}")
+        at = 0
+        for n in row:
+            out[b, 0, at:at + n] = at
+            out[b, 1, at:at + n] = at + n
+            at += n
+    return out.to(device) if device is not None else out
+
+
+def mask_boundary_targets(targets: Tensor, tokens: Tensor, eos_id: int, ignore_index: int = -100) -> Tensor:
+    """Next-token ``targets`` with the target of each document's last token (an EOS in ``tokens``, whose next
+    token opens another document) set to the loss's ``ignore_index``.  ``targets`` may be ``tokens``' shape or
+    flat in the same order; no host sync."""
+    eos = (tokens == eos_id).reshape(targets.shape)
+    return targets.masked_fill(eos, ignore_index)
