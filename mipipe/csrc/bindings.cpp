@@ -1539,6 +1539,20 @@ void attn_docs(AttnArgs& a, const char* who, const std::optional<Tensor>& doc_bo
   a.doc_end = a.doc_start + a.S;
 }
 
+// Attention sinks: `sinks` fp32 [H] on q's device, contiguous, one logit per QUERY head; bf16 q/k/v only and
+// always on attention.hip's generic kernels.  The values are free (-inf: no sink for that head).
+void attn_sinks(AttnArgs& a, const char* who, const std::optional<Tensor>& sinks, const Tensor& q) {
+  if (!sinks || !sinks->defined()) return;
+  const Tensor& t = *sinks;
+  MP_CHECK(q.scalar_type() == at::kBFloat16, who, ": attention with sinks runs on the bf16 kernels only, got ",
+           q.scalar_type());
+  MP_CHECK(t.scalar_type() == at::kFloat, who, ": sinks must be fp32, got ", t.scalar_type());
+  MP_CHECK(t.dim() == 1 && t.size(0) == a.H, who, ": sinks must be [H] = [", a.H, "], one per query head");
+  MP_CHECK(t.device() == q.device(), who, ": sinks must be on q's device");
+  MP_CHECK(t.is_contiguous(), who, ": sinks must be contiguous");
+  a.sinks = static_cast<const float*>(t.data_ptr());
+}
+
 // Returns (o, lse, seed, offset, dropout keep bits): the bits tensor (int32
 // [B*H, S/32, S]) is non-empty only for the long-sequence kernels with p > 0
 // and must be handed back to attention_bwd.  A windowed call (0 < window < S) or a soft-capped one returns none.
@@ -1548,10 +1562,12 @@ std::tuple<Tensor, Tensor, int64_t, int64_t, Tensor> py_attention_fwd(Tensor q, 
                                                                       double p, double scale, int64_t kv_len,
                                                                       std::optional<Tensor> words, int64_t words_seed,
                                                                       int64_t words_offset, int64_t window, double softcap,
-                                                                      std::optional<Tensor> doc_bounds) {
+                                                                      std::optional<Tensor> doc_bounds,
+                                                                      std::optional<Tensor> sinks) {
   AttnArgs a;
   fill_qkv(a, q, k, v);
   attn_docs(a, "attention", doc_bounds, causal, q);
+  attn_sinks(a, "attention", sinks, q);
   a.window = attn_window("attention", window, causal, q, a.S);
   a.softcap = attn_softcap("attention", softcap, q);
   MP_CHECK(p >= 0.0 && p < 1.0, "attention: bad dropout p");
@@ -1569,7 +1585,8 @@ std::tuple<Tensor, Tensor, int64_t, int64_t, Tensor> py_attention_fwd(Tensor q, 
   Tensor bits = at::empty({0}, q.options().dtype(at::kInt));
   if (q.scalar_type() == at::kFloat) {
     attention_f32_fwd(a, cur_stream(q));
-  } else if (a.window == 0 && a.softcap == 0.f && a.doc_start == nullptr && use_long(q, a.S, a.D)) {
+  } else if (a.window == 0 && a.softcap == 0.f && a.doc_start == nullptr && a.sinks == nullptr &&
+             use_long(q, a.S, a.D)) {
     bool reuse = false;
     if (p > 0.0) {
       const std::vector<int64_t> shape = {(int64_t)a.B * a.H, a.S / 32, a.S};
@@ -1590,10 +1607,19 @@ std::tuple<Tensor, Tensor, int64_t, int64_t, Tensor> py_attention_fwd(Tensor q, 
 void py_attention_bwd(Tensor dout, Tensor q, Tensor k, Tensor v, Tensor o, Tensor lse, bool causal, double p,
                       double scale, int64_t seed, int64_t offset, Tensor dq, Tensor dk, Tensor dv,
                       std::optional<Tensor> bits, int64_t kv_len, int64_t window, double softcap,
-                      std::optional<Tensor> doc_bounds) {
+                      std::optional<Tensor> doc_bounds, std::optional<Tensor> sinks, std::optional<Tensor> dsinks,
+                      bool dsinks_accumulate) {
   AttnArgs a;
   fill_qkv(a, q, k, v);
   attn_docs(a, "attention_bwd", doc_bounds, causal, q);
+  attn_sinks(a, "attention_bwd", sinks, q);
+  const bool want_dsinks = dsinks && dsinks->defined();
+  if (want_dsinks) {
+    MP_CHECK(a.sinks != nullptr, "attention_bwd: dsinks without sinks");
+    MP_CHECK(dsinks->scalar_type() == at::kFloat && dsinks->dim() == 1 && dsinks->size(0) == a.H &&
+                 dsinks->is_contiguous() && dsinks->device() == q.device(),
+             "attention_bwd: dsinks must be a contiguous fp32 [H] = [", a.H, "] on q's device");
+  }
   a.window = attn_window("attention_bwd", window, causal, q, a.S);
   a.softcap = attn_softcap("attention_bwd", softcap, q);
   MP_CHECK(kv_len == 0 || (q.scalar_type() == at::kFloat && kv_len > 0 && kv_len <= a.S),
@@ -1637,7 +1663,8 @@ void py_attention_bwd(Tensor dout, Tensor q, Tensor k, Tensor v, Tensor o, Tenso
   a.scale = (float)scale; a.p = (float)p; a.seed = (uint64_t)seed; a.offset = (uint64_t)offset; a.causal = causal;
   if (q.scalar_type() == at::kFloat) {
     attention_f32_bwd(a, cur_stream(q));
-  } else if (a.window == 0 && a.softcap == 0.f && a.doc_start == nullptr && use_long(q, a.S, a.D)) {
+  } else if (a.window == 0 && a.softcap == 0.f && a.doc_start == nullptr && a.sinks == nullptr &&
+             use_long(q, a.S, a.D)) {
     if (p > 0.0) {
       MP_CHECK(bits && bits->is_cuda() && bits->scalar_type() == at::kInt &&
                    bits->numel() == (int64_t)a.B * a.H * (a.S / 32) * a.S,
@@ -1648,10 +1675,29 @@ void py_attention_bwd(Tensor dout, Tensor q, Tensor k, Tensor v, Tensor o, Tenso
   } else {
     attention_bwd(a, cur_stream(q));
   }
+  if (want_dsinks) {  // from the lse the forward stored and the delta the backward just wrote
+    attention_dsink(a.lse, a.delta, a.sinks, ptr<float>(*dsinks), a.B, a.H, a.S, dsinks_accumulate, cur_stream(q));
+  }
   if (a.group > 1) {
     gqa_reduce_dkv<bf16_t>(cptr<bf16_t>(dkv), static_cast<bf16_t*>(dq.data_ptr()), (int64_t)a.B * a.S, a.H, (int)Hkv,
                            a.D, cur_stream(q));
   }
+}
+
+// The sinks' gradient alone (attention_bwd runs it itself when given `dsinks`; this entry is for tools that time
+// it): dsinks[h] (+)= -sum_{b,i} exp(sinks[h] - lse[b,h,i]) * delta[b,h,i].  fp32, contiguous, S % 4 == 0.
+void py_attention_dsink(Tensor lse, Tensor delta, Tensor sinks, Tensor dsinks, bool accumulate) {
+  for (const Tensor* t : {&lse, &delta, &sinks, &dsinks}) {
+    MP_CHECK(t->is_cuda() && t->scalar_type() == at::kFloat && t->is_contiguous() && t->device() == lse.device(),
+             "attention_dsink: lse, delta, sinks and dsinks must be contiguous fp32 tensors on one GPU");
+  }
+  MP_CHECK(lse.dim() == 3 && delta.sizes() == lse.sizes() && lse.size(2) % 4 == 0 && lse.size(1) > 0,
+           "attention_dsink: lse and delta must be [B, H, S] with S % 4 == 0");
+  MP_CHECK(sinks.dim() == 1 && sinks.size(0) == lse.size(1) && dsinks.sizes() == sinks.sizes(),
+           "attention_dsink: sinks and dsinks must be [H] = [", lse.size(1), "]");
+  at::hip::HIPGuardMasqueradingAsCUDA guard(lse.device());
+  attention_dsink(cptr<float>(lse), cptr<float>(delta), cptr<float>(sinks), ptr<float>(dsinks), (int)lse.size(0),
+                  (int)lse.size(1), (int)lse.size(2), accumulate, cur_stream(lse));
 }
 
 // ------------------------------------------------------------------ optimizer
@@ -1872,11 +1918,14 @@ PYBIND11_MODULE(_C, m) {
   m.def("attention_fwd", &py_attention_fwd, py::arg("q"), py::arg("k"), py::arg("v"), py::arg("causal"), py::arg("p"),
         py::arg("scale"), py::arg("kv_len") = 0, py::arg("words") = py::none(), py::arg("words_seed") = 0,
         py::arg("words_offset") = 0, py::arg("window") = 0, py::arg("softcap") = 0.0,
-        py::arg("doc_bounds") = py::none());
+        py::arg("doc_bounds") = py::none(), py::arg("sinks") = py::none());
   m.def("attention_bwd", &py_attention_bwd, py::arg("dout"), py::arg("q"), py::arg("k"), py::arg("v"), py::arg("o"),
         py::arg("lse"), py::arg("causal"), py::arg("p"), py::arg("scale"), py::arg("seed"), py::arg("offset"),
         py::arg("dq"), py::arg("dk"), py::arg("dv"), py::arg("bits") = py::none(), py::arg("kv_len") = 0,
-        py::arg("window") = 0, py::arg("softcap") = 0.0, py::arg("doc_bounds") = py::none());
+        py::arg("window") = 0, py::arg("softcap") = 0.0, py::arg("doc_bounds") = py::none(),
+        py::arg("sinks") = py::none(), py::arg("dsinks") = py::none(), py::arg("dsinks_accumulate") = false);
+  m.def("attention_dsink", &py_attention_dsink, py::arg("lse"), py::arg("delta"), py::arg("sinks"), py::arg("dsinks"),
+        py::arg("accumulate") = false);
   m.def("attention_long_supported", [](int64_t S, int64_t D) { return attention_long_supported((int)S, (int)D); });
   m.def("attention_long_set_fused_rng", &attention_long_set_fused_rng,
         "long-sequence attention: make the dropout keep words inside the forward kernel (true, default) or in a "

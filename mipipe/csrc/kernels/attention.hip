@@ -232,7 +232,9 @@ __device__ __forceinline__ int4 doc_rows4(const int32_t* bounds, const AttnArgs&
 // p = 0, as they do for a fresh row, so exp2 never sees (-inf) - (-inf).
 // DOCS (only with CAUSAL, see above): the loop starts at the tile of lo(q0); the mask is key < lo(row).  The same
 // guards cover a later row whose document starts after the first visited tile.
-template <int D, bool CAUSAL, bool WINDOW = false, bool SOFTCAP = false, bool DOCS = false>
+// SINK: a.sinks[h] joins the normalisation once, after the key-tile loop (see the epilogue); the loop is the
+// sinkless one, and so are the dropout mask and the backward kernels, which read the lse stored here.
+template <int D, bool CAUSAL, bool WINDOW = false, bool SOFTCAP = false, bool DOCS = false, bool SINK = false>
 __global__ void __launch_bounds__(kThreads, D == 256 ? 1 : 2) attn_fwd_kernel(AttnArgs a) {
   static_assert(!WINDOW || CAUSAL, "the sliding window is a band of the causal mask");
   static_assert(!DOCS || (CAUSAL && !WINDOW), "documents mask the causal triangle and merge the window at run time");
@@ -379,9 +381,28 @@ __global__ void __launch_bounds__(kThreads, D == 256 ? 1 : 2) attn_fwd_kernel(At
 
   // epilogue: O / l (bf16) and lse (natural log) per row
   bf16_t* O = reinterpret_cast<bf16_t*>(a.o) + (int64_t)b * a.sb_o + (int64_t)h * a.sh_o;
+  // SINK: one more term of the online softmax, with no value vector: m' = max(m, sink), l' = l * c + exp2(sink -
+  // m'), c = exp2(m - m'), and o scaled by c / l'.  A sink of -inf gives m' = m, c = 1 and l' = l + 0, so every
+  // stored bit is the sinkless kernel's; a sink far above m gives c -> 0 and l' = 1, so o -> 0 and lse = sink,
+  // all finite; a row that saw no key (m = -inf) has c = 0 by the guard, l' = 1, o = 0 and lse = sink.
+  float rescale[4] = {1.f, 1.f, 1.f, 1.f};
+  if constexpr (SINK) {
+    const float s2 = a.sinks[h] * kLog2e;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const float mn = fmaxf(m[r], s2);
+      rescale[r] = m[r] == -INFINITY ? 0.f : __builtin_amdgcn_exp2f(m[r] - mn);
+      const float es = mn == -INFINITY ? 0.f : __builtin_amdgcn_exp2f(s2 - mn);
+      l[r] = l[r] * rescale[r] + es;
+      m[r] = mn;
+    }
+  }
   float inv[4];
 #pragma unroll
-  for (int r = 0; r < 4; ++r) inv[r] = l[r] > 0.f ? 1.f / l[r] : 0.f;
+  for (int r = 0; r < 4; ++r) {
+    inv[r] = l[r] > 0.f ? 1.f / l[r] : 0.f;
+    if constexpr (SINK) inv[r] *= rescale[r];
+  }
 #pragma unroll
   for (int t2 = 0; t2 < ND; ++t2)
 #pragma unroll
@@ -636,6 +657,40 @@ __global__ void __launch_bounds__(kThreads) attn_delta_mfma_kernel(AttnArgs a) {
   if ((c >> 2) == g) {
     const float v = r == 0 ? acc[0] : (r == 1 ? acc[1] : (r == 2 ? acc[2] : acc[3]));
     a.delta[(int64_t)bh * a.S + row0 + c] = v;
+  }
+}
+
+// ------------------------------------------------------------------ dsink
+// The sink's probability of row (b, h, i) is exp(sink_h - lse) and it has no value vector (dP = 0), so dS = P (dP
+// - delta) gives dsink_h = -sum_{b,i} exp(sink_h - lse[b,h,i]) * delta[b,h,i].  One block per head: each thread
+// adds its rows in index order, then a wave butterfly and the four wave sums in order -- no atomics, so the same
+// bits on every run.  S % 4 == 0 (16-byte loads inside one row); a sink of -inf adds exp2(-inf) = 0 every time.
+__global__ void __launch_bounds__(kThreads) attn_dsink_kernel(const float* __restrict__ lse,
+                                                             const float* __restrict__ delta,
+                                                             const float* __restrict__ sinks,
+                                                             float* __restrict__ dsinks, int B, int H, int S,
+                                                             int accumulate) {
+  __shared__ float part[kThreads / 64];
+  const int h = blockIdx.x, tid = threadIdx.x;
+  const float sk = sinks[h];
+  float acc = 0.f;
+  for (int b = 0; b < B; ++b) {
+    const int64_t row = ((int64_t)b * H + h) * S;
+    for (int i = tid * 4; i < S; i += kThreads * 4) {
+      const float4 lv = *reinterpret_cast<const float4*>(lse + row + i);
+      const float4 dv = *reinterpret_cast<const float4*>(delta + row + i);
+      acc += __builtin_amdgcn_exp2f((sk - lv.x) * kLog2e) * dv.x;
+      acc += __builtin_amdgcn_exp2f((sk - lv.y) * kLog2e) * dv.y;
+      acc += __builtin_amdgcn_exp2f((sk - lv.z) * kLog2e) * dv.z;
+      acc += __builtin_amdgcn_exp2f((sk - lv.w) * kLog2e) * dv.w;
+    }
+  }
+  acc = wave_sum(acc);
+  if ((tid & 63) == 0) part[tid >> 6] = acc;
+  __syncthreads();
+  if (tid == 0) {
+    const float v = -(((part[0] + part[1]) + part[2]) + part[3]);
+    dsinks[h] = accumulate ? dsinks[h] + v : v;
   }
 }
 
@@ -1672,9 +1727,58 @@ void bwd_softcap(const AttnArgs& a, hipStream_t s) {
   else run_bwd_softcap<D, false, false>(a, s);
 }
 
+// Attention sinks (a.sinks set): always the generic 64-row kernels too, under every mask above -- the S = 128,
+// wide D = 64 and long-sequence kernels know no sink.  SINK multiplies the forward kernel only: the backward runs
+// the sinkless instantiations on the forward's lse (run_bwd_window, run_bwd_softcap, run_bwd_docs as they are).
+template <int D, bool CAUSAL, bool WINDOW, bool SOFTCAP, bool DOCS>
+void run_fwd_sink(const AttnArgs& a, hipStream_t s) {
+  const size_t sm = fwd_smem<D>();
+  static bool once = false;
+  if (!once) { set_smem(attn_fwd_kernel<D, CAUSAL, WINDOW, SOFTCAP, DOCS, true>, sm); once = true; }
+  hipLaunchKernelGGL((attn_fwd_kernel<D, CAUSAL, WINDOW, SOFTCAP, DOCS, true>), dim3(a.S / kRows, a.B * a.H),
+                     dim3(kThreads), sm, s, a);
+}
+
+template <int D, bool SOFTCAP>
+void fwd_sink_masks(const AttnArgs& a, hipStream_t s, bool docs) {
+  if (docs) run_fwd_sink<D, true, false, SOFTCAP, true>(a, s);
+  else if (a.window > 0) run_fwd_sink<D, true, true, SOFTCAP, false>(a, s);
+  else if (a.causal) run_fwd_sink<D, true, false, SOFTCAP, false>(a, s);
+  else run_fwd_sink<D, false, false, SOFTCAP, false>(a, s);
+}
+
+template <int D>
+void fwd_sink(const AttnArgs& a, hipStream_t s, bool docs) {
+  if (a.softcap > 0.f) fwd_sink_masks<D, true>(a, s, docs);
+  else fwd_sink_masks<D, false>(a, s, docs);
+}
+
+// The backward of a call with sinks and no window, cap or documents: the generic dK/dV and dQ kernels at every S
+// and D, with delta from attn_delta_mfma_kernel, as under a window.
+template <int D, bool CAUSAL>
+void run_bwd_sink(const AttnArgs& a, hipStream_t s) {
+  const size_t sm = fwd_smem<D>(), sm2 = dkdv_smem<D>();
+  static bool once = false;
+  if (!once) {
+    set_smem(attn_dq_kernel<D, CAUSAL>, sm);
+    set_smem(attn_dkdv_kernel<D, CAUSAL>, sm2);
+    once = true;
+  }
+  const dim3 grid(a.S / kRows, a.B * a.H);
+  hipLaunchKernelGGL((attn_delta_mfma_kernel<D>), grid, dim3(kThreads), 0, s, a);
+  hipLaunchKernelGGL((attn_dkdv_kernel<D, CAUSAL>), grid, dim3(kThreads), sm2, s, a);
+  hipLaunchKernelGGL((attn_dq_kernel<D, CAUSAL>), grid, dim3(kThreads), sm, s, a);
+}
+
 }  // namespace
 
 void attention_set_fused_bwd(int on) { g_attn_fused_bwd = on; }
+
+void attention_dsink(const float* lse, const float* delta, const float* sinks, float* dsinks, int B, int H, int S,
+                     bool accumulate, hipStream_t s) {
+  hipLaunchKernelGGL(attn_dsink_kernel, dim3(H), dim3(kThreads), 0, s, lse, delta, sinks, dsinks, B, H, S,
+                     accumulate ? 1 : 0);
+}
 
 bool attention_supported(int S, int D) { return S > 0 && S % kRows == 0 && (D == 64 || D == 128 || D == 256); }
 
@@ -1682,6 +1786,13 @@ void attention_fwd(const AttnArgs& ai, hipStream_t s) {
   AttnArgs a = attn_resolved(ai);
   a.threshold = dropout_threshold(a.p);
   normalise_window(a);
+  if (a.sinks != nullptr) {
+    const bool docs = normalise_docs(a);
+    if (a.D == 64) fwd_sink<64>(a, s, docs);
+    else if (a.D == 128) fwd_sink<128>(a, s, docs);
+    else fwd_sink<256>(a, s, docs);
+    return;
+  }
   if (normalise_docs(a)) {
     if (a.D == 64) fwd_docs<64>(a, s);
     else if (a.D == 128) fwd_docs<128>(a, s);
@@ -1731,6 +1842,18 @@ void attention_bwd(const AttnArgs& ai, hipStream_t s) {
     if (a.D == 64) run_bwd_window<64>(a, s);
     else if (a.D == 128) run_bwd_window<128>(a, s);
     else run_bwd_window<256>(a, s);
+    return;
+  }
+  if (a.sinks != nullptr) {  // the forward ran the generic kernel: so does the backward, at every S and D
+    if (a.causal) {
+      if (a.D == 64) run_bwd_sink<64, true>(a, s);
+      else if (a.D == 128) run_bwd_sink<128, true>(a, s);
+      else run_bwd_sink<256, true>(a, s);
+    } else {
+      if (a.D == 64) run_bwd_sink<64, false>(a, s);
+      else if (a.D == 128) run_bwd_sink<128, false>(a, s);
+      else run_bwd_sink<256, false>(a, s);
+    }
     return;
   }
   if (a.causal) {

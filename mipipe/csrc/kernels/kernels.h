@@ -347,6 +347,12 @@ struct AttnArgs {
   // non-decreasing along a row.  nullptr = no documents.  Appended after `softcap` for the same reason.
   const int32_t* doc_start = nullptr;
   const int32_t* doc_end = nullptr;
+  // Attention sinks (bf16 attention.hip's generic kernels): fp32 [H], one learned logit per QUERY head that joins
+  // the softmax normalisation (after the cap and the masks, neither scaled nor capped) and has no value vector;
+  // lse is then the log-sum-exp over the scores and the sink.  nullptr = no sinks; -inf = no sink for that head.
+  // Only the forward reads it (the backward's P = exp(s - lse) is already right).  Appended after `doc_end` for
+  // the same reason.
+  const float* sinks = nullptr;
 };
 // K / V head of query head h: h / group as a scalar multiply by ceil(2^20 / group) and a shift instead of a
 // division.  Exact for every h when group == 1 (the 64-bit product is h * 2^20) and while h * group < 2^20
@@ -412,6 +418,11 @@ bool attention_supported(int S, int D);
 void attention_set_fused_bwd(int on);
 void attention_fwd(const AttnArgs& a, hipStream_t s);
 void attention_bwd(const AttnArgs& a, hipStream_t s);
+// The sinks' gradient, after attention_bwd (which leaves delta): dsinks[h] (+)= -sum_{b,i} exp(sinks[h] -
+// lse[b,h,i]) * delta[b,h,i], fp32, one block per head adding in a fixed order (no atomics: the same bits on
+// every run).  lse, delta: [B, H, S]; sinks, dsinks: [H].  accumulate: add to dsinks (an fp32 main_grad view).
+void attention_dsink(const float* lse, const float* delta, const float* sinks, float* dsinks, int B, int H, int S,
+                     bool accumulate, hipStream_t s);
 // fp32 q/k/v/o (v_mfma_f32_32x32x2_f32): S % 32 == 0, D == 64; "key-quad" dropout layout.
 bool attention_f32_supported(int S, int D);
 // bf16, D == 64, S >= 256, S % 64 == 0 (attention_long.hip): 32x32x16 MFMA, stored dropout bits.

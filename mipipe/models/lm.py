@@ -233,6 +233,7 @@ class LMConfig:
     head_dim: Optional[int] = None    # head width; None = d_model // nhead
     attn_scale: Optional[float] = None  # score scale; None = head_dim ** -0.5 (Gemma-2: query_pre_attn_scalar ** -0.5)
     global_every: Optional[int] = None  # layer i is global (no window) when (i + 1) % n == 0; needs window
+    attn_sinks: bool = False          # a learned logit per query head in the softmax's denominator (gpt-oss): [nhead]
     qk_norm: bool = False             # per-head RMSNorm on Q and K before the rotation (Qwen3): two [head_dim] weights
 
     def __post_init__(self) -> None:
@@ -268,6 +269,8 @@ class LMConfig:
         layer = (qkv + self.attn_dim()) * e + 2 * norm + f1 * e + e * f + nb * (qkv + e + f1 + e)
         if self.qk_norm:
             layer += 2 * self.head_width()
+        if self.attn_sinks:
+            layer += self.nhead
         if self.sandwich_norm:
             layer += 2 * e   # the two post-norm weights
         total = self.num_layers * layer + v * e
@@ -342,6 +345,12 @@ CONFIGS = {
                             notes="mistral_tiny plus Gemma-2's soft caps: attention scores at 50, output logits at "
                                   "30 (the Gemma-2 block itself -- head dim of its own, GeGLU, sandwich norms, local / "
                                   "global layers -- is gemma2_block_tiny)"),
+    # mistral_tiny with attention sinks: every query head has a learned logit in its softmax's denominator, under
+    # the grouped-query heads and the window (gpt-oss's attention; its MoE MLP, QKV bias and YaRN are not here).
+    "sink_tiny": LMConfig("sink_tiny", 2, 256, 4, 512, 1000, 192, dropout=0.0, activation="swiglu",
+                          norm_first=True, causal=True, scale_embedding=False, act_dropout=0.0, norm="rms",
+                          bias=False, rope=True, positions="none", n_kv_heads=2, window=48, attn_sinks=True,
+                          notes="mistral_tiny plus attention sinks (one learned logit per query head) for tests"),
     # llama_gqa_tiny with QK-norm: every Q and K head RMS-normalised before the rotation.
     "qwen3_tiny": LMConfig("qwen3_tiny", 2, 256, 4, 512, 1000, 64, dropout=0.0, activation="swiglu",
                            norm_first=True, causal=True, scale_embedding=False, act_dropout=0.0, norm="rms",
@@ -381,7 +390,8 @@ def build_lm_blocks(cfg: LMConfig, *, device=None, dtype=None) -> List[nn.Module
                                  bias=cfg.bias, rope=cfg.rope, rope_base=cfg.rope_base, n_kv_heads=cfg.n_kv_heads,
                                  window=cfg.window, qk_norm=cfg.qk_norm, attn_softcap=cfg.attn_softcap,
                                  sandwich_norm=cfg.sandwich_norm, head_dim=cfg.head_dim, attn_scale=cfg.attn_scale,
-                                 global_every=cfg.global_every, device=device, dtype=dtype)
+                                 global_every=cfg.global_every, attn_sinks=cfg.attn_sinks, device=device,
+                                 dtype=dtype)
     if cfg.act_dropout is not None:
         for b in blocks:
             if isinstance(b, FeedForwardBlock):

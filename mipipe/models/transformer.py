@@ -37,7 +37,10 @@ tanh(s / c)`` before the softmax (Gemma-2's ``attn_logit_softcapping``).
 ``D`` features before the rotation, with the learned ``[D]`` weights
 ``q_norm_weight`` and ``k_norm_weight`` of the attention core and the block's
 ``layer_norm_eps`` (``ops.qk_norm_rope_projection``: one kernel with the
-rotation, or the norm alone with ``rope=False``).
+rotation, or the norm alone with ``rope=False``).  ``attn_sinks=True`` (gpt-oss)
+gives the attention core ``sinks``, a learned ``[nhead]`` parameter (zeros at
+initialisation): one logit per query head that joins the softmax's denominator
+and has no value (``ops.attention``'s ``sinks=``).
 
 Four more options make the halves a Gemma-2 block.  ``activation="geglu"`` is
 ``"swiglu"`` with the tanh-GELU as the gate (``ops.geglu``; the same ``[2F, E]``
@@ -163,7 +166,7 @@ class AttentionCore(nn.Module):
                  layer_norm_eps: float, norm: str = "layer", bias: bool = True, rope: bool = False,
                  rope_base: float = 10000.0, n_kv_heads: Optional[int] = None, window: Optional[int] = None,
                  qk_norm: bool = False, attn_softcap: Optional[float] = None, head_dim: Optional[int] = None,
-                 attn_scale: Optional[float] = None, device=None, dtype=None) -> None:
+                 attn_scale: Optional[float] = None, attn_sinks: bool = False, device=None, dtype=None) -> None:
         super().__init__()
         fk = {"device": device, "dtype": dtype}
         if head_dim is None:
@@ -214,6 +217,11 @@ class AttentionCore(nn.Module):
             # their gradients)
             self.q_norm_weight = nn.Parameter(torch.empty(self.head_dim, **fk))
             self.k_norm_weight = nn.Parameter(torch.empty(self.head_dim, **fk))
+        self.attn_sinks = bool(attn_sinks)
+        if self.attn_sinks:
+            # one learned logit per query head in the softmax's denominator (not a GEMM weight: the attention
+            # backward writes its gradient)
+            self.sinks = nn.Parameter(torch.empty(nhead, **fk))
         self.reset_parameters()
 
     def reset_parameters(self) -> None:
@@ -226,6 +234,8 @@ class AttentionCore(nn.Module):
         if self.qk_norm:
             nn.init.ones_(self.q_norm_weight)
             nn.init.ones_(self.k_norm_weight)
+        if self.attn_sinks:
+            nn.init.zeros_(self.sinks)
 
     def _rope_tables(self, seq_len: int, device):
         # rebuilt when too short, on another device, or cast by a module-wide .to(dtype): the kernel reads fp32
@@ -261,6 +271,7 @@ class AttentionCore(nn.Module):
         B, S, _ = x.shape
         H, D, E = self.nhead, self.head_dim, self.attn_dim  # E: the width of o
         docs = self._documents(B, S)
+        sinks = self.sinks if self.attn_sinks else None
         xr = x
         if self.norm_first:
             if fanout:
@@ -283,11 +294,11 @@ class AttentionCore(nn.Module):
             if Hkv != H:
                 o = ops.attention_gqa_packed(qkv_n, Hkv, causal=self.causal, dropout_p=self.dropout,
                                              training=self.training, scale=self.attn_scale, window=self.window,
-                                             softcap=self.attn_softcap, doc_bounds=docs)
+                                             softcap=self.attn_softcap, doc_bounds=docs, sinks=sinks)
             else:
                 o = ops.attention_packed(qkv_n, causal=self.causal, dropout_p=self.dropout, training=self.training,
                                          scale=self.attn_scale, window=self.window, softcap=self.attn_softcap,
-                                         doc_bounds=docs)
+                                         doc_bounds=docs, sinks=sinks)
             return o.reshape(B, S, E), xr
         if Hkv != H:
             # grouped-query attention: [B, S, H + 2 Hkv, D], the K/V heads read in place by every query head
@@ -299,7 +310,7 @@ class AttentionCore(nn.Module):
                 qkv4 = qkv.view(B, S, H + 2 * Hkv, D)
             o = ops.attention_gqa_packed(qkv4, Hkv, causal=self.causal, dropout_p=self.dropout,
                                          training=self.training, scale=self.attn_scale, window=self.window,
-                                         softcap=self.attn_softcap, doc_bounds=docs)
+                                         softcap=self.attn_softcap, doc_bounds=docs, sinks=sinks)
             return o.reshape(B, S, E), xr
         if self.rope:
             # Q and K rotated: in the projection's own output where no graph is recorded, else into a new tensor
@@ -309,7 +320,7 @@ class AttentionCore(nn.Module):
             qkv5 = qkv.view(B, S, 3, H, D)
         o = ops.attention_packed(qkv5, causal=self.causal, dropout_p=self.dropout, training=self.training,
                                  scale=self.attn_scale, window=self.window, softcap=self.attn_softcap,
-                                 doc_bounds=docs)
+                                 doc_bounds=docs, sinks=sinks)
         return o.reshape(B, S, E), xr
 
     def flops_per_token(self, seq_len: int) -> float:
@@ -385,7 +396,7 @@ class SelfAttentionBlock(nn.Module):
                  rope: bool = False, rope_base: float = 10000.0, n_kv_heads: Optional[int] = None,
                  window: Optional[int] = None, qk_norm: bool = False, attn_softcap: Optional[float] = None,
                  sandwich_norm: bool = False, head_dim: Optional[int] = None, attn_scale: Optional[float] = None,
-                 device=None, dtype=None) -> None:
+                 attn_sinks: bool = False, device=None, dtype=None) -> None:
         super().__init__()
         if head_dim is None and d_model % nhead != 0:
             raise ValueError("d_model must be divisible by nhead")
@@ -394,7 +405,7 @@ class SelfAttentionBlock(nn.Module):
                                   layer_norm_eps=layer_norm_eps, norm=norm, bias=bias, rope=rope,
                                   rope_base=rope_base, n_kv_heads=n_kv_heads, window=window, qk_norm=qk_norm,
                                   attn_softcap=attn_softcap, head_dim=head_dim, attn_scale=attn_scale,
-                                  device=device, dtype=dtype)
+                                  attn_sinks=attn_sinks, device=device, dtype=dtype)
         self.out = AttentionOutput(d_model, dropout, norm_first=norm_first, layer_norm_eps=layer_norm_eps,
                                    norm=norm, bias=bias, attn_dim=self.core.attn_dim, sandwich_norm=sandwich_norm,
                                    device=device, dtype=dtype)
@@ -704,13 +715,14 @@ class TransformerEncoderLayer(nn.Sequential):
         sandwich_norm: bool = False,
         head_dim: Optional[int] = None,
         attn_scale: Optional[float] = None,
+        attn_sinks: bool = False,
     ) -> None:
         super().__init__(
             SelfAttentionBlock(d_model, nhead, dropout, norm_first=norm_first, causal=causal,
                                layer_norm_eps=layer_norm_eps, norm=norm, bias=bias, rope=rope, rope_base=rope_base,
                                n_kv_heads=n_kv_heads, window=window, qk_norm=qk_norm, attn_softcap=attn_softcap,
                                sandwich_norm=sandwich_norm, head_dim=head_dim, attn_scale=attn_scale,
-                               device=device, dtype=dtype),
+                               attn_sinks=attn_sinks, device=device, dtype=dtype),
             FeedForwardBlock(d_model, dim_feedforward, dropout, activation, norm_first=norm_first,
                              layer_norm_eps=layer_norm_eps, norm=norm, bias=bias, sandwich_norm=sandwich_norm,
                              device=device, dtype=dtype),
@@ -778,6 +790,7 @@ def transformer_blocks(
     head_dim: Optional[int] = None,
     attn_scale: Optional[float] = None,
     global_every: Optional[int] = None,
+    attn_sinks: bool = False,
     device=None,
     dtype=None,
 ) -> List[nn.Module]:
@@ -793,7 +806,7 @@ def transformer_blocks(
                                         rope_base=rope_base, n_kv_heads=n_kv_heads,
                                         window=layer_window(window, global_every, i), qk_norm=qk_norm,
                                         attn_softcap=attn_softcap, sandwich_norm=sandwich_norm, head_dim=head_dim,
-                                        attn_scale=attn_scale, device=device, dtype=dtype)
+                                        attn_scale=attn_scale, attn_sinks=attn_sinks, device=device, dtype=dtype)
         blocks.extend(layer.children())
     return blocks
 

@@ -76,6 +76,19 @@ padded use :func:`attention_reference` with the document mask.  The contract on 
 end[i]``, both rows non-decreasing) is the caller's: :func:`check_doc_bounds` validates it on the host, with a
 sync, and is never called on the hot path; the kernels clamp the loop bounds they take from the tensor.
 :func:`use_documents` sets the bounds for the calling thread (``AttentionCore`` reads them).
+
+Attention sinks: every entry point takes a keyword-only ``sinks`` -- a ``[H]`` tensor, one learned logit per query
+head (also under grouped-query attention), fp32 or the activations' dtype.  The sink joins the softmax's
+normalisation after the cap and the masks, neither scaled nor capped, and has no value vector: ``p_ij = exp(s_ij -
+m) / (exp(sink_h - m) + sum_j exp(s_ij - m))`` -- Hugging Face gpt-oss's ``softmax(cat([scores, sinks], -1))[...,
+:-1]``.  ``None`` is the code path it always was; ``-inf`` is "no sink for this head".  It works with
+``causal=False`` too, and dropout acts on the real keys' ``p_ij`` only, with the sinkless call's mask.  A bf16 call
+on the GPU runs attention.hip's generic kernels whatever S and D: the sink is folded in once after the forward's
+key loop, the three backward kernels are the sinkless ones reading the forward's ``lse``, and ``dsinks[h] = -sum
+exp(sink_h - lse) * delta`` comes from one small fixed-order reduction (the same bits on every run; it goes
+straight into the parameter's fp32 ``main_grad`` where there is one).  Every padded shape stays native, the
+non-causal key mask included (a padded key still underflows against a running max the sink can only raise) unless
+there is a cap as well; fp32, the CPU and the shapes that cannot be padded use :func:`attention_reference`.
 """
 from __future__ import annotations
 
@@ -92,6 +105,7 @@ from torch import Tensor
 
 from ..checkpoint import is_recomputing, recompute_expected
 from ._util import kernels_for
+from .linear import accumulable
 
 __all__ = ["attention", "attention_packed", "attention_gqa_packed", "attention_reference", "clear_keep_words",
            "check_doc_bounds", "use_documents", "current_documents"]
@@ -133,6 +147,19 @@ def _check_docs(doc_bounds: Optional[Tensor], causal: bool, B: int, S: int) -> O
     if tuple(doc_bounds.shape) != (B, 2, S):
         raise ValueError(f"attention: doc_bounds must be [B, 2, S] = [{B}, 2, {S}], got {tuple(doc_bounds.shape)}")
     return doc_bounds
+
+
+def _check_sinks(sinks: Optional[Tensor], H: int, dtype: torch.dtype) -> Optional[Tensor]:
+    """``sinks`` validated: ``None`` (no sinks) or a ``[H]`` tensor, one logit per query head, in fp32 or the
+    activations' dtype.  The values are free (``-inf``: no sink for that head)."""
+    if sinks is None:
+        return None
+    if not isinstance(sinks, Tensor) or sinks.dim() != 1 or sinks.shape[0] != H:
+        raise ValueError(f"attention: sinks must be a [H] = [{H}] tensor, one per query head, got "
+                         f"{tuple(sinks.shape) if isinstance(sinks, Tensor) else sinks!r}")
+    if sinks.dtype not in (torch.float32, dtype):
+        raise ValueError(f"attention: sinks must be float32 or the activations' dtype ({dtype}), got {sinks.dtype}")
+    return sinks
 
 
 def check_doc_bounds(bounds: Tensor) -> None:
@@ -177,17 +204,20 @@ def use_documents(bounds: Optional[Tensor]):
 
 def attention_reference(q: Tensor, k: Tensor, v: Tensor, causal: bool, p: float, scale: Optional[float] = None,
                         *, window: Optional[int] = None, softcap: Optional[float] = None,
-                        doc_bounds: Optional[Tensor] = None) -> Tensor:
+                        doc_bounds: Optional[Tensor] = None, sinks: Optional[Tensor] = None) -> Tensor:
     """Eager fp32 math on ``[B, H, S, D]`` (CPU path and test oracle).  ``window``: query ``i`` sees the keys
     ``i - window < j <= i`` only.  ``softcap``: the scaled scores become ``softcap * tanh(s / softcap)`` before
     the masks.  ``doc_bounds`` (int32 ``[B, 2, S]``): query ``i`` sees the keys ``j >= doc_bounds[b, 0, i]``
-    only."""
+    only.  ``sinks`` (``[H]``): one more logit per query head in the softmax's denominator, with no value (the
+    module doc); the math then runs in fp64 for fp64 inputs."""
     d = q.shape[-1]
     scale = scale if scale is not None else 1.0 / math.sqrt(d)
     window = _check_window(window, bool(causal), q.shape[-2])
     softcap = _check_softcap(softcap)
     docs = _check_docs(doc_bounds, bool(causal), q.shape[0], q.shape[-2])
-    s = torch.matmul(q.float(), k.float().transpose(-1, -2)) * scale
+    sinks = _check_sinks(sinks, q.shape[1], q.dtype)
+    wide = torch.float32 if sinks is None else torch.promote_types(q.dtype, torch.float32)
+    s = torch.matmul(q.to(wide), k.to(wide).transpose(-1, -2)) * scale
     if softcap is not None:
         s = softcap * torch.tanh(s / softcap)
     if causal:
@@ -201,9 +231,14 @@ def attention_reference(q: Tensor, k: Tensor, v: Tensor, causal: bool, p: float,
             keys = torch.arange(m, device=s.device)
             s = s.masked_fill((keys[None, None, :] < start[:, :, None])[:, None], float("-inf"))
     pr = torch.softmax(s, dim=-1)
+    if sinks is not None:
+        # softmax(cat(s, sink))[..., :-1] = softmax(s) * den / (den + exp(sink)), den = sum_j exp(s_j): the factor
+        # is sigmoid(lse(s) - sink), exactly 1 at sink = -inf (the sinkless bits) and finite for any sink
+        sk = sinks.to(device=s.device, dtype=wide).view(1, -1, 1, 1)
+        pr = pr * torch.sigmoid(torch.logsumexp(s, dim=-1, keepdim=True) - sk)
     if p > 0:
         pr = F.dropout(pr, p, True)
-    return torch.matmul(pr, v.float()).to(q.dtype)
+    return torch.matmul(pr, v.to(wide)).to(q.dtype)
 
 
 # Keep words across a checkpoint: the long-sequence forward (attention_long.hip) makes its dropout keep words
@@ -242,8 +277,10 @@ def clear_keep_words() -> None:
         _keep_bytes = 0
 
 
-def _attention_fwd(kern, q, k, v, causal, p, scale, kv_len, window=0, softcap=0.0, docs=None):
+def _attention_fwd(kern, q, k, v, causal, p, scale, kv_len, window=0, softcap=0.0, docs=None, sinks=None):
     global _keep_bytes
+    if sinks is not None:  # the generic kernels, as below
+        return kern.attention_fwd(q, k, v, causal, p, scale, kv_len, None, 0, 0, window, softcap, docs, sinks)
     if docs is not None:  # the generic kernels, as below
         return kern.attention_fwd(q, k, v, causal, p, scale, kv_len, None, 0, 0, window, softcap, docs)
     if window or softcap:  # the generic kernels: the mask is regenerated from Philox, there are no keep words
@@ -274,55 +311,81 @@ def _attention_fwd(kern, q, k, v, causal, p, scale, kv_len, window=0, softcap=0.
     return out
 
 
+def _kernel_sinks(sinks: Optional[Tensor]) -> Optional[Tensor]:
+    """``sinks`` as the kernels read them: fp32, contiguous, detached (the same tensor where it already is)."""
+    return None if sinks is None else sinks.detach().float().contiguous()
+
+
+def _dsinks_out(sinks: Optional[Tensor], sk: Optional[Tensor], needed: bool):
+    """``(dsinks, accumulate)`` for ``attention_bwd``: the parameter's fp32 ``main_grad`` to add into where it has
+    one, a fresh fp32 ``[H]`` to store into otherwise, ``(None, False)`` where no gradient is asked for."""
+    if sinks is None or not needed:
+        return None, False
+    main = getattr(sinks, "main_grad", None)
+    if main is not None and main.dtype == torch.float32 and main.is_contiguous() and main.device == sk.device:
+        return accumulable(sinks), True  # claimed (and zero-filled if it was lazily zeroed) only once it is usable
+    return torch.empty_like(sk), False
+
+
+def _dsinks_grad(sinks: Optional[Tensor], ds: Optional[Tensor], accumulated: bool) -> Optional[Tensor]:
+    return None if ds is None or accumulated else ds.to(sinks.dtype)
+
+
 class _AttentionPacked(torch.autograd.Function):
     """``qkv [B, S, 3, H, D]`` (contiguous) in, ``o [B, S, H, D]`` out; the
     backward produces the packed ``dqkv`` in one buffer."""
 
     @staticmethod
-    def forward(ctx, qkv, causal, p, scale, kv_len=0, window=0, softcap=0.0, docs=None):  # type: ignore[override]
+    def forward(ctx, qkv, causal, p, scale, kv_len=0, window=0, softcap=0.0, docs=None,  # type: ignore[override]
+                sinks=None):
         kern = kernels_for(qkv)
         q, k, v = qkv.select(2, 0), qkv.select(2, 1), qkv.select(2, 2)
-        o, lse, seed, offset, bits = _attention_fwd(kern, q, k, v, causal, p, scale, kv_len, window, softcap, docs)
-        ctx.save_for_backward(qkv, o, lse, bits, docs)
+        sk = _kernel_sinks(sinks)
+        o, lse, seed, offset, bits = _attention_fwd(kern, q, k, v, causal, p, scale, kv_len, window, softcap, docs, sk)
+        ctx.save_for_backward(qkv, o, lse, bits, docs, sinks, sk)
         ctx.causal, ctx.p, ctx.scale, ctx.seed, ctx.offset, ctx.kv_len = causal, p, scale, seed, offset, kv_len
         ctx.window, ctx.softcap = window, softcap
         return o
 
     @staticmethod
     def backward(ctx, do):  # type: ignore[override]
-        qkv, o, lse, bits, docs = ctx.saved_tensors
+        qkv, o, lse, bits, docs, sinks, sk = ctx.saved_tensors
         kern = kernels_for(do)
         if do.stride() != o.stride():
             do = do.contiguous()
         dqkv = torch.empty_like(qkv)
+        ds, acc = _dsinks_out(sinks, sk, sinks is not None and ctx.needs_input_grad[8])
         kern.attention_bwd(do, qkv.select(2, 0), qkv.select(2, 1), qkv.select(2, 2), o, lse, ctx.causal, ctx.p,
                            ctx.scale, ctx.seed, ctx.offset, dqkv.select(2, 0), dqkv.select(2, 1), dqkv.select(2, 2),
-                           bits if bits.numel() else None, ctx.kv_len, ctx.window, ctx.softcap, docs)
-        return dqkv, None, None, None, None, None, None, None
+                           bits if bits.numel() else None, ctx.kv_len, ctx.window, ctx.softcap, docs, sk, ds, acc)
+        return dqkv, None, None, None, None, None, None, None, _dsinks_grad(sinks, ds, acc)
 
 
 class _Attention(torch.autograd.Function):
     """Separate q, k, v as [B, S, H, D] views sharing one layout."""
 
     @staticmethod
-    def forward(ctx, q, k, v, causal, p, scale, kv_len=0, window=0, softcap=0.0, docs=None):  # type: ignore[override]
+    def forward(ctx, q, k, v, causal, p, scale, kv_len=0, window=0, softcap=0.0, docs=None,  # type: ignore[override]
+                sinks=None):
         kern = kernels_for(q)
-        o, lse, seed, offset, bits = _attention_fwd(kern, q, k, v, causal, p, scale, kv_len, window, softcap, docs)
-        ctx.save_for_backward(q, k, v, o, lse, bits, docs)
+        sk = _kernel_sinks(sinks)
+        o, lse, seed, offset, bits = _attention_fwd(kern, q, k, v, causal, p, scale, kv_len, window, softcap, docs, sk)
+        ctx.save_for_backward(q, k, v, o, lse, bits, docs, sinks, sk)
         ctx.causal, ctx.p, ctx.scale, ctx.seed, ctx.offset, ctx.kv_len = causal, p, scale, seed, offset, kv_len
         ctx.window, ctx.softcap = window, softcap
         return o
 
     @staticmethod
     def backward(ctx, do):  # type: ignore[override]
-        q, k, v, o, lse, bits, docs = ctx.saved_tensors
+        q, k, v, o, lse, bits, docs, sinks, sk = ctx.saved_tensors
         kern = kernels_for(do)
         if do.stride() != o.stride():
             do = do.contiguous()
         dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
+        ds, acc = _dsinks_out(sinks, sk, sinks is not None and ctx.needs_input_grad[10])
         kern.attention_bwd(do, q, k, v, o, lse, ctx.causal, ctx.p, ctx.scale, ctx.seed, ctx.offset, dq, dk, dv,
-                           bits if bits.numel() else None, ctx.kv_len, ctx.window, ctx.softcap, docs)
-        return dq, dk, dv, None, None, None, None, None, None, None
+                           bits if bits.numel() else None, ctx.kv_len, ctx.window, ctx.softcap, docs, sk, ds, acc)
+        return dq, dk, dv, None, None, None, None, None, None, None, _dsinks_grad(sinks, ds, acc)
 
 
 class _AttentionGqaPacked(torch.autograd.Function):
@@ -331,42 +394,48 @@ class _AttentionGqaPacked(torch.autograd.Function):
     dK / dV into one packed ``dqkv`` of the same layout (the binding owns the per-query-head scratch)."""
 
     @staticmethod
-    def forward(ctx, qkv, n_kv, causal, p, scale, window=0, softcap=0.0, docs=None):  # type: ignore[override]
+    def forward(ctx, qkv, n_kv, causal, p, scale, window=0, softcap=0.0, docs=None,  # type: ignore[override]
+                sinks=None):
         kern = kernels_for(qkv)
         H = qkv.shape[2] - 2 * n_kv
         q, k, v = qkv[:, :, :H], qkv[:, :, H:H + n_kv], qkv[:, :, H + n_kv:]
-        o, lse, seed, offset, bits = _attention_fwd(kern, q, k, v, causal, p, scale, 0, window, softcap, docs)
-        ctx.save_for_backward(qkv, o, lse, bits, docs)
+        sk = _kernel_sinks(sinks)
+        o, lse, seed, offset, bits = _attention_fwd(kern, q, k, v, causal, p, scale, 0, window, softcap, docs, sk)
+        ctx.save_for_backward(qkv, o, lse, bits, docs, sinks, sk)
         ctx.n_kv, ctx.causal, ctx.p, ctx.scale, ctx.seed, ctx.offset = n_kv, causal, p, scale, seed, offset
         ctx.window, ctx.softcap = window, softcap
         return o
 
     @staticmethod
     def backward(ctx, do):  # type: ignore[override]
-        qkv, o, lse, bits, docs = ctx.saved_tensors
+        qkv, o, lse, bits, docs, sinks, sk = ctx.saved_tensors
         kern = kernels_for(do)
         if do.stride() != o.stride():
             do = do.contiguous()
         n_kv = ctx.n_kv
         H = qkv.shape[2] - 2 * n_kv
         dqkv = torch.empty_like(qkv)
+        ds, acc = _dsinks_out(sinks, sk, sinks is not None and ctx.needs_input_grad[8])
         kern.attention_bwd(do, qkv[:, :, :H], qkv[:, :, H:H + n_kv], qkv[:, :, H + n_kv:], o, lse, ctx.causal, ctx.p,
                            ctx.scale, ctx.seed, ctx.offset, dqkv[:, :, :H], dqkv[:, :, H:H + n_kv],
-                           dqkv[:, :, H + n_kv:], bits if bits.numel() else None, 0, ctx.window, ctx.softcap, docs)
-        return dqkv, None, None, None, None, None, None, None
+                           dqkv[:, :, H + n_kv:], bits if bits.numel() else None, 0, ctx.window, ctx.softcap, docs,
+                           sk, ds, acc)
+        return dqkv, None, None, None, None, None, None, None, _dsinks_grad(sinks, ds, acc)
 
 
 _noted = set()
 
 
 def _note_math_path(S: int, D: int, dtype, window: Optional[int] = None, softcap: Optional[float] = None,
-                    docs: bool = False) -> None:
+                    docs: bool = False, sinks: bool = False) -> None:
     """Shapes outside the kernels' tiling use the eager math path; say so once per shape."""
     key = (S, D, dtype) if window is None else (S, D, dtype, "window")
     if softcap is not None:
         key += ("softcap",)
     if docs:
         key += ("documents",)
+    if sinks:
+        key += ("sinks",)
     if key not in _noted:
         _noted.add(key)
         import warnings
@@ -380,6 +449,9 @@ def _note_math_path(S: int, D: int, dtype, window: Optional[int] = None, softcap
         if docs:
             extra += " doc_bounds"
             tail += ".  Document-masked attention is native in bf16 only"
+        if sinks:
+            extra += " sinks"
+            tail += ".  Attention with sinks is native in bf16 only"
         warnings.warn(f"mipipe attention: S={S} D={D} {dtype}{extra} runs the eager math path (HIP kernels: bf16 "
                       "with S % 64 == 0, D in {64, 128, 256}; fp32 with S % 32 == 0, D in {64, 128})" + tail,
                       stacklevel=3)
@@ -454,6 +526,22 @@ def _generic_shape(t: Tensor, S: int, D: int, causal: bool, scale: float) -> Opt
     return run[0], run[1]
 
 
+def _sink_shape(t: Tensor, S: int, D: int, causal: bool, scale: float,
+                softcap: Optional[float]) -> Optional[Tuple[int, int, bool]]:
+    """(sequence length, head dim, key mask) a bf16 call with sinks runs at on the generic kernels, or None:
+    :func:`_generic_shape`, and without a cap also :func:`_run_shape`'s non-causal sequence end-padded behind the
+    spare-feature key mask (key mask True: the caller sets the feature).  The sink only raises the row's running
+    max, so a padded key's ``-32768 * scale`` underflows as it does without one."""
+    run = _generic_shape(t, S, D, causal, scale)
+    if run is not None:
+        return run[0], run[1], False
+    if softcap is None and not causal:
+        full = _run_shape(t, S, D, causal, scale)
+        if full is not None:
+            return full[0], full[1], True
+    return None
+
+
 def _pad_docs(docs: Tensor, S: int, sp: int) -> Tensor:
     """``docs [B, 2, S]`` for a sequence end-padded to ``sp``: the pad tokens ``[S, sp)`` are one trailing
     document (no real query sees them under the causal mask anyway).  Tensor ops only, no sync."""
@@ -467,9 +555,27 @@ def _pad_docs(docs: Tensor, S: int, sp: int) -> Tensor:
 
 
 def _packed_generic(qkv: Tensor, S: int, D: int, causal: bool, p: float, scale: float, window: Optional[int],
-                    softcap: Optional[float], docs: Optional[Tensor] = None) -> Tensor:
-    """:func:`attention_packed` with a window ``< S`` (causal), a soft cap and / or document bounds."""
-    if _window_native(qkv):
+                    softcap: Optional[float], docs: Optional[Tensor] = None,
+                    sinks: Optional[Tensor] = None) -> Tensor:
+    """:func:`attention_packed` with a window ``< S`` (causal), a soft cap, document bounds and / or sinks."""
+    if sinks is not None and _window_native(qkv):
+        run = _sink_shape(qkv, S, D, causal, scale, softcap)
+        if run is not None:
+            sp, dp, key_mask = run
+            if docs is not None:
+                docs = _pad_docs(docs.to(qkv.device), S, sp)
+            if (sp, dp) == (S, D):
+                return _AttentionPacked.apply(qkv.contiguous(), causal, p, scale, 0, window or 0, softcap or 0.0, docs,
+                                              sinks)
+            padded = F.pad(qkv, (0, dp - D, 0, 0, 0, 0, 0, sp - S))
+            if key_mask:  # mask the padded keys through the spare feature D, as attention_packed does
+                c = torch.zeros_like(padded)
+                c[:, :, 0, :, D] = 1.0
+                c[:, S:, 1, :, D] = _KEY_MASK
+                padded = padded + c
+            return _AttentionPacked.apply(padded, causal, p, scale, 0, window or 0, softcap or 0.0, docs,
+                                          sinks)[:, :S, :, :D]
+    elif _window_native(qkv):
         run = _generic_shape(qkv, S, D, causal, scale)
         if docs is not None and run is not None:
             docs = _pad_docs(docs.to(qkv.device), S, run[0])
@@ -482,17 +588,18 @@ def _packed_generic(qkv: Tensor, S: int, D: int, causal: bool, p: float, scale: 
                                           docs)[:, :S, :, :D]
     q, k, v = qkv.select(2, 0), qkv.select(2, 1), qkv.select(2, 2)
     if qkv.is_cuda:
-        _note_math_path(S, D, qkv.dtype, window, softcap, docs is not None)
+        _note_math_path(S, D, qkv.dtype, window, softcap, docs is not None, sinks is not None)
     o = attention_reference(q.transpose(1, 2), k.transpose(1, 2), v.transpose(1, 2), causal, p, scale, window=window,
-                            softcap=softcap, doc_bounds=docs)
+                            softcap=softcap, doc_bounds=docs, sinks=sinks)
     return o.transpose(1, 2)
 
 
 def attention_packed(qkv: Tensor, causal: bool = False, dropout_p: float = 0.0, training: bool = True,
                      scale: Optional[float] = None, *, window: Optional[int] = None,
-                     softcap: Optional[float] = None, doc_bounds: Optional[Tensor] = None) -> Tensor:
+                     softcap: Optional[float] = None, doc_bounds: Optional[Tensor] = None,
+                     sinks: Optional[Tensor] = None) -> Tensor:
     """``qkv [B, S, 3, H, D]`` -> ``o [B, S, H, D]``.  ``window``: sliding-window attention, ``softcap``: logit
-    soft-capping, ``doc_bounds``: document masks (module doc)."""
+    soft-capping, ``doc_bounds``: document masks, ``sinks``: attention sinks (module doc)."""
     B, S, three, H, D = qkv.shape
     assert three == 3
     p = float(dropout_p) if training else 0.0
@@ -500,8 +607,9 @@ def attention_packed(qkv: Tensor, causal: bool = False, dropout_p: float = 0.0, 
     window = _check_window(window, bool(causal), S)
     softcap = _check_softcap(softcap)
     docs = _check_docs(doc_bounds, bool(causal), B, S)
-    if window is not None or softcap is not None or docs is not None:
-        return _packed_generic(qkv, S, D, bool(causal), p, scale, window, softcap, docs)
+    sinks = _check_sinks(sinks, H, qkv.dtype)
+    if window is not None or softcap is not None or docs is not None or sinks is not None:
+        return _packed_generic(qkv, S, D, bool(causal), p, scale, window, softcap, docs, sinks)
     if qkv.is_cuda and _gpu_ok(qkv, S, D):
         return _AttentionPacked.apply(qkv.contiguous(), bool(causal), p, scale)
     run = _run_shape(qkv, S, D, bool(causal), scale) if qkv.is_cuda else None
@@ -539,10 +647,10 @@ def _expand_kv(qkv: Tensor, n_kv: int) -> Tensor:
 def attention_gqa_packed(qkv: Tensor, n_kv_heads: int, causal: bool = False, dropout_p: float = 0.0,
                          training: bool = True, scale: Optional[float] = None, *,
                          window: Optional[int] = None, softcap: Optional[float] = None,
-                         doc_bounds: Optional[Tensor] = None) -> Tensor:
+                         doc_bounds: Optional[Tensor] = None, sinks: Optional[Tensor] = None) -> Tensor:
     """``qkv [B, S, H + 2 Hkv, D]`` -> ``o [B, S, H, D]`` (grouped-query attention, ``Hkv = n_kv_heads``).
-    ``window``: sliding-window attention, ``softcap``: logit soft-capping, ``doc_bounds``: document masks
-    (module doc)."""
+    ``window``: sliding-window attention, ``softcap``: logit soft-capping, ``doc_bounds``: document masks,
+    ``sinks``: attention sinks, one per QUERY head (module doc)."""
     if qkv.dim() != 4:
         raise ValueError(f"attention_gqa_packed: qkv must be [B, S, H + 2 Hkv, D], got {tuple(qkv.shape)}")
     B, S, heads, D = qkv.shape
@@ -554,30 +662,36 @@ def attention_gqa_packed(qkv: Tensor, n_kv_heads: int, causal: bool = False, dro
     window = _check_window(window, bool(causal), S)
     softcap = _check_softcap(softcap)
     docs = _check_docs(doc_bounds, bool(causal), B, S)
+    sinks = _check_sinks(sinks, H, qkv.dtype)
     if n_kv == H:  # plain multi-head attention: the same bytes as [B, S, 3, H, D]
         return attention_packed(qkv.reshape(B, S, 3, H, D), causal, dropout_p, training, scale, window=window,
-                                softcap=softcap, doc_bounds=docs)
+                                softcap=softcap, doc_bounds=docs, sinks=sinks)
     if qkv.is_cuda and qkv.dtype == torch.bfloat16 and _gpu_ok(qkv, S, D):
         p = float(dropout_p) if training else 0.0
         scale = float(scale) if scale is not None else 1.0 / math.sqrt(D)
+        if sinks is not None:
+            return _AttentionGqaPacked.apply(qkv.contiguous(), n_kv, bool(causal), p, scale, window or 0,
+                                             softcap or 0.0,
+                                             None if docs is None else docs.to(qkv.device).contiguous(), sinks)
         if docs is not None:
             return _AttentionGqaPacked.apply(qkv.contiguous(), n_kv, bool(causal), p, scale, window or 0,
                                              softcap or 0.0, docs.to(qkv.device).contiguous())
         return _AttentionGqaPacked.apply(qkv.contiguous(), n_kv, bool(causal), p, scale, window or 0,
                                          softcap or 0.0)
+    # the repeated-head fallback: sinks are per query head already
     return attention_packed(_expand_kv(qkv, n_kv), causal, dropout_p, training, scale, window=window,
-                            softcap=softcap, doc_bounds=docs)
+                            softcap=softcap, doc_bounds=docs, sinks=sinks)
 
 
 def attention(
     q: Tensor, k: Tensor, v: Tensor, causal: bool = False, dropout_p: float = 0.0, training: bool = True,
     scale: Optional[float] = None, *, window: Optional[int] = None, softcap: Optional[float] = None,
-    doc_bounds: Optional[Tensor] = None,
+    doc_bounds: Optional[Tensor] = None, sinks: Optional[Tensor] = None,
 ) -> Tensor:
     """``q, k, v [B, H, S, D]`` -> ``[B, H, S, D]``.  ``k`` and ``v`` may have fewer heads, ``Hkv | H``
     (grouped-query attention): separate tensors do not share q's strides, so their heads are repeated
     (autograd sums each group's gradient).  ``window``: sliding-window attention, ``softcap``: logit
-    soft-capping, ``doc_bounds``: document masks (module doc)."""
+    soft-capping, ``doc_bounds``: document masks, ``sinks``: attention sinks (module doc)."""
     if k.shape[1] != q.shape[1]:
         if k.shape[1] != v.shape[1] or k.shape[1] <= 0 or q.shape[1] % k.shape[1] != 0:
             raise ValueError(f"attention: {k.shape[1]} / {v.shape[1]} K/V heads do not divide {q.shape[1]} query heads")
@@ -588,9 +702,33 @@ def attention(
     window = _check_window(window, bool(causal), q.shape[2])
     softcap = _check_softcap(softcap)
     docs = _check_docs(doc_bounds, bool(causal), q.shape[0], q.shape[2])
+    sinks = _check_sinks(sinks, q.shape[1], q.dtype)
     if not q.is_cuda:
-        return attention_reference(q, k, v, causal, p, scale, window=window, softcap=softcap, doc_bounds=docs)
+        return attention_reference(q, k, v, causal, p, scale, window=window, softcap=softcap, doc_bounds=docs,
+                                   sinks=sinks)
     S, D = q.shape[2], q.shape[3]
+    if sinks is not None:
+        causal = bool(causal)
+        run = _sink_shape(q, S, D, causal, scale, softcap) if _window_native(q) else None
+        if run is None:
+            _note_math_path(S, D, q.dtype, window, softcap, docs is not None, True)
+            return attention_reference(q, k, v, causal, p, scale, window=window, softcap=softcap, doc_bounds=docs,
+                                       sinks=sinks)
+        sp, dp, key_mask = run
+        if docs is not None:
+            docs = _pad_docs(docs.to(q.device), S, sp)
+        pad = (lambda t: F.pad(t, (0, dp - D, 0, sp - S))) if (sp, dp) != (S, D) else (lambda t: t)  # noqa: E731
+        qp, kp, vp = pad(q), pad(k), pad(v)
+        if key_mask:  # mask the padded keys through the spare feature D, as below
+            cq, ck = torch.zeros_like(qp), torch.zeros_like(kp)
+            cq[..., D] = 1.0
+            ck[:, :, S:, D] = _KEY_MASK
+            qp, kp = qp + cq, kp + ck
+        qs, ks, vs = (t.transpose(1, 2) for t in (qp, kp, vp))
+        if not (qs.stride() == ks.stride() == vs.stride()) or qs.stride(3) != 1:
+            qs, ks, vs = (t.contiguous() for t in (qs, ks, vs))
+        o = _Attention.apply(qs, ks, vs, causal, p, scale, 0, window or 0, softcap or 0.0, docs, sinks)
+        return o.transpose(1, 2)[:, :, :S, :D]
     if window is not None or softcap is not None or docs is not None:
         causal = bool(causal)
         run = _generic_shape(q, S, D, causal, scale) if _window_native(q) else None
