@@ -43,7 +43,7 @@ import torch.distributed as dist  # noqa: E402
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 
 from mipipe import ops  # noqa: E402
-from mipipe.models import CONFIGS  # noqa: E402
+from mipipe.models import CONFIGS, MOE_CONFIGS  # noqa: E402
 from mipipe.optim import FlatAdam  # noqa: E402
 from mipipe.parallel import PipelineEngine  # noqa: E402
 from mipipe.parallel.data_parallel import DataParallelGrads, make_pp_dp_groups  # noqa: E402
@@ -54,7 +54,7 @@ from mipipe.utils.checkpoint_io import load_training_state, rank_path, save_trai
 
 def parse(argv=None):
     ap = argparse.ArgumentParser()
-    ap.add_argument("--config", default="tiny", choices=sorted(CONFIGS))
+    ap.add_argument("--config", default="tiny", choices=sorted(CONFIGS) + sorted(MOE_CONFIGS))
     ap.add_argument("--layers", type=int, default=None)
     ap.add_argument("--pp", type=int, default=None, help="pipeline stages (default: world / dp)")
     ap.add_argument("--dp", type=int, default=1, help="data-parallel replicas of the pipeline")

@@ -33,7 +33,7 @@ from torch import nn
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 
 import mipipe  # noqa: E402
-from mipipe.models import CONFIGS, build_lm_blocks  # noqa: E402
+from mipipe.models import CONFIGS, MOE_CONFIGS, build_lm_blocks  # noqa: E402
 from mipipe.ops import cross_entropy  # noqa: E402
 from mipipe.optim import FlatAdam  # noqa: E402
 from mipipe.utils import data as D  # noqa: E402
@@ -43,7 +43,7 @@ from mipipe.utils import profiling as P  # noqa: E402
 def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("checkpoint", nargs="?", default="except_last", choices=["never", "except_last", "always"])
-    ap.add_argument("--config", default="ref_main", choices=sorted(CONFIGS))
+    ap.add_argument("--config", default="ref_main", choices=sorted(CONFIGS) + sorted(MOE_CONFIGS))
     ap.add_argument("--layers", type=int, default=None, help="override number of layers")
     ap.add_argument("--chunks", type=int, default=4)
     ap.add_argument("--partitions", type=int, default=None, help="pipeline stages (default: #GPUs, 2 on CPU)")

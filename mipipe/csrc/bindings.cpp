@@ -618,6 +618,171 @@ std::tuple<Tensor, std::optional<Tensor>, std::optional<Tensor>> py_qk_norm_rope
   return {dx, rq, rk};
 }
 
+// ------------------------------------------------------------------ mixture of experts
+void moe_check_i32(const Tensor& t, const Tensor& like, int64_t numel, const char* name, const char* what) {
+  check_cuda(t, what);
+  MP_CHECK(t.scalar_type() == at::kInt && t.device() == like.device() && t.numel() == numel, name, ": ", what,
+           " must be int32 with ", numel, " entries on the same device");
+}
+void moe_check_f32(const Tensor& t, const Tensor& like, int64_t numel, const char* name, const char* what) {
+  check_cuda(t, what);
+  MP_CHECK(t.scalar_type() == at::kFloat && t.device() == like.device() && t.numel() == numel, name, ": ", what,
+           " must be fp32 with ", numel, " entries on the same device");
+}
+void moe_check_rows(const Tensor& t, const char* name, const char* what) {
+  check_cuda(t, what);
+  MP_CHECK(t.dim() == 2, name, ": ", what, " must be 2-D");
+  MP_CHECK(t.scalar_type() == at::kBFloat16 || t.scalar_type() == at::kFloat, name, ": unsupported dtype ",
+           t.scalar_type());
+  const int64_t E = t.size(1);
+  MP_CHECK(E > 0 && E <= (1 << 24) && (E * t.element_size()) % 16 == 0, name, ": the width of ", what,
+           " must fill whole 16-byte vectors (a multiple of 8; fp32: of 4), got ", E);
+  MP_CHECK(reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0, name, ": ", what, " must be 16-byte aligned");
+}
+
+// (idx int32 [T, k], gate fp32 [T, k], probs_sum fp32 [Ne]) of logits [T, Ne].
+std::tuple<Tensor, Tensor, Tensor> py_moe_route_fwd(Tensor logits, int64_t k) {
+  const char* name = "moe_route_fwd";
+  check_cuda(logits, "logits");
+  MP_CHECK(logits.dim() == 2, name, ": logits must be [T, Ne]");
+  const int64_t T = logits.size(0), Ne = logits.size(1);
+  MP_CHECK(Ne <= 256 && k <= 8 && moe_route_supported((int)Ne, (int)k), name,
+           ": needs 2 <= Ne <= 256 and 1 <= k <= min(8, Ne), got Ne=", Ne, ", k=", k);
+  MP_CHECK(T * Ne < (int64_t(1) << 40), name, ": too many tokens");
+  at::hip::HIPGuardMasqueradingAsCUDA guard(logits.device());
+  auto idx = at::empty({T, k}, logits.options().dtype(at::kInt));
+  auto gate = at::empty({T, k}, logits.options().dtype(at::kFloat));
+  auto probs = at::empty({Ne}, logits.options().dtype(at::kFloat));
+  if (T == 0) {
+    probs.zero_();
+    return {idx, gate, probs};
+  }
+  const int nparts = moe_route_parts(T, (int)Ne);
+  auto part = at::empty({nparts, Ne}, logits.options().dtype(at::kFloat));
+  auto s = cur_stream(logits);
+  dispatch_fb(logits, name, [&](auto* tag) {
+    using T_ = std::remove_pointer_t<decltype(tag)>;
+    moe_route_fwd<T_>(cptr<T_>(logits), ptr<int32_t>(idx), ptr<float>(gate), ptr<float>(part), nparts, T, (int)Ne,
+                      (int)k, s);
+  });
+  reduce_parts(ptr<float>(part), nullptr, nparts, (int)Ne, probs.data_ptr(), nullptr, true, false, s);
+  return {idx, gate, probs};
+}
+
+Tensor py_moe_route_bwd(Tensor logits, Tensor idx, Tensor gate, Tensor dgate, std::optional<Tensor> dprobs) {
+  const char* name = "moe_route_bwd";
+  check_cuda(logits, "logits");
+  MP_CHECK(logits.dim() == 2 && idx.dim() == 2 && idx.size(0) == logits.size(0), name,
+           ": logits must be [T, Ne] and idx [T, k]");
+  const int64_t T = logits.size(0), Ne = logits.size(1), k = idx.size(1);
+  MP_CHECK(Ne <= 256 && k <= 8 && moe_route_supported((int)Ne, (int)k), name,
+           ": needs 2 <= Ne <= 256 and 1 <= k <= min(8, Ne), got Ne=", Ne, ", k=", k);
+  moe_check_i32(idx, logits, T * k, name, "idx");
+  moe_check_f32(gate, logits, T * k, name, "gate");
+  moe_check_f32(dgate, logits, T * k, name, "dgate");
+  if (dprobs.has_value()) moe_check_f32(*dprobs, logits, Ne, name, "dprobs");
+  at::hip::HIPGuardMasqueradingAsCUDA guard(logits.device());
+  auto dlogits = at::empty_like(logits);
+  auto s = cur_stream(logits);
+  dispatch_fb(logits, name, [&](auto* tag) {
+    using T_ = std::remove_pointer_t<decltype(tag)>;
+    moe_route_bwd<T_>(cptr<T_>(logits), cptr<int32_t>(idx), cptr<float>(gate), cptr<float>(dgate),
+                      optr<float>(dprobs), ptr<T_>(dlogits), T, (int)Ne, (int)k, s);
+  });
+  return dlogits;
+}
+
+// (slot int32 [T, k], src int32 [Ne * C], counts int32 [Ne]) of idx [T, k].
+std::tuple<Tensor, Tensor, Tensor> py_moe_assign(Tensor idx, int64_t n_experts, int64_t capacity) {
+  const char* name = "moe_assign";
+  check_cuda(idx, "idx");
+  MP_CHECK(idx.dim() == 2 && idx.scalar_type() == at::kInt, name, ": idx must be int32 [T, k]");
+  const int64_t T = idx.size(0), k = idx.size(1);
+  MP_CHECK(n_experts <= 256 && k <= 8 && moe_route_supported((int)n_experts, (int)k), name,
+           ": needs 2 <= Ne <= 256 and 1 <= k <= min(8, Ne), got Ne=", n_experts, ", k=", k);
+  MP_CHECK(capacity >= 1 && n_experts * capacity < (int64_t(1) << 31), name,
+           ": needs capacity >= 1 and Ne * capacity < 2^31, got ", capacity);
+  MP_CHECK(T * k < (int64_t(1) << 31), name, ": T * k must be below 2^31");
+  at::hip::HIPGuardMasqueradingAsCUDA guard(idx.device());
+  auto slot = at::empty({T, k}, idx.options());
+  auto src = at::empty({n_experts * capacity}, idx.options());
+  auto counts = at::empty({n_experts}, idx.options());
+  auto ws = at::empty({(int64_t)moe_assign_blocks(T, (int)k), n_experts}, idx.options());
+  moe_assign(cptr<int32_t>(idx), ptr<int32_t>(slot), ptr<int32_t>(src), ptr<int32_t>(counts), ptr<int32_t>(ws), T,
+             (int)k, (int)n_experts, (int)capacity, cur_stream(idx));
+  return {slot, src, counts};
+}
+
+// xe [nslots, E]: xe[s] = x[src[s] / k], zeros for an empty slot.
+Tensor py_moe_gather_slots(Tensor x, Tensor src, int64_t k) {
+  const char* name = "moe_gather_slots";
+  moe_check_rows(x, name, "x");
+  MP_CHECK(k >= 1 && k <= 8, name, ": k must be in [1, 8], got ", k);
+  const int64_t T = x.size(0), E = x.size(1), nslots = src.numel();
+  moe_check_i32(src, x, nslots, name, "src");
+  MP_CHECK(T * k < (int64_t(1) << 31) && nslots < (int64_t(1) << 31), name, ": T * k and the slots must be below 2^31");
+  at::hip::HIPGuardMasqueradingAsCUDA guard(x.device());
+  auto xe = at::empty({nslots, E}, x.options());
+  auto s = cur_stream(x);
+  dispatch_fb(x, name, [&](auto* tag) {
+    using T_ = std::remove_pointer_t<decltype(tag)>;
+    moe_gather_slots<T_>(cptr<T_>(x), cptr<int32_t>(src), ptr<T_>(xe), nslots, T, (int)k, (int)E, s);
+  });
+  return xe;
+}
+
+// y [T, E]: y[t] = res[t] + sum_j w[t, j] ye[slot[t, j]] (w fp32 [T, k] and res [T, E] optional).
+Tensor py_moe_gather_tokens(Tensor ye, Tensor slot, std::optional<Tensor> w, std::optional<Tensor> res) {
+  const char* name = "moe_gather_tokens";
+  moe_check_rows(ye, name, "ye");
+  check_cuda(slot, "slot");
+  MP_CHECK(slot.dim() == 2 && slot.size(1) >= 1 && slot.size(1) <= 8, name, ": slot must be [T, k] with k in [1, 8]");
+  const int64_t T = slot.size(0), k = slot.size(1), nslots = ye.size(0), E = ye.size(1);
+  moe_check_i32(slot, ye, T * k, name, "slot");
+  MP_CHECK(nslots < (int64_t(1) << 31), name, ": the slots must be below 2^31");
+  if (w.has_value()) moe_check_f32(*w, ye, T * k, name, "w");
+  if (res.has_value()) {
+    moe_check_rows(*res, name, "res");
+    check_same(ye, *res, "ye", "res");
+    MP_CHECK(res->size(0) == T && res->size(1) == E, name, ": res must be [T, E]");
+  }
+  at::hip::HIPGuardMasqueradingAsCUDA guard(ye.device());
+  auto y = at::empty({T, E}, ye.options());
+  auto s = cur_stream(ye);
+  dispatch_fb(ye, name, [&](auto* tag) {
+    using T_ = std::remove_pointer_t<decltype(tag)>;
+    moe_gather_tokens<T_>(cptr<T_>(ye), cptr<int32_t>(slot), optr<float>(w), optr<T_>(res), ptr<T_>(y), T, (int)k,
+                          nslots, (int)E, s);
+  });
+  return y;
+}
+
+// (dye [nslots, E], dgate fp32 [T, k]) of dy [T, E], ye [nslots, E], gate [T, k], src [nslots].
+std::tuple<Tensor, Tensor> py_moe_combine_bwd(Tensor dy, Tensor ye, Tensor gate, Tensor src) {
+  const char* name = "moe_combine_bwd";
+  moe_check_rows(dy, name, "dy");
+  moe_check_rows(ye, name, "ye");
+  check_same(dy, ye, "dy", "ye");
+  check_cuda(gate, "gate");
+  MP_CHECK(gate.dim() == 2 && gate.size(0) == dy.size(0) && gate.size(1) >= 1 && gate.size(1) <= 8, name,
+           ": gate must be [T, k] with k in [1, 8]");
+  const int64_t T = dy.size(0), E = dy.size(1), k = gate.size(1), nslots = ye.size(0);
+  MP_CHECK(ye.size(1) == E, name, ": dy and ye must have the same width");
+  moe_check_f32(gate, dy, T * k, name, "gate");
+  moe_check_i32(src, dy, nslots, name, "src");
+  MP_CHECK(T * k < (int64_t(1) << 31) && nslots < (int64_t(1) << 31), name, ": T * k and the slots must be below 2^31");
+  at::hip::HIPGuardMasqueradingAsCUDA guard(dy.device());
+  auto dye = at::empty_like(ye);
+  auto dgate = at::zeros({T, k}, gate.options());  // a dropped (t, j) keeps its 0
+  auto s = cur_stream(dy);
+  dispatch_fb(dy, name, [&](auto* tag) {
+    using T_ = std::remove_pointer_t<decltype(tag)>;
+    moe_combine_bwd<T_>(cptr<T_>(dy), cptr<T_>(ye), cptr<float>(gate), cptr<int32_t>(src), ptr<T_>(dye),
+                        ptr<float>(dgate), nslots, T, (int)k, (int)E, s);
+  });
+  return {dye, dgate};
+}
+
 // dkv [B, S, 2, H, D] (per-query-head dK / dV partials) summed per group into the K and V heads of
 // dqkv [B, S, H + 2 Hkv, D]; the Q heads of dqkv are not touched.
 void py_gqa_reduce_dkv(Tensor dkv, Tensor dqkv, int64_t H, int64_t Hkv) {
@@ -1896,6 +2061,18 @@ PYBIND11_MODULE(_C, m) {
         py::arg("wk"), py::arg("cos") = py::none(), py::arg("sin") = py::none(), py::arg("n_q"), py::arg("n_k"),
         py::arg("pos0") = 0, py::arg("acc_q") = py::none(), py::arg("acc_k") = py::none(),
         "(dx, dwq, dwk); a weight gradient with an fp32 accumulation target is added there and returned as None");
+  m.def("moe_route_supported",
+        [](int64_t n_experts, int64_t k) { return n_experts <= 256 && k <= 8 && moe_route_supported((int)n_experts, (int)k); });
+  m.def("moe_route_fwd", &py_moe_route_fwd, py::arg("logits"), py::arg("k"),
+        "logits [T, Ne] -> (idx int32 [T, k], gate fp32 [T, k], probs_sum fp32 [Ne])");
+  m.def("moe_route_bwd", &py_moe_route_bwd, py::arg("logits"), py::arg("idx"), py::arg("gate"), py::arg("dgate"),
+        py::arg("dprobs") = py::none());
+  m.def("moe_assign", &py_moe_assign, py::arg("idx"), py::arg("n_experts"), py::arg("capacity"),
+        "idx int32 [T, k] -> (slot int32 [T, k], src int32 [Ne * C], counts int32 [Ne])");
+  m.def("moe_gather_slots", &py_moe_gather_slots, py::arg("x"), py::arg("src"), py::arg("k"));
+  m.def("moe_gather_tokens", &py_moe_gather_tokens, py::arg("ye"), py::arg("slot"), py::arg("w") = py::none(),
+        py::arg("res") = py::none());
+  m.def("moe_combine_bwd", &py_moe_combine_bwd, py::arg("dy"), py::arg("ye"), py::arg("gate"), py::arg("src"));
   m.def("bias_act_fwd", &py_bias_act_fwd);
   m.def("softcap_fwd", &py_softcap_fwd, py::arg("x"), py::arg("cap"), py::arg("out") = py::none());
   m.def("softcap_bwd", &py_softcap_bwd, py::arg("dy"), py::arg("y"), py::arg("cap"), py::arg("out") = py::none());

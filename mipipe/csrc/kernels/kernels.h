@@ -155,6 +155,44 @@ void qknorm_rope_bwd(const T* dout, const T* x, const float* rstd, const T* wq, 
                      const float* sin_t, T* dx, float* part_q, float* part_k, int nparts, int64_t tokens, int S,
                      int n_q, int n_k, int n_v, int D, int pos0, hipStream_t s);
 
+// ------------------------------------------------------------------ mixture of experts (moe.hip)
+// T tokens, Ne experts, k experts per token, C slots per expert, a = t * k + j token t's j-th choice.  All index
+// tensors are int32; every kernel range-checks the indices it reads.  No float atomics: the same bits every run.
+bool moe_route_supported(int Ne, int k);  // 2 <= Ne <= 256, 1 <= k <= min(8, Ne)
+// Partial rows of probs_sum that moe_route_fwd writes (its grid).
+int moe_route_parts(int64_t tokens, int Ne);
+// logits [T, Ne] (finite or -inf, one finite value per row at least): idx [T, k] the k largest of a row in descending
+// order, the lower expert first among equal values; gate [T, k] the softmax over those k; part [nparts, Ne] per-block
+// sums over tokens of the full-row softmax, for reduce_parts.
+template <typename T>
+void moe_route_fwd(const T* logits, int32_t* idx, float* gate, float* part, int nparts, int64_t tokens, int Ne, int k,
+                   hipStream_t s);
+// dlogits [T, Ne]: gate_j (dgate_j - sum_i gate_i dgate_i) at the selected experts plus, with dprobs [Ne] (optional),
+// p (dprobs - <dprobs, p>) with p the row's full softmax.
+template <typename T>
+void moe_route_bwd(const T* logits, const int32_t* idx, const float* gate, const float* dgate, const float* dprobs,
+                   T* dlogits, int64_t tokens, int Ne, int k, hipStream_t s);
+// slot [T, k] = e * C + pos or -1 (pos >= C: dropped), src [Ne * C] = a or -1, counts [Ne] before the capacity; pos
+// is the number of earlier entries of the same expert in choice-major order (j first, then t).  ws: int32
+// [moe_assign_blocks(T, k), Ne].  Ne * C < 2^31 (the caller checks).
+int moe_assign_blocks(int64_t tokens, int k);
+void moe_assign(const int32_t* idx, int32_t* slot, int32_t* src, int32_t* counts, int32_t* ws, int64_t tokens, int k,
+                int Ne, int C, hipStream_t s);
+// xe [nslots, E]: xe[s] = x[src[s] / k], zeros where src[s] < 0.  E * sizeof(T) % 16 == 0, 16-byte aligned pointers.
+template <typename T>
+void moe_gather_slots(const T* x, const int32_t* src, T* xe, int64_t nslots, int64_t tokens, int k, int E,
+                      hipStream_t s);
+// y [T, E]: y[t] = res[t] + sum_j w[t, j] ye[slot[t, j]] over the slots >= 0, fp32 in j order, one rounding; w
+// (fp32 [T, k]) and res are optional.
+template <typename T>
+void moe_gather_tokens(const T* ye, const int32_t* slot, const float* w, const T* res, T* y, int64_t tokens, int k,
+                       int64_t nslots, int E, hipStream_t s);
+// One pass over the slots: dye[s] = gate[a] dy[t] (zeros for an empty slot) and dgate[a] = <dy[t], ye[s]>; dgate of
+// a dropped entry is not written (the caller zero-fills it).
+template <typename T>
+void moe_combine_bwd(const T* dy, const T* ye, const float* gate, const int32_t* src, T* dye, float* dgate,
+                     int64_t nslots, int64_t tokens, int k, int E, hipStream_t s);
+
 // ------------------------------------------------------------------ elementwise
 enum Activation : int { kActNone = 0, kActRelu = 1, kActGelu = 2 };
 // Backward-only activation code: the saved tensor IS act'(pre) (a GELU forward

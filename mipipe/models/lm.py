@@ -29,6 +29,7 @@ __all__ = [
     "Decoder",
     "LMConfig",
     "CONFIGS",
+    "MOE_CONFIGS",
     "build_lm_blocks",
     "sinusoidal_positions",
 ]
@@ -234,6 +235,11 @@ class LMConfig:
     attn_scale: Optional[float] = None  # score scale; None = head_dim ** -0.5 (Gemma-2: query_pre_attn_scalar ** -0.5)
     global_every: Optional[int] = None  # layer i is global (no window) when (i + 1) % n == 0; needs window
     attn_sinks: bool = False          # a learned logit per query head in the softmax's denominator (gpt-oss): [nhead]
+    # Mixture-of-experts MLP in every layer (Mixtral, Qwen3-MoE): None = the dense MLP
+    n_experts: Optional[int] = None   # experts per layer, each a gated MLP of width dim_feedforward
+    experts_per_token: int = 2        # experts a token runs, weighted by the softmax over their router logits
+    capacity_factor: Optional[float] = 1.25  # slots per expert = factor * tokens * k / n_experts; None drops nothing
+    moe_aux_coef: float = 0.01        # weight of the load-balancing term in the router's gradient
     qk_norm: bool = False             # per-head RMSNorm on Q and K before the rotation (Qwen3): two [head_dim] weights
 
     def __post_init__(self) -> None:
@@ -266,7 +272,11 @@ class LMConfig:
         nb = 1 if self.bias else 0
         norm = e * (2 if self.norm == "layer" else 1)
         qkv = self.qkv_dim()
-        layer = (qkv + self.attn_dim()) * e + 2 * norm + f1 * e + e * f + nb * (qkv + e + f1 + e)
+        if self.n_experts is not None:  # the router and the experts (bias-free) in place of the dense MLP
+            mlp = self.n_experts * (e + f1 * e + e * f)
+            layer = (qkv + self.attn_dim()) * e + 2 * norm + mlp + nb * (qkv + e)
+        else:
+            layer = (qkv + self.attn_dim()) * e + 2 * norm + f1 * e + e * f + nb * (qkv + e + f1 + e)
         if self.qk_norm:
             layer += 2 * self.head_width()
         if self.attn_sinks:
@@ -290,7 +300,53 @@ _GEMMA2_NOTE = ("Not Gemma-2's: the decoder is untied and keeps its (zero-initia
                 "rather than 1e-6 (the block's layer_norm_eps is not a config field), and the norm weights are "
                 "plain w rather than 1 + w")
 
-CONFIGS = {
+# Mixture-of-experts configs.  Their layers are three pipeline units (core, out, moe), not the four of every config
+# that CONFIGS lists, so they are kept apart: CONFIGS[name] finds them, a sweep over CONFIGS does not run into them.
+MOE_CONFIGS = {
+    # mistral_tiny with a mixture-of-experts MLP: 4 experts of width 512, every token runs its best 2.
+    "moe_tiny": LMConfig("moe_tiny", 2, 256, 4, 512, 1000, 192, dropout=0.0, activation="swiglu",
+                         norm_first=True, causal=True, scale_embedding=False, act_dropout=0.0, norm="rms",
+                         bias=False, rope=True, positions="none", n_kv_heads=2, window=48, n_experts=4,
+                         experts_per_token=2,
+                         notes="mistral_tiny plus a mixture-of-experts MLP (4 experts, top-2, capacity 1.25) for tests"),
+    # Mixtral 8x7B: mistral_7b's attention without the window, 8 experts of width 14336, top-2, 32768 tokens.
+    "mixtral_8x7b": LMConfig("mixtral_8x7b", 32, 4096, 32, 14336, 32000, 32768, dropout=0.0, activation="swiglu",
+                             norm_first=True, causal=True, scale_embedding=False, act_dropout=0.0, norm="rms",
+                             bias=False, rope=True, rope_base=1000000.0, positions="none", n_kv_heads=8,
+                             n_experts=8, experts_per_token=2,
+                             notes="Mixtral 8x7B's block; the decoder is untied and keeps its (zero-initialised) "
+                                   "bias"),
+    # Qwen3-30B-A3B: 48 layers, 32 query heads over 4 K/V heads of width 128 on d_model 2048, QK-norm, 128 experts of
+    # width 768, top-8.
+    "qwen3_30b_a3b": LMConfig("qwen3_30b_a3b", 48, 2048, 32, 768, 151936, 32768, dropout=0.0, activation="swiglu",
+                              norm_first=True, causal=True, scale_embedding=False, act_dropout=0.0, norm="rms",
+                              bias=False, rope=True, rope_base=1000000.0, positions="none", n_kv_heads=4,
+                              head_dim=128, qk_norm=True, n_experts=128, experts_per_token=8,
+                              notes="Qwen3-30B-A3B's block; the decoder is untied and keeps its (zero-initialised) "
+                                    "bias"),
+}
+
+
+class _ConfigTable(dict):
+    """``CONFIGS``: a dict of the dense configs that also answers for the mixture-of-experts ones by name.
+
+    ``CONFIGS[name]``, ``name in CONFIGS`` and ``CONFIGS.get(name)`` know every config, :data:`MOE_CONFIGS`
+    included (``bench.py --config moe_tiny``).  Iterating it (``keys``, ``items``, ``values``, ``len``) lists the
+    dense configs alone: code that sweeps the table relies on every entry's layer being the four units ``core,
+    out, mlp_in, mlp_out`` (or Gemma-2's ``core_global``), which a mixture-of-experts layer is not.  Sweep
+    ``MOE_CONFIGS`` as well where those are wanted."""
+
+    def __missing__(self, name):
+        return MOE_CONFIGS[name]
+
+    def __contains__(self, name) -> bool:
+        return dict.__contains__(self, name) or name in MOE_CONFIGS
+
+    def get(self, name, default=None):
+        return self[name] if name in self else default
+
+
+CONFIGS = _ConfigTable({
     # BASELINE.json config #2/#3: 12-layer TransformerEncoder d_model=4096 nhead=16.
     # dim_feedforward = d_model and dropout 0.2 follow the reference driver's
     # convention (main.py:116-120: nhid = emsize, dropout = 0.2); the LM
@@ -346,7 +402,8 @@ CONFIGS = {
                                   "30 (the Gemma-2 block itself -- head dim of its own, GeGLU, sandwich norms, local / "
                                   "global layers -- is gemma2_block_tiny)"),
     # mistral_tiny with attention sinks: every query head has a learned logit in its softmax's denominator, under
-    # the grouped-query heads and the window (gpt-oss's attention; its MoE MLP, QKV bias and YaRN are not here).
+    # the grouped-query heads and the window (gpt-oss's attention; its QKV bias, YaRN, expert biases and clamped
+    # SwiGLU are not here; the MoE MLP itself is moe_tiny's).
     "sink_tiny": LMConfig("sink_tiny", 2, 256, 4, 512, 1000, 192, dropout=0.0, activation="swiglu",
                           norm_first=True, causal=True, scale_embedding=False, act_dropout=0.0, norm="rms",
                           bias=False, rope=True, positions="none", n_kv_heads=2, window=48, attn_sinks=True,
@@ -375,11 +432,12 @@ CONFIGS = {
     # 27B: query_pre_attn_scalar is d_model / nhead = 144, not the head dim 128
     "gemma2_27b": LMConfig("gemma2_27b", 46, 4608, 32, 36864, 256000, 8192, **_GEMMA2, n_kv_heads=16, head_dim=128,
                            window=4096, attn_scale=144 ** -0.5, notes="Gemma-2 27B's block.  " + _GEMMA2_NOTE),
-}
+})
 
 
 def build_lm_blocks(cfg: LMConfig, *, device=None, dtype=None) -> List[nn.Module]:
-    """``[Encoder, attn0, mlp0, attn1, mlp1, ..., (FinalNorm), Decoder]``."""
+    """``[Encoder, attn0, mlp0, attn1, mlp1, ..., (FinalNorm), Decoder]``; with ``cfg.n_experts`` every ``mlp`` is a
+    :class:`~mipipe.models.transformer.MoEFeedForwardBlock`."""
     blocks: List[nn.Module] = [
         Encoder(cfg.vocab, cfg.d_model, cfg.dropout, max_len=max(cfg.seq_len, 1024),
                 positions=cfg.encoder_positions(), scale_embedding=cfg.scale_embedding,
@@ -390,8 +448,9 @@ def build_lm_blocks(cfg: LMConfig, *, device=None, dtype=None) -> List[nn.Module
                                  bias=cfg.bias, rope=cfg.rope, rope_base=cfg.rope_base, n_kv_heads=cfg.n_kv_heads,
                                  window=cfg.window, qk_norm=cfg.qk_norm, attn_softcap=cfg.attn_softcap,
                                  sandwich_norm=cfg.sandwich_norm, head_dim=cfg.head_dim, attn_scale=cfg.attn_scale,
-                                 global_every=cfg.global_every, attn_sinks=cfg.attn_sinks, device=device,
-                                 dtype=dtype)
+                                 global_every=cfg.global_every, attn_sinks=cfg.attn_sinks, n_experts=cfg.n_experts,
+                                 experts_per_token=cfg.experts_per_token, capacity_factor=cfg.capacity_factor,
+                                 moe_aux_coef=cfg.moe_aux_coef, device=device, dtype=dtype)
     if cfg.act_dropout is not None:
         for b in blocks:
             if isinstance(b, FeedForwardBlock):

@@ -57,6 +57,12 @@ A]``.  ``attn_scale`` (``None`` means ``1 / sqrt(D)``) is the score scale
 (Gemma-2's ``query_pre_attn_scalar ** -0.5``).  ``transformer_blocks`` also takes
 ``global_every=n``: layer ``i`` with ``(i + 1) % n == 0`` is a global layer, built
 without the window.
+
+``transformer_blocks(..., n_experts=Ne)`` replaces every layer's MLP with a
+:class:`MoEFeedForwardBlock` (Mixtral, Qwen3-MoE): ``Ne`` gated experts, a top-k
+softmax router with a fixed capacity per expert (``ops.moe_route`` /
+``moe_assign`` / ``moe_dispatch`` / ``moe_combine``) and a load-balancing term
+that reaches the router through its backward.
 """
 from __future__ import annotations
 
@@ -144,6 +150,7 @@ __all__ = [
     "PackedAttentionOutput",
     "SelfAttentionBlock",
     "FeedForwardBlock",
+    "MoEFeedForwardBlock",
     "FeedForwardIn",
     "FeedForwardOut",
     "PackedFeedForwardIn",
@@ -650,6 +657,110 @@ class FeedForwardBlock(nn.Module):
         return self.fc_in.flops_per_token(seq_len) + self.fc_out.flops_per_token(seq_len)
 
 
+class MoEFeedForwardBlock(nn.Module):
+    """Mixture-of-experts MLP half of a pre-norm layer (Mixtral, Qwen3-MoE): ``x + sum_j gate_j expert_{idx_j}(norm(x))``
+    with ``n_experts`` gated MLPs (``activation="swiglu"`` or ``"geglu"``) of which every token runs its
+    ``experts_per_token`` best, weighted by the softmax over their router logits.  Bias-free and pre-norm only, no
+    dropout inside.
+
+    Parameters: ``norm_weight``; a plain ``router_weight [Ne, E]`` (not a tagged GEMM weight: ``ops.linear`` runs it
+    with ``torch.matmul`` where the tile kernel does not fit); per expert ``experts_w1[e] [2F, E]`` (gate rows
+    first) and ``experts_w2[e] [E, F]``, each a GEMM weight of its own, so the flat optimizer, the deferred weight
+    gradients and the checkpoint files treat them like any other.
+
+    Forward: norm, router logits, ``ops.moe_route``, ``ops.moe_assign`` with ``C = ops.moe_capacity(T, Ne, k,
+    capacity_factor)`` slots per expert (``T`` the tokens of the call; ``capacity_factor=None`` drops nothing),
+    ``ops.moe_dispatch``, per expert ``ops.linear`` on its ``[C, E]`` rows, the gate kernel, ``ops.linear``, then
+    ``ops.moe_combine`` with the residual.  Every shape is static.  Empty slots hold zeros and produce zeros.
+
+    Load balancing (Switch / Mixtral): ``aux = Ne sum_e (counts_e / (T k)) (probs_sum_e / T)``.  It is not added to
+    the loss tensor; the block feeds its gradient ``aux_coef * aux_scale * Ne / (T^2 k) * counts`` into the router's
+    backward.  ``aux_scale`` (a float attribute, 1.0) is the factor the loss's own backward is seeded with:
+    :class:`~mipipe.parallel.engine.PipelineEngine` sets it to ``1 / (chunks * grad_divisor)`` on every block of its
+    modules; outside the engine set it yourself when the loss is scaled (gradient accumulation).  ``aux_coef=0``
+    turns the term off.  ``last_aux`` and ``last_drop_fraction`` are detached device scalars of the last forward,
+    for logging."""
+
+    def __init__(self, d_model: int, dim_feedforward: int, n_experts: int, experts_per_token: int = 2, *,
+                 capacity_factor: Optional[float] = 1.25, aux_coef: float = 0.01, activation: str = "swiglu",
+                 norm_first: bool = True, norm: str = "rms", layer_norm_eps: float = 1e-5, bias: bool = False,
+                 device=None, dtype=None) -> None:
+        super().__init__()
+        fk = {"device": device, "dtype": dtype}
+        if not norm_first or bias:
+            raise ValueError(f"MoEFeedForwardBlock is pre-norm and bias-free, got norm_first={norm_first}, bias={bias}")
+        if activation not in GATED_ACTS:
+            raise ValueError(f"MoEFeedForwardBlock: activation must be one of {GATED_ACTS}, got {activation!r}")
+        if isinstance(n_experts, bool) or not isinstance(n_experts, int) or not 2 <= n_experts <= ops.moe.MAX_EXPERTS:
+            raise ValueError(f"n_experts must be an int in [2, {ops.moe.MAX_EXPERTS}], got {n_experts!r}")
+        if (isinstance(experts_per_token, bool) or not isinstance(experts_per_token, int)
+                or not 1 <= experts_per_token <= min(ops.moe.MAX_TOP_K, n_experts)):
+            raise ValueError(f"experts_per_token must be an int in [1, min({ops.moe.MAX_TOP_K}, n_experts)], got "
+                             f"{experts_per_token!r}")
+        if capacity_factor is not None and not (math.isfinite(capacity_factor) and capacity_factor > 0):
+            raise ValueError(f"capacity_factor must be a finite number > 0 or None, got {capacity_factor!r}")
+        self.d_model, self.dim_feedforward = d_model, dim_feedforward
+        self.n_experts, self.experts_per_token = n_experts, experts_per_token
+        self.capacity_factor, self.aux_coef, self.aux_scale = capacity_factor, float(aux_coef), 1.0
+        self.activation, self.norm_first, self.norm, self.eps = activation, True, norm, layer_norm_eps
+        _init_norm(self, d_model, norm, fk)
+        self.router_weight = nn.Parameter(torch.empty(n_experts, d_model, **fk))
+        self.experts_w1 = nn.ParameterList(
+            [mark_gemm_weight(nn.Parameter(torch.empty(2 * dim_feedforward, d_model, **fk))) for _ in range(n_experts)])
+        self.experts_w2 = nn.ParameterList(
+            [mark_gemm_weight(nn.Parameter(torch.empty(d_model, dim_feedforward, **fk))) for _ in range(n_experts)])
+        self.last_aux: Optional[Tensor] = None
+        self.last_drop_fraction: Optional[Tensor] = None
+        self.reset_parameters()
+
+    def reset_parameters(self) -> None:
+        _reset_norm(self)
+        nn.init.normal_(self.router_weight, std=0.02)
+        for w in list(self.experts_w1) + list(self.experts_w2):
+            nn.init.kaiming_uniform_(w, a=math.sqrt(5))
+
+    def route(self, logits: Tensor, tokens: int):
+        """``(gate, slot, src, capacity)`` of the router ``logits [T, Ne]``; records the logging scalars and, when a
+        graph is recorded, attaches the load-balancing gradient to the gate."""
+        ne, k = self.n_experts, self.experts_per_token
+        idx, gate, probs_sum = ops.moe_route(logits, k)
+        cap = ops.moe_capacity(tokens, ne, k, self.capacity_factor)
+        slot, src, counts = ops.moe_assign(idx, ne, cap)
+        attach = self.aux_coef != 0.0 and torch.is_grad_enabled() and gate.requires_grad
+        with torch.no_grad():
+            load = counts.to(probs_sum.dtype)
+            self.last_aux = (load * probs_sum).sum() * (ne / (float(tokens) * tokens * k))
+            self.last_drop_fraction = (slot < 0).to(torch.float32).mean()
+            if attach:
+                dprobs = load * (self.aux_coef * self.aux_scale * ne / (float(tokens) * tokens * k))
+        if attach:
+            gate = ops.moe_attach_aux(gate, probs_sum, dprobs)
+        return gate, slot, src, cap
+
+    def experts(self, xe: Tensor, cap: int) -> Tensor:
+        """The experts on their ``[C, E]`` slices of ``xe [Ne * C, E]``."""
+        act = ops.swiglu if self.activation == "swiglu" else ops.geglu
+        outs = []
+        for e in range(self.n_experts):
+            h = act(ops.linear(xe[e * cap:(e + 1) * cap], self.experts_w1[e]))
+            outs.append(ops.linear(h, self.experts_w2[e]))
+        return torch.cat(outs)
+
+    def forward(self, x: Tensor) -> Tensor:
+        shape = x.shape
+        xn, xr = _norm_fanout(self, x) if FANOUT else (_norm(self, x, None, 0.0), x)
+        x2 = xn.reshape(-1, shape[-1])
+        tokens = x2.shape[0]
+        gate, slot, src, cap = self.route(ops.linear(x2, self.router_weight), tokens)
+        ye = self.experts(ops.moe_dispatch(x2, slot, src), cap)
+        return ops.moe_combine(ye, gate, slot, src, residual=xr.reshape(-1, shape[-1])).view(shape)
+
+    def flops_per_token(self, seq_len: int) -> float:
+        """The model's FLOPs: the router and the ``experts_per_token`` active experts, not the capacity padding."""
+        e, f = self.d_model, self.dim_feedforward
+        return 2 * e * self.n_experts + self.experts_per_token * (2 * e * 2 * f + 2 * e * f)
+
+
 class PackedFeedForwardIn(nn.Module):
     """Pipeline unit: ``x -> [.., E + F]`` holding x and h block-concatenated
     (all of x, then all of h: see :class:`_Unpack`)."""
@@ -791,15 +902,37 @@ def transformer_blocks(
     attn_scale: Optional[float] = None,
     global_every: Optional[int] = None,
     attn_sinks: bool = False,
+    n_experts: Optional[int] = None,
+    experts_per_token: int = 2,
+    capacity_factor: Optional[float] = 1.25,
+    moe_aux_coef: float = 0.01,
     device=None,
     dtype=None,
 ) -> List[nn.Module]:
     """``2 * num_layers`` single-tensor blocks (attention, MLP, attention, ...).
 
     ``global_every=n`` (needs ``window``): layer ``i`` (0-based) with ``(i + 1) % n == 0`` is a global layer,
-    built with ``window=None``; every other layer gets the window (:func:`layer_window`)."""
+    built with ``window=None``; every other layer gets the window (:func:`layer_window`).
+
+    ``n_experts=Ne`` (``None``: dense) builds a :class:`MoEFeedForwardBlock` of ``Ne`` experts of width
+    ``dim_feedforward`` in place of the :class:`FeedForwardBlock` of every layer (pre-norm, bias-free, gated
+    activation, no sandwich norm)."""
     check_global_every(global_every, window)
     blocks: List[nn.Module] = []
+    if n_experts is not None:
+        if sandwich_norm:
+            raise ValueError("n_experts (a mixture-of-experts MLP) does not combine with sandwich_norm")
+        for i in range(num_layers):
+            blocks.append(SelfAttentionBlock(d_model, nhead, dropout, norm_first=norm_first, causal=causal, norm=norm,
+                                             bias=bias, rope=rope, rope_base=rope_base, n_kv_heads=n_kv_heads,
+                                             window=layer_window(window, global_every, i), qk_norm=qk_norm,
+                                             attn_softcap=attn_softcap, head_dim=head_dim, attn_scale=attn_scale,
+                                             attn_sinks=attn_sinks, device=device, dtype=dtype))
+            blocks.append(MoEFeedForwardBlock(d_model, dim_feedforward, n_experts, experts_per_token,
+                                              capacity_factor=capacity_factor, aux_coef=moe_aux_coef,
+                                              activation=activation, norm_first=norm_first, norm=norm, bias=bias,
+                                              device=device, dtype=dtype))
+        return blocks
     for i in range(num_layers):
         layer = TransformerEncoderLayer(d_model, nhead, dim_feedforward, dropout, activation,
                                         norm_first=norm_first, causal=causal, norm=norm, bias=bias, rope=rope,
@@ -814,7 +947,8 @@ def transformer_blocks(
 def pipeline_units(blocks: List[nn.Module]) -> List[nn.Module]:
     """Expands every :class:`SelfAttentionBlock` and :class:`FeedForwardBlock`
     into its two packed halves so a pipeline stage boundary may fall inside it
-    (see :func:`merge_units`): 4 units per layer."""
+    (see :func:`merge_units`): 4 units per layer.  A :class:`MoEFeedForwardBlock` stays whole (its cut would
+    need the routing tables in the boundary tensor): 3 units per layer."""
     units: List[nn.Module] = []
     for b in blocks:
         if isinstance(b, SelfAttentionBlock):

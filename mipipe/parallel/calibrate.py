@@ -23,7 +23,8 @@ layers:
   halves) at its tail -- with the configured micro-batch count, checkpoint
   mode and optimizer step.  Differences of the stage times give a layer, the
   embedding and the decoder end in engine context; the layer is split into
-  its four units in the proportions the per-unit times give.
+  its units (four, or three with a mixture-of-experts MLP) in the proportions the
+  per-unit times give.
 
 Costs are ms per micro-batch.  With a process group up every rank measures and
 the costs are averaged (``all_reduce``), so all ranks derive one plan.  Results
@@ -275,7 +276,7 @@ def _engine_step_ms(cfg: LMConfig, a: int, b: int, split_decoder: bool, micro_ba
     return sorted(walls)[len(walls) // 2]
 
 
-LAYER_KINDS = ("core", "out", "mlp_in", "mlp_out")
+LAYER_KINDS = ("core", "out", "mlp_in", "mlp_out")  # a dense layer; mipipe.parallel.stage.layer_kinds(cfg) in general
 
 
 def measure_engine_costs(cfg: LMConfig, micro_batch: int, chunks: int, checkpoint: str = "never", *,
@@ -284,32 +285,33 @@ def measure_engine_costs(cfg: LMConfig, micro_batch: int, chunks: int, checkpoin
     """``{kind: ms per micro-batch}`` in engine context (module docstring):
     checkpoint recompute, the deferred weight-gradient flush, the optimizer
     step and the host's issue overhead included as a pipeline rank pays them."""
-    from .stage import UNITS_PER_LAYER, block_costs, split_allowed, unit_kind
+    from .stage import block_costs, layer_kinds, split_allowed, unit_kind
 
     device = torch.device(device)
     if cfg.num_layers < 3:
         raise ValueError("engine-context calibration needs >= 3 layers")
+    lk = layer_kinds(cfg)  # LAYER_KINDS for a dense config
     iso = measure_unit_times(cfg, micro_batch, chunks=min(chunks, 4), device=device, dtype=dtype,
-                             kinds=LAYER_KINDS + ("core_global", "norm", "dec", "dec_head", "dec_tail"))
+                             kinds=lk + ("core_global", "norm", "dec", "dec_head", "dec_tail"))
     rec = {"never": 0.0, "except_last": (chunks - 1) / chunks, "always": 1.0}[checkpoint]
     iso_cost = {k: f * (1.0 + rec) + b for k, (f, b) in iso.items()}
     per = lambda ms: ms / chunks  # noqa: E731  -- per micro-batch
     run = lambda a, b, split=False: per(_engine_step_ms(cfg, a, b, split, micro_batch, chunks, checkpoint,  # noqa: E731
                                                         device=device, dtype=dtype, steps=steps))
-    L = UNITS_PER_LAYER
+    L = len(lk)
     layer = run(1, 1 + 2 * L) / 2.0
     n = len(block_costs(cfg, False))
     norm = 1 if cfg.norm_first else 0
     if cfg.global_every is None:
         first = last = layer
-        tot = sum(iso_cost[k] for k in LAYER_KINDS)
-        out = {k: layer * iso_cost[k] / tot for k in LAYER_KINDS}
+        tot = sum(iso_cost[k] for k in lk)
+        out = {k: layer * iso_cost[k] / tot for k in lk}
     else:
         # local / global layers: the two timed layers (0 and 1) are shared out over their own kinds, and the
         # layers next to the encoder and the decoder are priced as what they are
-        kinds_of = lambda i: (unit_kind(cfg, 1 + L * i),) + LAYER_KINDS[1:]  # noqa: E731
+        kinds_of = lambda i: (unit_kind(cfg, 1 + L * i),) + lk[1:]  # noqa: E731
         scale = 2.0 * layer / sum(iso_cost[k] for i in (0, 1) for k in kinds_of(i))
-        out = {k: scale * iso_cost[k] for k in LAYER_KINDS + ("core_global",)}
+        out = {k: scale * iso_cost[k] for k in lk + ("core_global",)}
         first = sum(out[k] for k in kinds_of(0))
         last = sum(out[k] for k in kinds_of(cfg.num_layers - 1))
     out["enc"] = max(run(0, 1 + L) - first, 0.0)

@@ -62,6 +62,7 @@ from torch import Tensor, nn
 from .. import ops
 from ..ops.attention import clear_keep_words as _clear_keep_words
 from ..checkpoint import enable_checkpointing, enable_recomputing
+from ..models.transformer import MoEFeedForwardBlock
 from ..pipeline import checkpoint_stop_for
 from ..skip.tracker import use_skip_tracker
 from ..worker import label_range
@@ -167,7 +168,10 @@ class PipelineEngine:
             :func:`mipipe.debug.check_engine` compares a scheduled step with.
         grad_divisor: the backward is seeded with ``loss / (chunks * grad_divisor)``;
             data-parallel replicas pass their count, so the gradient all-reduce
-            SUM is the mean (:mod:`mipipe.parallel.data_parallel`).
+            SUM is the mean (:mod:`mipipe.parallel.data_parallel`).  Every
+            :class:`~mipipe.models.transformer.MoEFeedForwardBlock` of the
+            modules gets ``aux_scale = 1 / (chunks * grad_divisor)``, so its
+            load-balancing gradient is scaled like the loss's.
         transport: how activations and gradients move between ranks when the
             engine builds its own channels (:func:`make_transport`):
             ``"auto"`` (default: self-tested IPC links, every rank falling
@@ -222,6 +226,12 @@ class PipelineEngine:
         self.measure = measure
         self.defer_wgrad = defer_wgrad
         self.grad_divisor = float(grad_divisor)
+        # a mixture-of-experts block feeds its load-balancing gradient into its router's backward itself: it is
+        # scaled like the loss's own backward (_loss_seed)
+        for mod in mods:
+            for sub in mod.modules():
+                if isinstance(sub, MoEFeedForwardBlock):
+                    sub.aux_scale = 1.0 / (self.chunks * self.grad_divisor)
         self._seeds: Dict[tuple, Tensor] = {}
         if schedule == "1f1b" and self.virtual > 1:
             raise ValueError("1f1b supports one chunk per rank")

@@ -21,7 +21,8 @@ from ..models.transformer import GATED_ACTS, merge_units
 from ..models.vocab_split import STAT_SLOTS, split_point
 from ..ops.linear import mark_gemm_weight
 
-__all__ = ["StagePlan", "plan_stages", "block_costs", "stage_input_shape", "build_stage", "simulate_step", "choose_virtual"]
+__all__ = ["StagePlan", "plan_stages", "block_costs", "moe_cost", "layer_kinds", "stage_input_shape", "build_stage",
+           "simulate_step", "choose_virtual"]
 
 
 @dataclass
@@ -60,7 +61,8 @@ class StagePlan:
 def block_costs(cfg: LMConfig, split_decoder: bool = False) -> List[float]:
     """Training FLOPs per token of the pipeline units
     ``[Encoder, (attn core, attn out, mlp in, mlp out) x L, (final norm), Decoder]``
-    (see ``mipipe.models.transformer.pipeline_units``)."""
+    (see ``mipipe.models.transformer.pipeline_units``); a mixture-of-experts layer (``cfg.n_experts``) is
+    ``(attn core, attn out, moe)``, its MLP one unit (:func:`moe_cost`)."""
     e, f, s, v = cfg.d_model, cfg.dim_feedforward, cfg.seq_len, cfg.vocab
 
     def core_cost(w: Optional[int]) -> float:
@@ -79,8 +81,9 @@ def block_costs(cfg: LMConfig, split_decoder: bool = False) -> List[float]:
     enc = 3.0 * 40 * e  # gather + scatter-add traffic, expressed in FLOP-equivalents
     dec = 3.0 * (2 * e * v) + 3.0 * 4 * v  # GEMM + cross-entropy passes
     costs = [enc]
+    mlp = [mlp_in, mlp_out] if cfg.n_experts is None else [moe_cost(cfg)]
     for i in range(cfg.num_layers):  # a global layer's core (global_every) is priced without the window
-        costs += [core_cost(cfg.layer_window(i)), out, mlp_in, mlp_out]
+        costs += [core_cost(cfg.layer_window(i)), out] + mlp
     if cfg.norm_first:
         costs.append(3.0 * 10 * e)
     if split_decoder:
@@ -89,6 +92,22 @@ def block_costs(cfg: LMConfig, split_decoder: bool = False) -> List[float]:
     else:
         costs.append(dec)
     return costs
+
+
+def moe_cost(cfg: LMConfig, tokens: Optional[int] = None) -> float:
+    """The whole mixture-of-experts MLP unit, priced by what runs: the router GEMM, the experts' GEMMs and gate
+    pass over their PADDED rows -- ``Ne * C / T`` rows per token, ``C`` the capacity at ``tokens`` tokens per
+    micro-batch (default: 8 sequences, as :func:`boundary_terms`) -- and the traffic of the norm, the dispatch and
+    the combine (``k`` rows gathered per token each way, forward and backward)."""
+    from ..ops.moe import moe_capacity
+
+    e, f, ne, k = cfg.d_model, cfg.dim_feedforward, cfg.n_experts, cfg.experts_per_token
+    t = tokens if tokens is not None else 8 * cfg.seq_len
+    rows = ne * moe_capacity(t, ne, k, cfg.capacity_factor) / t
+    router = 3.0 * (2 * e * ne) + 3.0 * 10 * ne
+    experts = rows * (3.0 * (2 * e * 2 * f) + 3.0 * 10 * f + 3.0 * (2 * e * f))
+    passes = 3.0 * 10 * e + 3.0 * 5 * e * (rows + k)
+    return router + experts + passes
 
 
 def _rank_balanced(costs: List[float], ranks: int, virtual: int) -> List[int]:
@@ -374,22 +393,30 @@ def _unload_busiest(plan: StagePlan, costs: List[float], chunks: int, bwd_ratio:
     return StagePlan(bal, costs, virtual, plan.split_decoder)
 
 
-UNITS_PER_LAYER = 4  # attention core, attention output, mlp in, mlp out
+UNITS_PER_LAYER = 4  # attention core, attention output, mlp in, mlp out (a dense layer: see layer_kinds)
+LAYER_KINDS = ("core", "out", "mlp_in", "mlp_out")
+MOE_LAYER_KINDS = ("core", "out", "moe")  # the mixture-of-experts MLP is one unit
 CORE_KINDS = ("core", "core_global")  # the packed attention cores: local (or every layer's) and global
 
 
+def layer_kinds(cfg: LMConfig) -> Tuple[str, ...]:
+    """The unit kinds of one layer of ``cfg``, in order (a global layer's first is ``core_global``)."""
+    return LAYER_KINDS if cfg.n_experts is None else MOE_LAYER_KINDS
+
+
 def unit_kind(cfg: LMConfig, index: int, split_decoder: bool = False) -> str:
-    """``enc`` / ``core`` / ``out`` / ``mlp_in`` / ``mlp_out`` / ``norm`` / ``dec``
-    (``dec_head`` / ``dec_tail`` when the decoder is split).  Under ``cfg.global_every`` the core of a
+    """``enc`` / ``core`` / ``out`` / ``mlp_in`` / ``mlp_out`` (``moe`` in their place with ``cfg.n_experts``) /
+    ``norm`` / ``dec`` (``dec_head`` / ``dec_tail`` when the decoder is split).  Under ``cfg.global_every`` the core of a
     global layer is ``core_global``: it attends every key, so it is measured and priced on its own."""
     if index == 0:
         return "enc"
-    body = UNITS_PER_LAYER * cfg.num_layers
+    kinds = layer_kinds(cfg)
+    body = len(kinds) * cfg.num_layers
     if index <= body:
-        layer, part = divmod(index - 1, UNITS_PER_LAYER)
+        layer, part = divmod(index - 1, len(kinds))
         if part == 0 and cfg.global_every is not None and cfg.layer_window(layer) is None:
             return "core_global"
-        return ("core", "out", "mlp_in", "mlp_out")[part]
+        return kinds[part]
     rest = index - body - 1 - (1 if cfg.norm_first else 0)
     if rest < 0:
         return "norm"
