@@ -1318,8 +1318,9 @@ Tensor py_linear_dgrad(Tensor dy, Tensor w, std::optional<Tensor> res, std::opti
   MP_CHECK(act == kActNone || act == kActRelu || act == kActGelu || act == kActSavedGrad || act == kActReluBits,
            "linear_dgrad: bad act");
   if (act != kActNone) {
-    MP_CHECK(saved.has_value() && dt == at::kBFloat16 && !res, "linear_dgrad: the activation backward needs bf16 "
-             "operands, the saved tensor and no residual addend");
+    // (with `res`: dx = (dy . w) x act'(saved) + res, the order of the GEMM's store pass)
+    MP_CHECK(saved.has_value() && dt == at::kBFloat16, "linear_dgrad: the activation backward needs bf16 "
+             "operands and the saved tensor");
     if (act == kActReluBits) {
       check_cuda(*saved, "saved");
       MP_CHECK(saved->scalar_type() == at::kByte && saved->dim() == 2 && saved->size(0) == M &&

@@ -36,6 +36,7 @@
 //   kEpiStoreF32  -- fp32 store (first write of a step, split-K partials).
 #include <algorithm>
 #include <cstdlib>
+#include <stdexcept>
 #include <type_traits>
 
 #include "common.h"
@@ -516,71 +517,190 @@ __device__ __forceinline__ void epi_rows(const EpiParams ep, f32x4 (&acc)[8][NJ]
   }
 }
 
-// Writes the block's result through LDS (two halves: waves wm = 0, then 1):
-// each wave spills its 128 x W/4 accumulator tile into a [128][W+4] fp32
-// image (the 4-float row pad keeps the scattered 4-byte writes conflict-free),
-// then all 512 threads stream whole rows out with 16-byte accesses -- 8 bf16
-// per store (+ the bf16 addend `res`, read as 16-byte row chunks), fp32
-// read-modify-write (kEpiAccumF32) or fp32 stores.  Starts with the LDS free,
-// ends with a barrier (so it can run twice: aux, then the output).
-template <int EPI, int W>
-__device__ __forceinline__ void staged_store(char* smem, const f32x4 (&acc)[8][W / 64], int wm, int wn, int lane,
-                                             int tid, int m0, int n0, int M, int N, int64_t ldc, void* out,
-                                             const bf16_t* res, int64_t ldr = 0, const bf16_t* dact_in = nullptr,
-                                             int64_t ldd = 0, int dact = 0, float dact_scale = 1.f,
-                                             bool trans = false, bool dgelu = false) {
+// Side operand of the bf16 store pass, a compile-time mode of the kernel (the
+// launcher picks it from the GemmArgs fields), so a kernel carries the code of
+// its own mode only:
+//   kSideNone  -- nothing is read;
+//   kSideRes   -- + res (the bf16 addend);
+//   kSideBits  -- x the ReLU (+ dropout) bit mask (dact_in, kActReluBits), + res if given;
+//   kSideSaved -- x dact_scale act'(saved) (dact_in as bf16), + res if given.
+constexpr int kSideNone = 0, kSideRes = 1, kSideBits = 2, kSideSaved = 3;
+
+// The side operands as plain values (see EpiParams).
+struct SideArgs {
+  const bf16_t* res;
+  int64_t ldr;
+  const bf16_t* dact_in;
+  int64_t ldd;
+  int dact;
+  float dact_scale;
+};
+
+// An absent addend as registers: x + (-0) == x for every x, signed zeros
+// included, so the arithmetic below needs no branch on `res`.
+__device__ __forceinline__ bf16x8 neg_zero8() {
+  return __builtin_bit_cast(bf16x8, s16x8{(short)0x8000, (short)0x8000, (short)0x8000, (short)0x8000,
+                                          (short)0x8000, (short)0x8000, (short)0x8000, (short)0x8000});
+}
+
+// One 8-column chunk of the bf16 store pass: v x mask-or-act', then + res, then
+// one bf16 rounding.  The interior and the edge path both call this.
+template <int SIDE, bool RES>
+__device__ __forceinline__ bf16x8 side_apply(const f32x4 lo, const f32x4 hi, uint32_t mb, const bf16x8 sv,
+                                             const bf16x8 rv, int dact, float dact_scale) {
+  float v[8] = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+  if (SIDE == kSideBits) {  // the ReLU (+ dropout) mask as bits: one byte
+#pragma unroll
+    for (int e = 0; e < 8; ++e) v[e] *= (mb >> e) & 1 ? dact_scale : 0.f;
+  }
+  if (SIDE == kSideSaved) {  // activation backward: x act'(saved); one uniform branch per chunk, not per element
+    if (dact == kActSavedGrad) {
+#pragma unroll
+      for (int e = 0; e < 8; ++e) v[e] *= dact_scale * dact_f(kActSavedGrad, (float)sv[e]);
+    } else if (dact == kActRelu) {
+#pragma unroll
+      for (int e = 0; e < 8; ++e) v[e] *= dact_scale * dact_f(kActRelu, (float)sv[e]);
+    } else {
+#pragma unroll
+      for (int e = 0; e < 8; ++e) v[e] *= dact_scale * dact_f(kActGelu, (float)sv[e]);
+    }
+  }
+  if (RES) {
+#pragma unroll
+    for (int e = 0; e < 8; ++e) v[e] += (float)rv[e];
+  }
+  bf16x8 o;
+#pragma unroll
+  for (int e = 0; e < 8; ++e) o[e] = (__bf16)v[e];
+  return o;
+}
+
+// The accumulators of wave group `pass` into the [128][W+4] fp32 LDS image
+// (the 4-float row pad keeps the scattered 4-byte writes conflict-free).
+template <int W>
+__device__ __forceinline__ void spill_half(float* stg, const f32x4 (&acc)[8][W / 64], int pass, int wm, int wn,
+                                           int lane) {
   constexpr int NJ = W / 64, WN = 16 * NJ, kStride = W + 4;  // NJ: 16-wide accumulator tiles per wave
   const int quad = lane >> 4, col_in = lane & 15;
+  if (wm == pass) {
+#pragma unroll
+    for (int i = 0; i < 8; ++i)
+#pragma unroll
+      for (int j = 0; j < NJ; ++j)
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+          stg[(16 * i + 4 * quad + r) * kStride + wn * WN + 16 * j + col_in] = acc[i][j][r];
+  }
+}
+
+// staged_store's bf16 pass with a side operand, for a tile that lies wholly
+// inside M x N: straight-line code.  All side-operand loads of a pass are
+// issued before the accumulator spill and its barrier, which hide them; one
+// wait; then the LDS reads and the arithmetic of every chunk, and the pass's
+// stores back to back.  (A branch and a load per chunk made the compiler wait
+// vmcnt(0) per chunk, which on gfx9 also drains the chunk before's store: 16
+// serialised memory round trips per tile.)  Kept apart from the edge path: in
+// one control-flow graph with it, the wait counts of either leak into the other.
+template <int W, int SIDE, bool RES>
+__device__ __forceinline__ void staged_store_interior(char* smem, const f32x4 (&acc)[8][W / 64], int wm, int wn,
+                                                      int lane, int tid, int m0, int n0, int64_t ldc, bf16_t* C,
+                                                      const SideArgs sd) {
+  constexpr int kStride = W + 4, CPR = W / 8, NU = 128 * CPR / kThreads, RS = kThreads / CPR;  // RS: rows per step u
   float* stg = reinterpret_cast<float*>(smem);
+  const int crow = tid / CPR, c8 = tid % CPR;
+  const int col = n0 + 8 * c8;
 #pragma unroll
   for (int pass = 0; pass < 2; ++pass) {
-    if (wm == pass) {
+    const int64_t row = m0 + pass * 128 + crow;  // chunk u: row + u RS
+    bf16x8 rv[NU], sv[NU];
+    uint32_t mb[NU];
+    if (RES) {
+      const bf16_t* p = sd.res + row * sd.ldr + col;
 #pragma unroll
-      for (int i = 0; i < 8; ++i)
-#pragma unroll
-        for (int j = 0; j < NJ; ++j)
-#pragma unroll
-          for (int r = 0; r < 4; ++r)
-            stg[(16 * i + 4 * quad + r) * kStride + wn * WN + 16 * j + col_in] = acc[i][j][r];
+      for (int u = 0; u < NU; ++u) rv[u] = *reinterpret_cast<const bf16x8*>(p + u * RS * sd.ldr);
     }
+    if (SIDE == kSideBits) {
+      const uint8_t* p = reinterpret_cast<const uint8_t*>(sd.dact_in) + row * sd.ldd + (col >> 3);
+#pragma unroll
+      for (int u = 0; u < NU; ++u) mb[u] = p[u * RS * sd.ldd];
+    }
+    if (SIDE == kSideSaved) {
+      const bf16_t* p = sd.dact_in + row * sd.ldd + col;
+#pragma unroll
+      for (int u = 0; u < NU; ++u) sv[u] = *reinterpret_cast<const bf16x8*>(p + u * RS * sd.ldd);
+    }
+    spill_half<W>(stg, acc, pass, wm, wn, lane);
+    __syncthreads();
+    bf16x8 o[NU];
+    bf16_t* q = C + row * ldc + col;
+#pragma unroll
+    for (int u = 0; u < NU; ++u) {
+      const float* sp = stg + (crow + u * RS) * kStride + 8 * c8;
+      o[u] = side_apply<SIDE, RES>(*reinterpret_cast<const f32x4*>(sp), *reinterpret_cast<const f32x4*>(sp + 4), mb[u],
+                                   sv[u], rv[u], sd.dact, sd.dact_scale);
+      if (SIDE == kSideSaved) {
+        // act' one chunk at a time, each stored at once: interleaved over the pass's
+        // chunks, or with the results held back, its temporaries spill.  (No wait
+        // comes between the stores either way: every load was issued before them.)
+        *reinterpret_cast<bf16x8*>(q + u * RS * ldc) = o[u];
+        __builtin_amdgcn_sched_barrier(0);
+      }
+    }
+    if (SIDE != kSideSaved) {
+#pragma unroll
+      for (int u = 0; u < NU; ++u) *reinterpret_cast<bf16x8*>(q + u * RS * ldc) = o[u];
+    }
+    __syncthreads();
+  }
+}
+
+// Writes the block's result through LDS (two halves: waves wm = 0, then 1):
+// each wave spills its 128 x W/4 accumulator tile into the fp32 image
+// (spill_half), then all 512 threads stream whole rows out with 16-byte
+// accesses -- 8 bf16 per store, fp32 read-modify-write (kEpiAccumF32) or fp32
+// stores.  Starts with the LDS free, ends with a barrier.
+// bf16 with a side operand (SIDE, and RES: with the addend): interior tiles go
+// to staged_store_interior; edge tiles keep the per-chunk predicated loop
+// here, so nothing is loaded or stored for a row >= M or a column >= N.
+// Saved activation + addend stays on the predicated loop everywhere: the two
+// operands of a pass do not fit the registers beside the accumulators.
+template <int EPI, int W, int SIDE = kSideNone, bool RES = false>
+__device__ __forceinline__ void staged_store(char* smem, const f32x4 (&acc)[8][W / 64], int wm, int wn, int lane,
+                                             int tid, int m0, int n0, int M, int N, int64_t ldc, void* out,
+                                             const SideArgs sd, bool trans = false) {
+  constexpr int kStride = W + 4;
+  float* stg = reinterpret_cast<float*>(smem);
+  if constexpr (EPI == kEpiStoreBf16 && SIDE != kSideNone && !(SIDE == kSideSaved && RES)) {
+    if (m0 + BM <= M && n0 + W <= N) {  // block-uniform
+      staged_store_interior<W, SIDE, RES>(smem, acc, wm, wn, lane, tid, m0, n0, ldc, reinterpret_cast<bf16_t*>(out), sd);
+      return;
+    }
+  }
+#pragma unroll
+  for (int pass = 0; pass < 2; ++pass) {
+    spill_half<W>(stg, acc, pass, wm, wn, lane);
     __syncthreads();
     const int rbase = m0 + pass * 128;
     auto grow = [&](int R) { return rbase + R; };  // tile row of image row R
     if (EPI == kEpiStoreBf16) {
       bf16_t* C = reinterpret_cast<bf16_t*>(out);
       constexpr int CPR = W / 8;  // 128 rows x W/8 chunks of 8 columns
-#pragma unroll
+      constexpr int kEdgeUnroll = SIDE == kSideSaved ? 1 : 128 * CPR / kThreads;  // act' is long: its loop stays rolled
+#pragma unroll kEdgeUnroll
       for (int u = 0; u < 128 * CPR / kThreads; ++u) {
         const int idx = tid + u * kThreads;
         const int row = idx / CPR, c8 = idx % CPR;
-        if (grow(row) >= M || n0 + 8 * c8 >= N) continue;
-        const f32x4 lo = *reinterpret_cast<const f32x4*>(stg + row * kStride + 8 * c8);
-        const f32x4 hi = *reinterpret_cast<const f32x4*>(stg + row * kStride + 8 * c8 + 4);
-        const int64_t at = (int64_t)grow(row) * ldc + n0 + 8 * c8;
-        float v[8] = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-        if (dgelu) {  // GELU'(pre) for the backward instead of pre (GemmArgs::aux_grad)
-#pragma unroll
-          for (int e = 0; e < 8; ++e) v[e] = gelu_grad_f(v[e]);
-        }
-        if (dact_in != nullptr && dact == kActReluBits) {  // the ReLU (+ dropout) mask as bits: one byte
-          const uint32_t mb =
-              reinterpret_cast<const uint8_t*>(dact_in)[(int64_t)grow(row) * ldd + ((n0 + 8 * c8) >> 3)];
-#pragma unroll
-          for (int e = 0; e < 8; ++e) v[e] *= (mb >> e) & 1 ? dact_scale : 0.f;
-        } else if (dact_in != nullptr) {  // activation backward: x act'(saved)
-          const bf16x8 sv = *reinterpret_cast<const bf16x8*>(dact_in + (int64_t)grow(row) * ldd + n0 + 8 * c8);
-#pragma unroll
-          for (int e = 0; e < 8; ++e) v[e] *= dact_scale * dact_f(dact, (float)sv[e]);
-        }
-        if (res != nullptr) {
-          const bf16x8 rv = *reinterpret_cast<const bf16x8*>(res + (int64_t)grow(row) * ldr + n0 + 8 * c8);
-#pragma unroll
-          for (int e = 0; e < 8; ++e) v[e] += (float)rv[e];
-        }
-        bf16x8 o;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) o[e] = (__bf16)v[e];
-        *reinterpret_cast<bf16x8*>(C + at) = o;
+        const int col = n0 + 8 * c8;
+        if (grow(row) >= M || col >= N) continue;
+        const float* sp = stg + row * kStride + 8 * c8;
+        uint32_t mb = 0;
+        bf16x8 sv = {}, rv = {};
+        if (SIDE == kSideBits) mb = reinterpret_cast<const uint8_t*>(sd.dact_in)[(int64_t)grow(row) * sd.ldd + (col >> 3)];
+        if (SIDE == kSideSaved) sv = *reinterpret_cast<const bf16x8*>(sd.dact_in + (int64_t)grow(row) * sd.ldd + col);
+        if (RES) rv = *reinterpret_cast<const bf16x8*>(sd.res + (int64_t)grow(row) * sd.ldr + col);
+        *reinterpret_cast<bf16x8*>(C + (int64_t)grow(row) * ldc + col) =
+            side_apply<SIDE, RES>(*reinterpret_cast<const f32x4*>(sp), *reinterpret_cast<const f32x4*>(sp + 4), mb, sv,
+                                  rv, sd.dact, sd.dact_scale);
       }
     } else if (trans) {
       // C^T: element (row m, col n) to C[n * ldc + m].  Item (mq, n): rows
@@ -604,11 +724,11 @@ __device__ __forceinline__ void staged_store(char* smem, const f32x4 (&acc)[8][W
       }
     } else {
       float* C = reinterpret_cast<float*>(out);
-      constexpr int CPR = W / 4;  // 128 rows x W/4 chunks of 4 columns
+      constexpr int CPR4 = W / 4;  // 128 rows x W/4 chunks of 4 columns
 #pragma unroll
-      for (int u = 0; u < 128 * CPR / kThreads; ++u) {
+      for (int u = 0; u < 128 * CPR4 / kThreads; ++u) {
         const int idx = tid + u * kThreads;
-        const int row = idx / CPR, c4 = idx % CPR;
+        const int row = idx / CPR4, c4 = idx % CPR4;
         if (grow(row) >= M || n0 + 4 * c4 >= N) continue;
         const float4 v = *reinterpret_cast<const float4*>(stg + row * kStride + 4 * c4);
         float4* dst = reinterpret_cast<float4*>(C + (int64_t)grow(row) * ldc + n0 + 4 * c4);
@@ -635,91 +755,124 @@ __device__ __forceinline__ void staged_store(char* smem, const f32x4 (&acc)[8][W
 // (18432 x 6400 x 1600, GELU, p 0.1, pre saved) cost 542 us against 358 plain
 // (tools/epilogue_cost_probe.py).  Also the activation backward of a dgrad
 // whose forward had dropout (dact_in with the mask regenerated).
+// Everything the epilogue reads, as plain values (see EpiParams: read through a
+// GemmArgs reference, the kernel arguments were re-loaded after every store).
+struct ActParams {
+  bf16_t* C;
+  bf16_t* aux;
+  const bf16_t* res;
+  const bf16_t* dact_in;
+  uint8_t* bits;
+  int64_t ldc, ldr, ldd, ldbits, mask_ld;
+  uint64_t seed, offset;
+  int M, N, mask_row0, mask_col0, dact;
+  float pscale, dact_scale;
+  uint32_t thr16;
+  bool drop, aux_grad;
+};
+
+// One 4-row x 8-column block of the EXTRA epilogue.  INTERIOR (the tile lies
+// wholly inside M x N): straight-line; otherwise rows >= M are predicated off.
+// The block's dact_in / res rows are loaded together, ahead of its first store.
+template <int ACT, int W, bool INTERIOR, bool SIDE = true>
+__device__ __forceinline__ void act_block(const ActParams& a, const float* stg, int rq, int c8, int row0, int col) {
+  constexpr int kStride = W + 4;
+  bf16x8 sv[4], rv[4];
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    sv[r] = rv[r] = neg_zero8();
+    if (SIDE && (INTERIOR || row0 + r < a.M)) {
+      if (a.dact_in != nullptr) sv[r] = *reinterpret_cast<const bf16x8*>(a.dact_in + (int64_t)(row0 + r) * a.ldd + col);
+      if (a.res != nullptr) rv[r] = *reinterpret_cast<const bf16x8*>(a.res + (int64_t)(row0 + r) * a.ldr + col);
+    }
+  }
+  uint32_t wd[4][4];  // [column pair][row]: two 16-bit uniforms per word
+  if (a.drop) {
+    const uint64_t sub = drop_sub(row0 + a.mask_row0, col + a.mask_col0, a.mask_ld);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const uint4 w = Philox(a.seed, sub + e, a.offset).next4();
+      wd[e][0] = w.x; wd[e][1] = w.y; wd[e][2] = w.z; wd[e][3] = w.w;
+    }
+  }
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const int row = row0 + r;
+    if (!INTERIOR && row >= a.M) break;
+    const float* sp = stg + (4 * rq + r) * kStride + 8 * c8;
+    const f32x4 lo = *reinterpret_cast<const f32x4*>(sp);
+    const f32x4 hi = *reinterpret_cast<const f32x4*>(sp + 4);
+    const float pre[8] = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+    if (a.aux != nullptr) {
+      bf16x8 x;
+#pragma unroll
+      for (int e = 0; e < 8; ++e) x[e] = (__bf16)(ACT == kActGelu && a.aux_grad ? gelu_grad_f(pre[e]) : pre[e]);
+      *reinterpret_cast<bf16x8*>(a.aux + (int64_t)row * a.ldc + col) = x;
+    }
+    float v[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      float o = ACT == kActRelu ? fmaxf(pre[e], 0.f) : (ACT == kActGelu ? gelu_f(pre[e]) : pre[e]);
+      if (a.drop) o = drop_keep(wd[e >> 1][r], e & 1, a.thr16) ? o * a.pscale : 0.f;
+      v[e] = o;
+    }
+    if (SIDE && a.dact_in != nullptr) {
+#pragma unroll
+      for (int e = 0; e < 8; ++e) v[e] *= a.dact_scale * dact_f(a.dact, (float)sv[r][e]);
+    }
+    if (SIDE) {
+#pragma unroll
+      for (int e = 0; e < 8; ++e) v[e] += (float)rv[r][e];  // -0 where there is no addend
+    }
+    bf16x8 o;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) o[e] = (__bf16)v[e];
+    *reinterpret_cast<bf16x8*>(a.C + (int64_t)row * a.ldc + col) = o;
+    if (a.bits != nullptr) {  // the output's nonzeros, for the consumer's dgrad (kActReluBits)
+      uint32_t mb = 0;
+#pragma unroll
+      for (int e = 0; e < 8; ++e) mb |= (v[e] != 0.f ? 1u : 0u) << e;
+      a.bits[(int64_t)row * a.ldbits + (col >> 3)] = (uint8_t)mb;
+    }
+  }
+}
+
 template <int ACT, int W>
 __device__ __forceinline__ void staged_store_act(char* smem, const f32x4 (&acc)[8][W / 64], int wm, int wn,
-                                                 int lane, int tid, int m0, int n0, const GemmArgs& g) {
-  constexpr int NJ = W / 64, WN = 16 * NJ, kStride = W + 4, CB = W / 8;
-  const int quad = lane >> 4, col_in = lane & 15;
+                                                 int lane, int tid, int m0, int n0, const ActParams a) {
+  constexpr int CB = W / 8;
   float* stg = reinterpret_cast<float*>(smem);
-  bf16_t* C = reinterpret_cast<bf16_t*>(g.C);
-  bf16_t* aux = reinterpret_cast<bf16_t*>(g.aux);
-  const bf16_t* res = reinterpret_cast<const bf16_t*>(g.res);
-  const bf16_t* dact_in = reinterpret_cast<const bf16_t*>(g.dact_in);
-  const int64_t ldr = g.ldr > 0 ? g.ldr : g.ldc;
-  const bool drop = g.p > 0.f;
-  const float pscale = drop ? 1.f / (1.f - g.p) : 1.f;
-  const int64_t mask_ld = g.mask_ld > 0 ? g.mask_ld : g.N;
-  const uint32_t thr16 = g.threshold >> 16;
-#pragma unroll
+  const bool interior = m0 + BM <= a.M && n0 + W <= a.N;  // block-uniform
+  const bool plain = a.dact_in == nullptr && a.res == nullptr;
+  // (the pass loop and the block loops are left rolled: unrolled,
+  // the Philox-heavy block body is compiled eight times over and the kernel
+  // outgrows the instruction cache)
+#pragma unroll 1
   for (int pass = 0; pass < 2; ++pass) {
-    if (wm == pass) {
-#pragma unroll
-      for (int i = 0; i < 8; ++i)
-#pragma unroll
-        for (int j = 0; j < NJ; ++j)
-#pragma unroll
-          for (int r = 0; r < 4; ++r)
-            stg[(16 * i + 4 * quad + r) * kStride + wn * WN + 16 * j + col_in] = acc[i][j][r];
-    }
+    spill_half<W>(stg, acc, pass, wm, wn, lane);
     __syncthreads();
     const int rbase = m0 + pass * 128;
-#pragma unroll
-    for (int u = 0; u < 32 * CB / kThreads; ++u) {
-      const int idx = tid + u * kThreads;
-      const int rq = idx / CB, c8 = idx % CB;  // consecutive lanes on consecutive 8-column chunks
-      const int col = n0 + 8 * c8;
-      const int row0 = rbase + 4 * rq;
-      if (col >= g.N || row0 >= g.M) continue;
-      uint32_t wd[4][4];  // [column pair][row]: two 16-bit uniforms per word
-      if (drop) {
-        const uint64_t sub = drop_sub(row0 + g.mask_row0, col + g.mask_col0, mask_ld);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const uint4 w = Philox(g.seed, sub + e, g.offset).next4();
-          wd[e][0] = w.x; wd[e][1] = w.y; wd[e][2] = w.z; wd[e][3] = w.w;
-        }
+    if (interior && plain) {  // no side operand (the forward with dropout): nothing is loaded, stores only
+#pragma unroll 1
+      for (int u = 0; u < 32 * CB / kThreads; ++u) {
+        const int idx = tid + u * kThreads;
+        const int rq = idx / CB, c8 = idx % CB;  // consecutive lanes on consecutive 8-column chunks
+        act_block<ACT, W, true, false>(a, stg, rq, c8, rbase + 4 * rq, n0 + 8 * c8);
       }
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int row = row0 + r;
-        if (row >= g.M) break;
-        const float* sp = stg + (4 * rq + r) * kStride + 8 * c8;
-        const f32x4 lo = *reinterpret_cast<const f32x4*>(sp);
-        const f32x4 hi = *reinterpret_cast<const f32x4*>(sp + 4);
-        const float pre[8] = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-        if (aux != nullptr) {
-          bf16x8 a;
-#pragma unroll
-          for (int e = 0; e < 8; ++e) a[e] = (__bf16)(ACT == kActGelu && g.aux_grad ? gelu_grad_f(pre[e]) : pre[e]);
-          *reinterpret_cast<bf16x8*>(aux + (int64_t)row * g.ldc + col) = a;
-        }
-        float v[8];
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          float o = ACT == kActRelu ? fmaxf(pre[e], 0.f) : (ACT == kActGelu ? gelu_f(pre[e]) : pre[e]);
-          if (drop) o = drop_keep(wd[e >> 1][r], e & 1, thr16) ? o * pscale : 0.f;
-          v[e] = o;
-        }
-        if (dact_in != nullptr) {
-          const bf16x8 sv = *reinterpret_cast<const bf16x8*>(dact_in + (int64_t)row * g.ldd + col);
-#pragma unroll
-          for (int e = 0; e < 8; ++e) v[e] *= g.dact_scale * dact_f(g.dact, (float)sv[e]);
-        }
-        if (res != nullptr) {
-          const bf16x8 rv = *reinterpret_cast<const bf16x8*>(res + (int64_t)row * ldr + col);
-#pragma unroll
-          for (int e = 0; e < 8; ++e) v[e] += (float)rv[e];
-        }
-        bf16x8 o;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) o[e] = (__bf16)v[e];
-        *reinterpret_cast<bf16x8*>(C + (int64_t)row * g.ldc + col) = o;
-        if (g.bits != nullptr) {  // the output's nonzeros, for the consumer's dgrad (kActReluBits)
-          uint32_t mb = 0;
-#pragma unroll
-          for (int e = 0; e < 8; ++e) mb |= (v[e] != 0.f ? 1u : 0u) << e;
-          reinterpret_cast<uint8_t*>(g.bits)[(int64_t)row * g.ldbits + (col >> 3)] = (uint8_t)mb;
-        }
+    } else if (interior) {
+#pragma unroll 1
+      for (int u = 0; u < 32 * CB / kThreads; ++u) {
+        const int idx = tid + u * kThreads;
+        const int rq = idx / CB, c8 = idx % CB;
+        act_block<ACT, W, true>(a, stg, rq, c8, rbase + 4 * rq, n0 + 8 * c8);
+      }
+    } else {
+#pragma unroll 1
+      for (int u = 0; u < 32 * CB / kThreads; ++u) {
+        const int idx = tid + u * kThreads;
+        const int rq = idx / CB, c8 = idx % CB;
+        const int col = n0 + 8 * c8, row0 = rbase + 4 * rq;
+        if (col < a.N && row0 < a.M) act_block<ACT, W, false>(a, stg, rq, c8, row0, col);
       }
     }
     __syncthreads();
@@ -757,7 +910,7 @@ __device__ __forceinline__ void staged_store_act(char* smem, const f32x4 (&acc)[
 // plain kernels keep their register allocation.
 constexpr int kXEmit = 1, kXColsum = 2;
 
-template <bool A_KC, bool B_KC, int EPI, int ACT, int W, bool EXTRA, int X = 0>
+template <bool A_KC, bool B_KC, int EPI, int ACT, int W, bool EXTRA, int X = 0, int SIDE = kSideNone>
 __global__ void __launch_bounds__(kThreads, 1) gemm256_kernel(GemmArgs g) {
   constexpr int NJ = W / 64;          // 16-wide MFMA column tiles per wave
   constexpr int WN = W / 4;           // wave tile width
@@ -1164,51 +1317,68 @@ __global__ void __launch_bounds__(kThreads, 1) gemm256_kernel(GemmArgs g) {
   //    (The earlier direct 2-byte bf16 stores cost ~5 us per 256x256 tile at
   //    K = 64 more than this path: tools/gemm_k_sweep.py.)
   const int quad = lane >> 4, col_in = lane & 15;
+  // The lane's NJ bias columns: one uniform branch, the loads issued together
+  // ahead of the barrier (which hides them) and waited for once.  Columns
+  // past N read the last valid entry: their results are never stored.
+  uint32_t braw[NJ];
+#pragma unroll
+  for (int j = 0; j < NJ; ++j) braw[j] = 0;
+  if (EPI == kEpiStoreBf16 && g.bias != nullptr) {
+    const bf16_t* bp = reinterpret_cast<const bf16_t*>(g.bias);
+    const int ncol = n0 + wn * WN + col_in, last = g.N - 1;
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) braw[j] = bp[min(ncol + 16 * j, last)];
+  }
   __syncthreads();  // every wave is done reading the operand buffers
-  if (EPI == kEpiStoreBf16 && EXTRA) {  // dropout and / or aux: the staged-layout epilogue does it all
-    const int ncol = n0 + wn * WN + col_in;
+  float bias[NJ];
+#pragma unroll
+  for (int j = 0; j < NJ; ++j) {
+    // pins the first use below the barrier (the conversion is otherwise hoisted
+    // into the branch above, and its wait with it)
+    if (EPI == kEpiStoreBf16) asm volatile("" : "+v"(braw[j]));
+    bias[j] = __uint_as_float(braw[j] << 16);
+  }
+  if constexpr (EPI == kEpiStoreBf16 && EXTRA) {  // dropout and / or aux: the staged-layout epilogue does it all
     if (g.bias != nullptr) {
 #pragma unroll
-      for (int j = 0; j < NJ; ++j) {
-        const float b = ncol + 16 * j < g.N ? bf2f(reinterpret_cast<const bf16_t*>(g.bias)[ncol + 16 * j]) : 0.f;
+      for (int j = 0; j < NJ; ++j)
 #pragma unroll
-        for (int i = 0; i < 8; ++i) acc[i][j] += b;
-      }
+        for (int i = 0; i < 8; ++i) acc[i][j] += bias[j];
     }
-    staged_store_act<ACT, W>(smem, acc, wm, wn, lane, tid, m0, n0, g);
+    const bool drop = g.p > 0.f;
+    const ActParams ap{reinterpret_cast<bf16_t*>(g.C), reinterpret_cast<bf16_t*>(g.aux),
+                       reinterpret_cast<const bf16_t*>(g.res), reinterpret_cast<const bf16_t*>(g.dact_in),
+                       reinterpret_cast<uint8_t*>(g.bits), g.ldc, g.ldr > 0 ? g.ldr : g.ldc, g.ldd, g.ldbits,
+                       g.mask_ld > 0 ? g.mask_ld : g.N, g.seed, g.offset, g.M, g.N, g.mask_row0, g.mask_col0, g.dact,
+                       drop ? 1.f / (1.f - g.p) : 1.f, g.dact_scale, g.threshold >> 16, drop, g.aux_grad};
+    staged_store_act<ACT, W>(smem, acc, wm, wn, lane, tid, m0, n0, ap);
     return;
+  } else {
+    if (EPI == kEpiStoreBf16 && (ACT != kActNone || g.bias != nullptr)) {
+      const int ncol = n0 + wn * WN + col_in, nrow = m0 + wm * 128 + 4 * quad;
+      const float pscale = g.p > 0.f ? 1.f / (1.f - g.p) : 1.f;
+      const EpiParams ep{g.seed, g.offset, g.N, g.p, pscale, g.threshold, g.mask_row0, g.mask_col0,
+                         g.mask_ld > 0 ? g.mask_ld : g.N};
+      epi_rows<0, ACT, NJ, EXTRA>(ep, acc, nrow, ncol, bias);
+      epi_rows<1, ACT, NJ, EXTRA>(ep, acc, nrow, ncol, bias);
+      epi_rows<2, ACT, NJ, EXTRA>(ep, acc, nrow, ncol, bias);
+      epi_rows<3, ACT, NJ, EXTRA>(ep, acc, nrow, ncol, bias);
+      epi_rows<4, ACT, NJ, EXTRA>(ep, acc, nrow, ncol, bias);
+      epi_rows<5, ACT, NJ, EXTRA>(ep, acc, nrow, ncol, bias);
+      epi_rows<6, ACT, NJ, EXTRA>(ep, acc, nrow, ncol, bias);
+      epi_rows<7, ACT, NJ, EXTRA>(ep, acc, nrow, ncol, bias);
+    }
+    void* out = EPI == kEpiStoreBf16 ? g.C
+                                     : reinterpret_cast<void*>(reinterpret_cast<float*>(g.C) +
+                                                               (int64_t)blockIdx.y * g.M * g.ldc);  // split-K partial y
+    const SideArgs sd{reinterpret_cast<const bf16_t*>(g.res), g.ldr, reinterpret_cast<const bf16_t*>(g.dact_in), g.ldd,
+                      g.dact, g.dact_scale};
+    if (SIDE >= kSideBits && sd.res != nullptr)  // the activation backward's optional addend
+      staged_store<EPI, W, SIDE, SIDE >= kSideBits>(smem, acc, wm, wn, lane, tid, m0, n0, g.M, g.N, g.ldc, out, sd);
+    else
+      staged_store<EPI, W, SIDE, SIDE == kSideRes>(smem, acc, wm, wn, lane, tid, m0, n0, g.M, g.N, g.ldc, out, sd,
+                                                   EPI != kEpiStoreBf16 && g.trans_c && g.k_splits <= 1);
   }
-  if (EPI == kEpiStoreBf16 && (ACT != kActNone || g.bias != nullptr)) {
-    const int ncol = n0 + wn * WN + col_in, nrow = m0 + wm * 128 + 4 * quad;
-    const float pscale = g.p > 0.f ? 1.f / (1.f - g.p) : 1.f;
-    const EpiParams ep{g.seed, g.offset, g.N, g.p, pscale, g.threshold, g.mask_row0, g.mask_col0,
-                       g.mask_ld > 0 ? g.mask_ld : g.N};
-    float bias[NJ];  // the lane's NJ columns: loaded once, all in flight together
-#pragma unroll
-    for (int j = 0; j < NJ; ++j)
-      bias[j] = (g.bias != nullptr && ncol + 16 * j < g.N) ? bf2f(reinterpret_cast<const bf16_t*>(g.bias)[ncol + 16 * j]) : 0.f;
-    epi_rows<0, ACT, NJ, EXTRA>(ep, acc, nrow, ncol, bias);
-    epi_rows<1, ACT, NJ, EXTRA>(ep, acc, nrow, ncol, bias);
-    epi_rows<2, ACT, NJ, EXTRA>(ep, acc, nrow, ncol, bias);
-    epi_rows<3, ACT, NJ, EXTRA>(ep, acc, nrow, ncol, bias);
-    epi_rows<4, ACT, NJ, EXTRA>(ep, acc, nrow, ncol, bias);
-    epi_rows<5, ACT, NJ, EXTRA>(ep, acc, nrow, ncol, bias);
-    epi_rows<6, ACT, NJ, EXTRA>(ep, acc, nrow, ncol, bias);
-    epi_rows<7, ACT, NJ, EXTRA>(ep, acc, nrow, ncol, bias);
-  }
-  void* out = EPI == kEpiStoreBf16 ? g.C
-                                   : reinterpret_cast<void*>(reinterpret_cast<float*>(g.C) +
-                                                             (int64_t)blockIdx.y * g.M * g.ldc);  // split-K partial y
-  if (EPI == kEpiStoreBf16 && g.dact_in != nullptr)
-    staged_store<EPI, W>(smem, acc, wm, wn, lane, tid, m0, n0, g.M, g.N, g.ldc, out,
-                         reinterpret_cast<const bf16_t*>(g.res), g.ldr, reinterpret_cast<const bf16_t*>(g.dact_in),
-                         g.ldd, g.dact, g.dact_scale);
-  else if (EPI != kEpiStoreBf16 && g.trans_c && g.k_splits <= 1)
-    staged_store<EPI, W>(smem, acc, wm, wn, lane, tid, m0, n0, g.M, g.N, g.ldc, out, nullptr, 0, nullptr, 0, 0, 1.f,
-                         true);
-  else
-    staged_store<EPI, W>(smem, acc, wm, wn, lane, tid, m0, n0, g.M, g.N, g.ldc, out,
-                         EPI == kEpiStoreBf16 ? reinterpret_cast<const bf16_t*>(g.res) : nullptr, g.ldr);
 }
 
 }  // namespace big
@@ -1247,41 +1417,69 @@ int big_width(const GemmArgs& g) {
   return 0.75 * r128 < 1.0 * r256 ? 128 : 256;
 }
 
-template <bool A_KC, bool B_KC, int EPI, int ACT, int W, bool EXTRA, int X = 0>
+template <bool A_KC, bool B_KC, int EPI, int ACT, int W, bool EXTRA, int X = 0, int SIDE = big::kSideNone>
 void launch_big(const GemmArgs& g, hipStream_t s) {
   constexpr int smem = big::smem_bytes<B_KC, W>();
   static bool attr_set = false;
   if (!attr_set) {
     (void)hipFuncSetAttribute(
-        reinterpret_cast<const void*>(&big::gemm256_kernel<A_KC, B_KC, EPI, ACT, W, EXTRA, X>),
+        reinterpret_cast<const void*>(&big::gemm256_kernel<A_KC, B_KC, EPI, ACT, W, EXTRA, X, SIDE>),
         hipFuncAttributeMaxDynamicSharedMemorySize, smem);
     attr_set = true;
   }
-  hipLaunchKernelGGL((big::gemm256_kernel<A_KC, B_KC, EPI, ACT, W, EXTRA, X>), dim3(big_tiles(g, W), g.k_splits),
+  hipLaunchKernelGGL((big::gemm256_kernel<A_KC, B_KC, EPI, ACT, W, EXTRA, X, SIDE>), dim3(big_tiles(g, W), g.k_splits),
                      dim3(big::kThreads), smem, s, g);
 }
 
+template <bool A_KC, bool B_KC, int EPI, int ACT, bool EXTRA, int X = 0, int SIDE = big::kSideNone>
+void launch_big_width(const GemmArgs& g, hipStream_t s) {
+  if (big_width(g) == 128) launch_big<A_KC, B_KC, EPI, ACT, 128, EXTRA, X, SIDE>(g, s);
+  else launch_big<A_KC, B_KC, EPI, ACT, 256, EXTRA, X, SIDE>(g, s);
+}
+
 // One kernel, 256 or 128 wide, plus its two main-loop extras (the compared-
-// and-lost loops and the 4-wave kernel are gone: see above gemm256_kernel).
+// and-lost loops and the 4-wave kernel are gone: see above gemm256_kernel)
+// and, for the bf16 store pass without dropout / aux, its side-operand mode
+// (big::kSide*).  The modes are compiled for the layouts that use them: the
+// addend for forward GEMMs (y = res + act(x W^T + b)) and dgrads, the two
+// activation-backward modes for dgrads (no bias, no activation of their own).
 template <bool A_KC, bool B_KC, int EPI, int ACT, bool EXTRA>
 void launch_big_w(const GemmArgs& g, hipStream_t s) {
-  const bool narrow = big_width(g) == 128;
+  if constexpr (EPI == kEpiStoreBf16 && !EXTRA) {
+    const int side = g.dact_in != nullptr ? (g.dact == kActReluBits ? big::kSideBits : big::kSideSaved)
+                                          : (g.res != nullptr ? big::kSideRes : big::kSideNone);
+    if (side != big::kSideNone) {
+      if constexpr (A_KC && B_KC) {
+        if (side == big::kSideRes) {
+          if (g.at != nullptr) launch_big_width<A_KC, B_KC, EPI, ACT, EXTRA, big::kXEmit, big::kSideRes>(g, s);
+          else launch_big_width<A_KC, B_KC, EPI, ACT, EXTRA, 0, big::kSideRes>(g, s);
+          return;
+        }
+      }
+      if constexpr (A_KC && !B_KC && ACT == kActNone) {
+        if (g.at == nullptr && g.bias == nullptr) {
+          if (side == big::kSideRes) launch_big_width<A_KC, B_KC, EPI, ACT, EXTRA, 0, big::kSideRes>(g, s);
+          else if (side == big::kSideBits) launch_big_width<A_KC, B_KC, EPI, ACT, EXTRA, 0, big::kSideBits>(g, s);
+          else launch_big_width<A_KC, B_KC, EPI, ACT, EXTRA, 0, big::kSideSaved>(g, s);
+          return;
+        }
+      }
+      throw std::runtime_error("gemm_bf16: no kernel with this side operand (res / dact_in) for this operand layout");
+    }
+  }
   if constexpr (A_KC && B_KC && EPI == kEpiStoreBf16 && !(ACT == kActGelu && EXTRA)) {
     if (g.at != nullptr) {  // forward GEMM that also writes A^T (gemm_emit_ok)
-      if (narrow) launch_big<A_KC, B_KC, EPI, ACT, 128, EXTRA, big::kXEmit>(g, s);
-      else launch_big<A_KC, B_KC, EPI, ACT, 256, EXTRA, big::kXEmit>(g, s);
+      launch_big_width<A_KC, B_KC, EPI, ACT, EXTRA, big::kXEmit>(g, s);
       return;
     }
   }
   if constexpr (A_KC && !B_KC && EPI != kEpiStoreBf16 && !EXTRA) {
     if (g.colsum != nullptr) {  // transposed weight gradient with the bias fold
-      if (narrow) launch_big<A_KC, B_KC, EPI, ACT, 128, EXTRA, big::kXColsum>(g, s);
-      else launch_big<A_KC, B_KC, EPI, ACT, 256, EXTRA, big::kXColsum>(g, s);
+      launch_big_width<A_KC, B_KC, EPI, ACT, EXTRA, big::kXColsum>(g, s);
       return;
     }
   }
-  if (narrow) launch_big<A_KC, B_KC, EPI, ACT, 128, EXTRA>(g, s);
-  else launch_big<A_KC, B_KC, EPI, ACT, 256, EXTRA>(g, s);
+  launch_big_width<A_KC, B_KC, EPI, ACT, EXTRA>(g, s);
 }
 
 int g_gemm_group = -1;  // MIPIPE_GEMM_G: tile-rows per ordering group (A/B); -1 unread, 0 default
