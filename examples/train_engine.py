@@ -71,6 +71,9 @@ def parse(argv=None):
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--doc-eos", type=int, default=None, metavar="ID",
                     help="token id that ends a document: mask attention across documents (causal models)")
+    ap.add_argument("--expert-gemm", default=None, choices=["loop", "grouped"],
+                    help="mixture-of-experts configs: 'grouped' runs the dropless grouped-GEMM experts "
+                         "(capacity_factor=None), 'loop' the config's own capacity with one GEMM per expert")
     return ap.parse_args(argv)
 
 
@@ -94,6 +97,13 @@ def main(argv=None) -> int:
     cfg = CONFIGS[args.config]
     if args.layers:
         cfg = dataclasses.replace(cfg, num_layers=args.layers)
+    if args.expert_gemm is not None:
+        if cfg.n_experts is None:
+            raise SystemExit(f"--expert-gemm needs a mixture-of-experts config, {args.config} is dense")
+        if args.expert_gemm == "grouped":
+            cfg = dataclasses.replace(cfg, expert_gemm="grouped", capacity_factor=None)
+        else:
+            cfg = dataclasses.replace(cfg, expert_gemm="loop")
 
     # ---- data: every rank builds the same stream and takes its replica's columns
     m, mb, S = args.chunks, args.micro_batch, cfg.seq_len

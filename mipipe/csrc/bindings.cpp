@@ -713,6 +713,91 @@ std::tuple<Tensor, Tensor, Tensor> py_moe_assign(Tensor idx, int64_t n_experts, 
   return {slot, src, counts};
 }
 
+// The sorted layout (kernels.h): (slot [T, k], src [rows], counts [Ne], offsets [Ne + 1], tile_expert [rows / 128]).
+std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> py_moe_assign_sorted(Tensor idx, int64_t n_experts, int64_t rows) {
+  const char* name = "moe_assign_sorted";
+  check_cuda(idx, "idx");
+  MP_CHECK(idx.dim() == 2 && idx.scalar_type() == at::kInt, name, ": idx must be int32 [T, k]");
+  const int64_t T = idx.size(0), k = idx.size(1);
+  MP_CHECK(n_experts <= 256 && k <= 8 && moe_route_supported((int)n_experts, (int)k), name,
+           ": needs 2 <= Ne <= 256 and 1 <= k <= min(8, Ne), got Ne=", n_experts, ", k=", k);
+  MP_CHECK(T * k < (int64_t(1) << 31), name, ": T * k must be below 2^31");
+  // every count vector fits: sum_e ceil128(c_e) <= 128 * (n + (T k - n) / 128), n = min(Ne, T k)
+  const int64_t n = std::min<int64_t>(n_experts, T * k);
+  MP_CHECK(rows % 128 == 0 && rows >= 128 * (n + (T * k - n) / 128) && rows < (int64_t(1) << 31), name,
+           ": rows must be a multiple of 128, at least 128 * (n + (T k - n) / 128) and below 2^31, got ", rows);
+  at::hip::HIPGuardMasqueradingAsCUDA guard(idx.device());
+  auto slot = at::empty({T, k}, idx.options());
+  auto src = at::empty({rows}, idx.options());
+  auto counts = at::empty({n_experts}, idx.options());
+  auto offsets = at::empty({n_experts + 1}, idx.options());
+  auto tile_expert = at::empty({rows / 128}, idx.options());
+  auto ws = at::empty({(int64_t)moe_assign_blocks(T, (int)k), n_experts}, idx.options());
+  moe_assign_sorted(cptr<int32_t>(idx), ptr<int32_t>(slot), ptr<int32_t>(src), ptr<int32_t>(counts),
+                    ptr<int32_t>(offsets), ptr<int32_t>(tile_expert), ptr<int32_t>(ws), T, (int)k, (int)n_experts,
+                    (int)rows, cur_stream(idx));
+  return {slot, src, counts, offsets, tile_expert};
+}
+
+// ------------------------------------------------------------------ grouped GEMM
+void grouped_check_table(const Tensor& t, const Tensor& like, int64_t n, at::ScalarType st, const char* name,
+                         const char* what) {
+  MP_CHECK(t.is_cuda() && t.is_contiguous() && t.device() == like.device() && t.scalar_type() == st &&
+               t.dim() == 1 && t.numel() == n,
+           name, ": ", what, " must be a contiguous ", st, " [", n, "] tensor on the operands' device");
+}
+
+void grouped_check_rows(const Tensor& t, const char* name, const char* what) {
+  check_cuda(t, what);
+  MP_CHECK(t.dim() == 2 && t.scalar_type() == at::kBFloat16, name, ": ", what, " must be bf16 [rows, width]");
+  MP_CHECK(reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0, name, ": ", what, " must be 16-byte aligned");
+}
+
+// y [R, n_out] = a [R, Kred] . op(W_e) per 128-row tile, e = tile_expert[tile] (zeros for -1).  wptrs [Ne]: the
+// experts' weight pointers, each a contiguous bf16 [n_out, Kred] (w_kc, the forward) or [Kred, n_out] (the dgrad).
+// The caller keeps the weights alive and answers for the table.
+Tensor py_grouped_gemm_rows(Tensor a, Tensor wptrs, Tensor tile_expert, int64_t n_out, bool w_kc) {
+  const char* name = "grouped_gemm_rows";
+  grouped_check_rows(a, name, "a");
+  const int64_t R = a.size(0), Kred = a.size(1), Ne = wptrs.numel();
+  MP_CHECK(grouped_gemm_supported(R, n_out, Kred), name, ": needs rows % 128 == 0, n_out % 128 == 0 and a reduction "
+           "width % 64 == 0, got rows=", R, ", n_out=", n_out, ", reduction=", Kred);
+  MP_CHECK(Ne >= 1 && Ne < (1 << 16), name, ": needs 1 <= Ne < 65536 experts, got ", Ne);
+  grouped_check_table(wptrs, a, Ne, at::kLong, name, "wptrs");
+  grouped_check_table(tile_expert, a, R / 128, at::kInt, name, "tile_expert");
+  at::hip::HIPGuardMasqueradingAsCUDA guard(a.device());
+  auto y = at::empty({R, n_out}, a.options());
+  grouped_gemm_rows(cptr<bf16_t>(a), cptr<int64_t>(wptrs), cptr<int32_t>(tile_expert), ptr<bf16_t>(y), R, n_out, Kred,
+                    (int)Ne, w_kc, cur_stream(a));
+  return y;
+}
+
+// dW_e [N, K] fp32 = or += dy[rows_e]^T x[rows_e], rows_e = [offsets[e], offsets[e + 1]).  With `optrs` (int64 [Ne])
+// the experts' outputs are those pointers (fp32 [N, K] each, 16-byte aligned; the caller answers for them) and
+// nothing is returned; without it a fresh fp32 [Ne, N, K] is written (store mode only) and returned.
+std::optional<Tensor> py_grouped_gemm_wgrad(Tensor dy, Tensor x, Tensor offsets, std::optional<Tensor> optrs,
+                                            bool accumulate) {
+  const char* name = "grouped_gemm_wgrad";
+  grouped_check_rows(dy, name, "dy");
+  grouped_check_rows(x, name, "x");
+  MP_CHECK(dy.device() == x.device(), name, ": dy and x must be on the same device");
+  const int64_t R = dy.size(0), N = dy.size(1), K = x.size(1), Ne = offsets.numel() - 1;
+  MP_CHECK(x.size(0) == R, name, ": dy has ", R, " rows, x ", x.size(0));
+  MP_CHECK(R > 0 && R % 128 == 0 && N > 0 && N % 128 == 0 && K > 0 && K % 128 == 0 && R < (int64_t(1) << 31) &&
+               (N / 128) * (K / 128) < (int64_t(1) << 31),
+           name, ": needs rows, N and K to be multiples of 128, got ", R, ", ", N, ", ", K);
+  MP_CHECK(Ne >= 1 && Ne < (1 << 16), name, ": needs 1 <= Ne < 65536 experts, got ", Ne);
+  grouped_check_table(offsets, dy, Ne + 1, at::kInt, name, "offsets");
+  MP_CHECK(optrs.has_value() || !accumulate, name, ": accumulate needs the table of outputs");
+  at::hip::HIPGuardMasqueradingAsCUDA guard(dy.device());
+  std::optional<Tensor> out;
+  if (optrs.has_value()) grouped_check_table(*optrs, dy, Ne, at::kLong, name, "optrs");
+  else out = at::empty({Ne, N, K}, dy.options().dtype(at::kFloat));
+  grouped_gemm_wgrad(cptr<bf16_t>(dy), cptr<bf16_t>(x), cptr<int32_t>(offsets), optr<int64_t>(optrs),
+                     out.has_value() ? ptr<float>(*out) : nullptr, R, N, K, (int)Ne, accumulate, cur_stream(dy));
+  return out;
+}
+
 // xe [nslots, E]: xe[s] = x[src[s] / k], zeros for an empty slot.
 Tensor py_moe_gather_slots(Tensor x, Tensor src, int64_t k) {
   const char* name = "moe_gather_slots";
@@ -2070,6 +2155,13 @@ PYBIND11_MODULE(_C, m) {
         py::arg("dprobs") = py::none());
   m.def("moe_assign", &py_moe_assign, py::arg("idx"), py::arg("n_experts"), py::arg("capacity"),
         "idx int32 [T, k] -> (slot int32 [T, k], src int32 [Ne * C], counts int32 [Ne])");
+  m.def("moe_assign_sorted", &py_moe_assign_sorted, py::arg("idx"), py::arg("n_experts"), py::arg("rows"),
+        "idx int32 [T, k] -> (slot [T, k], src [rows], counts [Ne], offsets [Ne + 1], tile_expert [rows / 128])");
+  m.def("grouped_gemm_supported", &grouped_gemm_supported, py::arg("rows"), py::arg("n_out"), py::arg("reduction"));
+  m.def("grouped_gemm_rows", &py_grouped_gemm_rows, py::arg("a"), py::arg("wptrs"), py::arg("tile_expert"),
+        py::arg("n_out"), py::arg("w_kc"));
+  m.def("grouped_gemm_wgrad", &py_grouped_gemm_wgrad, py::arg("dy"), py::arg("x"), py::arg("offsets"),
+        py::arg("optrs") = py::none(), py::arg("accumulate") = false);
   m.def("moe_gather_slots", &py_moe_gather_slots, py::arg("x"), py::arg("src"), py::arg("k"));
   m.def("moe_gather_tokens", &py_moe_gather_tokens, py::arg("ye"), py::arg("slot"), py::arg("w") = py::none(),
         py::arg("res") = py::none());

@@ -178,6 +178,12 @@ void moe_route_bwd(const T* logits, const int32_t* idx, const float* gate, const
 int moe_assign_blocks(int64_t tokens, int k);
 void moe_assign(const int32_t* idx, int32_t* slot, int32_t* src, int32_t* counts, int32_t* ws, int64_t tokens, int k,
                 int Ne, int C, hipStream_t s);
+// The sorted (dropless) layout: expert e's rows are [offsets[e], offsets[e + 1]) with offsets[e + 1] = offsets[e] +
+// ceil128(counts[e]); slot [T, k] = offsets[e] + pos (-1 only for an expert outside [0, Ne)), src [rows] = a or -1
+// (padding), tile_expert [rows / 128] the expert of a 128-row tile or -1 past offsets[Ne].  rows is a multiple of
+// 128 that bounds offsets[Ne] (the caller checks).  ws as for moe_assign.
+void moe_assign_sorted(const int32_t* idx, int32_t* slot, int32_t* src, int32_t* counts, int32_t* offsets,
+                       int32_t* tile_expert, int32_t* ws, int64_t tokens, int k, int Ne, int rows, hipStream_t s);
 // xe [nslots, E]: xe[s] = x[src[s] / k], zeros where src[s] < 0.  E * sizeof(T) % 16 == 0, 16-byte aligned pointers.
 template <typename T>
 void moe_gather_slots(const T* x, const int32_t* src, T* xe, int64_t nslots, int64_t tokens, int k, int E,
@@ -333,6 +339,18 @@ void gemm_set_width(int w);    // 256-row GEMM block width: 0 auto, 128, 256
 void gemm_set_rounds(int on);  // 1: multi-round grids launched one round at a time (default), 0: one launch
 void gemm_set_splitk(int n);  // split-K factor: 0 off, 1 auto (gemm_splitk_factor), n >= 2 forced (A/B tools)
 void gemm_bf16(const GemmArgs& g, hipStream_t s);
+// Grouped GEMMs over expert-sorted rows (gemm_grouped.hip): R rows in 128-row tiles, tile_expert [R / 128] the
+// expert of a tile (-1: the tile stores zeros), wptr [Ne] a device table of the experts' bf16 weight pointers.
+// R % 128 == 0, Nout % 128 == 0, Kred % 64 == 0 (grouped_gemm_supported).
+bool grouped_gemm_supported(int64_t R, int64_t Nout, int64_t Kred);
+// C[R, Nout] = A[R, Kred] . op(W_e): w_kc, W_e is [Nout, Kred] (the forward); otherwise [Kred, Nout] (the dgrad).
+void grouped_gemm_rows(const bf16_t* A, const int64_t* wptr, const int32_t* tile_expert, bf16_t* C, int64_t R,
+                       int64_t Nout, int64_t Kred, int Ne, bool w_kc, hipStream_t s);
+// dW_e[N, K] (fp32) = or += dY[rows_e, N]^T . X[rows_e, K] with rows_e = [offsets[e], offsets[e + 1]), whole 128-row
+// tiles.  dW_e is optr[e] (a device table) or, with optr null, obase + e * N * K.  An expert without rows is
+// zero-filled, or left alone when accumulating.  N % 128 == 0, K % 128 == 0.
+void grouped_gemm_wgrad(const bf16_t* dY, const bf16_t* X, const int32_t* offsets, const int64_t* optr, float* obase,
+                        int64_t R, int64_t N, int64_t K, int Ne, bool accumulate, hipStream_t s);
 // Same interface with fp32 operands (and fp32 bias / res / aux / C): v_mfma_f32_32x32x2_f32.
 bool gemm_f32_supported(int64_t M, int64_t N, int64_t K);
 void gemm_f32(const GemmArgs& g, hipStream_t s);

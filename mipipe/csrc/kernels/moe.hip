@@ -13,6 +13,10 @@
 //   assign      slot [T, k] = e * C + pos or -1, src [Ne * C] = a or -1, counts
 //               [Ne]; pos counts the earlier entries of the same expert in
 //               choice-major order (j first, then t).
+//   assign_sorted  the dropless layout for the grouped GEMMs (gemm_grouped.hip):
+//               expert e owns rows [offsets[e], offsets[e + 1]), offsets[e + 1] =
+//               offsets[e] + ceil128(counts[e]); slot = offsets[e] + pos; src [R];
+//               tile_expert [R / 128] = the expert of a 128-row tile or -1.
 //   gather_slots   xe[s] = x[src[s] / k]            (dispatch forward)
 //   gather_tokens  y[t] = res[t] + sum_j w[t, j] ye[slot[t, j]]
 //                                                   (combine forward, dispatch backward)
@@ -314,14 +318,21 @@ __global__ void __launch_bounds__(kThreads) moe_assign_scan_kernel(int32_t* __re
 
 // Ranks: a lane's place among the wave's earlier lanes of the same expert from ballots over the expert's 8 bits,
 // the waves of a round one after the other over running[] in LDS, the rounds in order.
+//
+// kSorted (moe_assign_sorted): expert e's rows start at offsets[e] instead of e * C, nothing is dropped, and C is the
+// number of rows of src (a bound the counts cannot exceed; it only guards the store).
+template <bool kSorted>
 __global__ void __launch_bounds__(kThreads) moe_assign_rank_kernel(const int32_t* __restrict__ idx,
                                                                    const int32_t* __restrict__ base,
+                                                                   const int32_t* __restrict__ offsets,
                                                                    int32_t* __restrict__ slot,
                                                                    int32_t* __restrict__ src, int64_t tokens, int k,
                                                                    int Ne, int C) {
   __shared__ int32_t running[256];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  running[threadIdx.x] = (int)threadIdx.x < Ne ? base[(size_t)blockIdx.x * Ne + threadIdx.x] : 0;
+  running[threadIdx.x] = (int)threadIdx.x < Ne ? base[(size_t)blockIdx.x * Ne + threadIdx.x] +
+                                                     (kSorted ? offsets[threadIdx.x] : 0)
+                                               : 0;
   __syncthreads();
   const int64_t n = tokens * k;
   const int64_t q0 = (int64_t)blockIdx.x * kAssignChunk;
@@ -341,7 +352,7 @@ __global__ void __launch_bounds__(kThreads) moe_assign_rank_kernel(const int32_t
       if (wave == w && e >= 0) {
         const int pos = running[e] + rank;
         if (pos < C) {
-          const int s = e * C + pos;  // < Ne * C < 2^31 (the launcher checks)
+          const int s = kSorted ? pos : e * C + pos;  // < Ne * C < 2^31 (the launcher checks)
           slot[a] = s;
           src[s] = (int32_t)a;
         } else {
@@ -353,6 +364,44 @@ __global__ void __launch_bounds__(kThreads) moe_assign_rank_kernel(const int32_t
     }
     if (q < n && e < 0) slot[a] = -1;
   }
+}
+
+// The sorted layout's scan: as moe_assign_scan_kernel, and from the totals offsets[e + 1] = offsets[e] +
+// ceil128(counts[e]) and the expert of every 128-row tile (-1 past offsets[Ne]).
+__global__ void __launch_bounds__(kThreads) moe_assign_sorted_scan_kernel(int32_t* __restrict__ hist,
+                                                                          int32_t* __restrict__ counts,
+                                                                          int32_t* __restrict__ offsets,
+                                                                          int32_t* __restrict__ tile_expert,
+                                                                          int nblocks, int Ne, int ntiles) {
+  __shared__ int32_t first[257];  // first tile of expert e; first[Ne] the live tiles
+  const int e = threadIdx.x;
+  int32_t run = 0;
+  if (e < Ne) {
+    for (int b = 0; b < nblocks; ++b) {
+      const int32_t c = hist[(size_t)b * Ne + e];
+      hist[(size_t)b * Ne + e] = run;
+      run += c;
+    }
+    counts[e] = run;
+  }
+  first[e + 1] = (run + 127) >> 7;
+  __syncthreads();
+  if (e == 0) {
+    int32_t t = 0;
+    first[0] = 0;
+    for (int i = 1; i <= Ne; ++i) {
+      t += first[i];
+      first[i] = t;
+    }
+  }
+  __syncthreads();
+  if (e <= Ne) offsets[e] = first[e] * 128;
+  if (e == 0 && Ne == 256) offsets[256] = first[256] * 128;
+  if (e < Ne) {
+    const int hi = min(first[e + 1], ntiles);
+    for (int t = first[e]; t < hi; ++t) tile_expert[t] = e;
+  }
+  for (int t = first[Ne] + e; t < ntiles; t += kThreads) tile_expert[t] = -1;
 }
 
 // ---------------------------------------------------------------- row kernels
@@ -567,7 +616,19 @@ void moe_assign(const int32_t* idx, int32_t* slot, int32_t* src, int32_t* counts
   const dim3 grid((unsigned)nb), block(kThreads);
   hipLaunchKernelGGL(moe_assign_count_kernel, grid, block, 0, s, idx, ws, src, tokens, k, Ne, (int64_t)Ne * C);
   hipLaunchKernelGGL(moe_assign_scan_kernel, dim3(1), block, 0, s, ws, counts, nb, Ne);
-  hipLaunchKernelGGL(moe_assign_rank_kernel, grid, block, 0, s, idx, ws, slot, src, tokens, k, Ne, C);
+  hipLaunchKernelGGL(moe_assign_rank_kernel<false>, grid, block, 0, s, idx, ws, (const int32_t*)nullptr, slot, src,
+                     tokens, k, Ne, C);
+}
+
+void moe_assign_sorted(const int32_t* idx, int32_t* slot, int32_t* src, int32_t* counts, int32_t* offsets,
+                       int32_t* tile_expert, int32_t* ws, int64_t tokens, int k, int Ne, int rows, hipStream_t s) {
+  const int nb = moe_assign_blocks(tokens, k);
+  const dim3 grid((unsigned)nb), block(kThreads);
+  hipLaunchKernelGGL(moe_assign_count_kernel, grid, block, 0, s, idx, ws, src, tokens, k, Ne, (int64_t)rows);
+  hipLaunchKernelGGL(moe_assign_sorted_scan_kernel, dim3(1), block, 0, s, ws, counts, offsets, tile_expert, nb, Ne,
+                     rows / 128);
+  hipLaunchKernelGGL(moe_assign_rank_kernel<true>, grid, block, 0, s, idx, ws, offsets, slot, src, tokens, k, Ne,
+                     rows);
 }
 
 template <typename T>

@@ -22,7 +22,8 @@ from torch import Tensor, nn
 from .. import ops
 from ..ops.linear import mark_gemm_weight
 from ..ops.softcap import softcap_owned
-from .transformer import GATED_ACTS, FeedForwardBlock, check_global_every, layer_window, transformer_blocks
+from .transformer import (GATED_ACTS, FeedForwardBlock, check_expert_gemm, check_global_every, layer_window,
+                          transformer_blocks)
 
 __all__ = [
     "Encoder",
@@ -240,10 +241,13 @@ class LMConfig:
     experts_per_token: int = 2        # experts a token runs, weighted by the softmax over their router logits
     capacity_factor: Optional[float] = 1.25  # slots per expert = factor * tokens * k / n_experts; None drops nothing
     moe_aux_coef: float = 0.01        # weight of the load-balancing term in the router's gradient
+    expert_gemm: str = "loop"         # "loop": one GEMM per expert on capacity slices; "grouped": dropless, needs
+    #                                   capacity_factor=None (MoEFeedForwardBlock)
     qk_norm: bool = False             # per-head RMSNorm on Q and K before the rotation (Qwen3): two [head_dim] weights
 
     def __post_init__(self) -> None:
         check_global_every(self.global_every, self.window)
+        check_expert_gemm(self.expert_gemm, self.capacity_factor)
 
     def head_width(self) -> int:
         return self.d_model // self.nhead if self.head_dim is None else self.head_dim
@@ -450,7 +454,8 @@ def build_lm_blocks(cfg: LMConfig, *, device=None, dtype=None) -> List[nn.Module
                                  sandwich_norm=cfg.sandwich_norm, head_dim=cfg.head_dim, attn_scale=cfg.attn_scale,
                                  global_every=cfg.global_every, attn_sinks=cfg.attn_sinks, n_experts=cfg.n_experts,
                                  experts_per_token=cfg.experts_per_token, capacity_factor=cfg.capacity_factor,
-                                 moe_aux_coef=cfg.moe_aux_coef, device=device, dtype=dtype)
+                                 moe_aux_coef=cfg.moe_aux_coef, expert_gemm=cfg.expert_gemm, device=device,
+                                 dtype=dtype)
     if cfg.act_dropout is not None:
         for b in blocks:
             if isinstance(b, FeedForwardBlock):

@@ -657,6 +657,16 @@ class FeedForwardBlock(nn.Module):
         return self.fc_in.flops_per_token(seq_len) + self.fc_out.flops_per_token(seq_len)
 
 
+EXPERT_GEMMS = ("loop", "grouped")
+
+
+def check_expert_gemm(expert_gemm: str, capacity_factor: Optional[float]) -> None:
+    if expert_gemm not in EXPERT_GEMMS:
+        raise ValueError(f"expert_gemm must be one of {EXPERT_GEMMS}, got {expert_gemm!r}")
+    if expert_gemm == "grouped" and capacity_factor is not None:
+        raise ValueError(f"expert_gemm='grouped' is dropless: it needs capacity_factor=None, got {capacity_factor!r}")
+
+
 class MoEFeedForwardBlock(nn.Module):
     """Mixture-of-experts MLP half of a pre-norm layer (Mixtral, Qwen3-MoE): ``x + sum_j gate_j expert_{idx_j}(norm(x))``
     with ``n_experts`` gated MLPs (``activation="swiglu"`` or ``"geglu"``) of which every token runs its
@@ -679,16 +689,25 @@ class MoEFeedForwardBlock(nn.Module):
     :class:`~mipipe.parallel.engine.PipelineEngine` sets it to ``1 / (chunks * grad_divisor)`` on every block of its
     modules; outside the engine set it yourself when the loss is scaled (gradient accumulation).  ``aux_coef=0``
     turns the term off.  ``last_aux`` and ``last_drop_fraction`` are detached device scalars of the last forward,
-    for logging."""
+    for logging.
+
+    ``expert_gemm="grouped"`` (needs ``capacity_factor=None``) is the dropless path: ``ops.moe_assign_sorted`` sorts
+    the choices by expert into ``ops.moe_sorted_rows(T, Ne, k)`` rows (segments padded to whole 128-row tiles: about
+    ``k T + 64 Ne`` rows, not ``Ne ceil64(T)``), and the experts run as ``ops.grouped_linear(w1)``, the gate op once,
+    ``ops.grouped_linear(w2)``: three GEMM launches and one gate launch per direction whatever ``Ne``, no
+    concatenation.  Nothing is dropped: ``last_drop_fraction`` is exactly 0.  Its weight gradients run in the
+    backward, not in the deferred flush.  ``"loop"`` (the default) is the path described above."""
 
     def __init__(self, d_model: int, dim_feedforward: int, n_experts: int, experts_per_token: int = 2, *,
                  capacity_factor: Optional[float] = 1.25, aux_coef: float = 0.01, activation: str = "swiglu",
                  norm_first: bool = True, norm: str = "rms", layer_norm_eps: float = 1e-5, bias: bool = False,
-                 device=None, dtype=None) -> None:
+                 expert_gemm: str = "loop", device=None, dtype=None) -> None:
         super().__init__()
         fk = {"device": device, "dtype": dtype}
         if not norm_first or bias:
             raise ValueError(f"MoEFeedForwardBlock is pre-norm and bias-free, got norm_first={norm_first}, bias={bias}")
+        check_expert_gemm(expert_gemm, capacity_factor)
+        self.expert_gemm = expert_gemm
         if activation not in GATED_ACTS:
             raise ValueError(f"MoEFeedForwardBlock: activation must be one of {GATED_ACTS}, got {activation!r}")
         if isinstance(n_experts, bool) or not isinstance(n_experts, int) or not 2 <= n_experts <= ops.moe.MAX_EXPERTS:
@@ -721,11 +740,16 @@ class MoEFeedForwardBlock(nn.Module):
 
     def route(self, logits: Tensor, tokens: int):
         """``(gate, slot, src, capacity)`` of the router ``logits [T, Ne]``; records the logging scalars and, when a
-        graph is recorded, attaches the load-balancing gradient to the gate."""
+        graph is recorded, attaches the load-balancing gradient to the gate.  The grouped path returns ``(offsets,
+        tile_expert)`` of the sorted layout in the capacity's place."""
         ne, k = self.n_experts, self.experts_per_token
         idx, gate, probs_sum = ops.moe_route(logits, k)
-        cap = ops.moe_capacity(tokens, ne, k, self.capacity_factor)
-        slot, src, counts = ops.moe_assign(idx, ne, cap)
+        if getattr(self, "expert_gemm", "loop") == "grouped":
+            slot, src, counts, offsets, tile_expert = ops.moe_assign_sorted(idx, ne)
+            cap = (offsets, tile_expert)
+        else:
+            cap = ops.moe_capacity(tokens, ne, k, self.capacity_factor)
+            slot, src, counts = ops.moe_assign(idx, ne, cap)
         attach = self.aux_coef != 0.0 and torch.is_grad_enabled() and gate.requires_grad
         with torch.no_grad():
             load = counts.to(probs_sum.dtype)
@@ -746,13 +770,22 @@ class MoEFeedForwardBlock(nn.Module):
             outs.append(ops.linear(h, self.experts_w2[e]))
         return torch.cat(outs)
 
+    def experts_grouped(self, xe: Tensor, offsets: Tensor, tile_expert: Tensor) -> Tensor:
+        """The experts on their row ranges of the sorted ``xe [R, E]``: one launch per GEMM and one for the gate."""
+        act = ops.swiglu if self.activation == "swiglu" else ops.geglu
+        h = act(ops.grouped_linear(xe, list(self.experts_w1), tile_expert, offsets))
+        return ops.grouped_linear(h, list(self.experts_w2), tile_expert, offsets)
+
     def forward(self, x: Tensor) -> Tensor:
         shape = x.shape
         xn, xr = _norm_fanout(self, x) if FANOUT else (_norm(self, x, None, 0.0), x)
         x2 = xn.reshape(-1, shape[-1])
         tokens = x2.shape[0]
         gate, slot, src, cap = self.route(ops.linear(x2, self.router_weight), tokens)
-        ye = self.experts(ops.moe_dispatch(x2, slot, src), cap)
+        if getattr(self, "expert_gemm", "loop") == "grouped":
+            ye = self.experts_grouped(ops.moe_dispatch(x2, slot, src), *cap)
+        else:
+            ye = self.experts(ops.moe_dispatch(x2, slot, src), cap)
         return ops.moe_combine(ye, gate, slot, src, residual=xr.reshape(-1, shape[-1])).view(shape)
 
     def flops_per_token(self, seq_len: int) -> float:
@@ -906,6 +939,7 @@ def transformer_blocks(
     experts_per_token: int = 2,
     capacity_factor: Optional[float] = 1.25,
     moe_aux_coef: float = 0.01,
+    expert_gemm: str = "loop",
     device=None,
     dtype=None,
 ) -> List[nn.Module]:
@@ -916,7 +950,8 @@ def transformer_blocks(
 
     ``n_experts=Ne`` (``None``: dense) builds a :class:`MoEFeedForwardBlock` of ``Ne`` experts of width
     ``dim_feedforward`` in place of the :class:`FeedForwardBlock` of every layer (pre-norm, bias-free, gated
-    activation, no sandwich norm)."""
+    activation, no sandwich norm); ``expert_gemm="grouped"`` (with ``capacity_factor=None``) selects its dropless
+    grouped-GEMM path."""
     check_global_every(global_every, window)
     blocks: List[nn.Module] = []
     if n_experts is not None:
@@ -931,7 +966,7 @@ def transformer_blocks(
             blocks.append(MoEFeedForwardBlock(d_model, dim_feedforward, n_experts, experts_per_token,
                                               capacity_factor=capacity_factor, aux_coef=moe_aux_coef,
                                               activation=activation, norm_first=norm_first, norm=norm, bias=bias,
-                                              device=device, dtype=dtype))
+                                              expert_gemm=expert_gemm, device=device, dtype=dtype))
         return blocks
     for i in range(num_layers):
         layer = TransformerEncoderLayer(d_model, nhead, dim_feedforward, dropout, activation,

@@ -17,8 +17,10 @@ from .swiglu import swiglu, swiglu_reference
 from .geglu import geglu, geglu_reference
 from .rope import rope_heads, rope_packed, rope_projection, rope_reference, rope_tables
 from .qknorm import qk_norm_rope_heads, qk_norm_rope_projection, qk_norm_rope_reference
-from .moe import (moe_assign, moe_assign_reference, moe_attach_aux, moe_capacity, moe_combine, moe_combine_reference,
-                  moe_dispatch, moe_dispatch_reference, moe_route, moe_route_reference)
+from .moe import (moe_assign, moe_assign_reference, moe_assign_sorted, moe_assign_sorted_reference, moe_attach_aux,
+                  moe_capacity, moe_combine, moe_combine_reference, moe_dispatch, moe_dispatch_reference, moe_route,
+                  moe_route_reference, moe_sorted_rows)
+from .grouped_linear import grouped_linear, grouped_linear_reference
 from .loss import cross_entropy
 from .embedding import embed_scale_posenc_dropout
 
@@ -69,6 +71,11 @@ __all__ = [
     "moe_assign_reference",
     "moe_dispatch_reference",
     "moe_combine_reference",
+    "moe_assign_sorted",
+    "moe_assign_sorted_reference",
+    "moe_sorted_rows",
+    "grouped_linear",
+    "grouped_linear_reference",
     "cross_entropy",
     "embed_scale_posenc_dropout",
 ]

@@ -27,6 +27,13 @@ float atomics, no host synchronisation, the same bits on every run.  A width
 that does not fill 16-byte vectors, a single expert or another dtype than bf16 /
 fp32 takes the eager reference and says so once per shape.  CPU tensors use the
 references.
+
+The dropless variant of the second step, for ``ops.grouped_linear``::
+
+    slot, src, counts, offsets, tile_expert = moe_assign_sorted(idx, Ne)
+
+sorts the choices by expert into ``R = moe_sorted_rows(T, Ne, k)`` rows, every expert's segment padded to whole
+128-row tiles (see :func:`moe_assign_sorted`); dispatch and combine take its tables unchanged.
 """
 from __future__ import annotations
 
@@ -41,7 +48,7 @@ from ._util import kernels_for
 
 __all__ = ["moe_route", "moe_assign", "moe_dispatch", "moe_combine", "moe_capacity", "moe_route_reference",
            "moe_assign_reference", "moe_dispatch_reference", "moe_combine_reference", "moe_attach_aux",
-           "MAX_EXPERTS", "MAX_TOP_K"]
+           "moe_assign_sorted", "moe_assign_sorted_reference", "moe_sorted_rows", "MAX_EXPERTS", "MAX_TOP_K"]
 
 MAX_EXPERTS = 256
 MAX_TOP_K = 8
@@ -237,6 +244,70 @@ def moe_assign(idx: Tensor, n_experts: int, capacity: int) -> Tuple[Tensor, Tens
         _note("moe_assign", "a single expert is not native", idx)
         return moe_assign_reference(idx, n_experts, capacity)
     return kernels_for(idx).moe_assign(idx.contiguous(), n_experts, capacity)
+
+
+def moe_sorted_rows(tokens: int, n_experts: int, k: int) -> int:
+    """Rows of the sorted layout: the largest ``sum_e ceil128(c_e)`` over every count vector with ``sum_e c_e =
+    tokens * k``.  With ``n = min(n_experts, tokens * k)`` the worst vector gives ``n`` experts one entry each (a
+    whole tile for one row) and every further 128 entries fill one more tile: ``128 * (n + (tokens * k - n) //
+    128)``.  Static: it depends on no routing decision."""
+    if tokens < 1 or n_experts < 1 or k < 1:
+        raise ValueError(f"moe_sorted_rows: tokens, n_experts and k must be >= 1, got {tokens}, {n_experts}, {k}")
+    n = min(n_experts, tokens * k)
+    return 128 * (n + (tokens * k - n) // 128)
+
+
+def moe_assign_sorted_reference(idx: Tensor, n_experts: int) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor]:
+    """Eager sorted assignment: :func:`moe_assign_reference`'s cumulative sums, the experts' segments padded to whole
+    128-row tiles and laid end to end.  No host synchronisation."""
+    T, k = idx.shape
+    rows = moe_sorted_rows(T, n_experts, k)
+    raw = idx.t().reshape(-1).long()  # entry q = j * T + t
+    valid = (raw >= 0) & (raw < n_experts)
+    flat = raw.clamp(0, n_experts - 1)
+    onehot = torch.nn.functional.one_hot(flat, n_experts) * valid[:, None]
+    pos = (onehot.cumsum(0) - onehot).gather(1, flat[:, None]).squeeze(1)
+    counts = onehot.sum(0)
+    ends = ((counts + 127) // 128 * 128).cumsum(0)
+    offsets = torch.cat([torch.zeros_like(ends[:1]), ends])
+    slot_cm = torch.where(valid, offsets[flat] + pos, torch.full_like(pos, -1))
+    q = torch.arange(T * k, device=idx.device)
+    a = (q % T) * k + q // T
+    # the invalid entries write to a spare last element
+    src = torch.full((rows + 1,), -1, dtype=torch.int64, device=idx.device)
+    src.scatter_(0, torch.where(valid, slot_cm, torch.full_like(pos, rows)),
+                 torch.where(valid, a, torch.full_like(a, -1)))
+    # a tile's expert: the number of segment ends at or before its first row (empty experts end where they start)
+    starts = torch.arange(rows // 128, device=idx.device) * 128
+    te = torch.searchsorted(ends, starts, right=True)
+    te = torch.where(te < n_experts, te, torch.full_like(te, -1))
+    slot = slot_cm.view(k, T).t().contiguous().to(torch.int32)
+    return (slot, src[:-1].to(torch.int32), counts.to(torch.int32), offsets.to(torch.int32), te.to(torch.int32))
+
+
+def moe_assign_sorted(idx: Tensor, n_experts: int) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor]:
+    """The dropless layout: ``(slot [T, k], src [R], counts [Ne], offsets [Ne + 1], tile_expert [R / 128])``, all
+    int32, with ``R = moe_sorted_rows(T, Ne, k)``.  Expert ``e`` owns rows ``[offsets[e], offsets[e + 1])``,
+    ``offsets[e + 1] = offsets[e] + ceil128(counts[e])``; ``slot = offsets[e] + pos`` with :func:`moe_assign`'s ``pos``
+    (``-1`` only for an ``idx`` outside ``[0, Ne)``); ``src`` is the owning ``a`` or ``-1`` for a padding row;
+    ``tile_expert`` the expert of each 128-row tile, ``-1`` past ``offsets[Ne]``.  :func:`moe_dispatch` and
+    :func:`moe_combine` take ``slot`` and ``src`` as they are; ``ops.grouped_linear`` takes the other two."""
+    if idx.dim() != 2:
+        raise ValueError(f"moe_assign_sorted: idx must be [T, k], got {tuple(idx.shape)}")
+    _check_index("moe_assign_sorted", "idx", idx, idx)
+    n_experts = int(n_experts)
+    _check_k("moe_assign_sorted", n_experts, idx.shape[1])
+    if idx.shape[0] < 1:
+        raise ValueError("moe_assign_sorted: needs at least one token")
+    rows = moe_sorted_rows(idx.shape[0], n_experts, idx.shape[1])
+    if rows >= 2 ** 31:
+        raise ValueError(f"moe_assign_sorted: the sorted layout must stay below 2^31 rows, got {rows}")
+    if not idx.is_cuda:
+        return moe_assign_sorted_reference(idx, n_experts)
+    if n_experts < 2:
+        _note("moe_assign_sorted", "a single expert is not native", idx)
+        return moe_assign_sorted_reference(idx, n_experts)
+    return kernels_for(idx).moe_assign_sorted(idx.contiguous(), n_experts, rows)
 
 
 # ------------------------------------------------------------------ dispatch / combine

@@ -98,12 +98,17 @@ def moe_cost(cfg: LMConfig, tokens: Optional[int] = None) -> float:
     """The whole mixture-of-experts MLP unit, priced by what runs: the router GEMM, the experts' GEMMs and gate
     pass over their PADDED rows -- ``Ne * C / T`` rows per token, ``C`` the capacity at ``tokens`` tokens per
     micro-batch (default: 8 sequences, as :func:`boundary_terms`) -- and the traffic of the norm, the dispatch and
-    the combine (``k`` rows gathered per token each way, forward and backward)."""
+    the combine (``k`` rows gathered per token each way, forward and backward).  A grouped config
+    (``cfg.expert_gemm == "grouped"``) runs ``k + 64 Ne / T`` rows per token: the true rows plus half a 128-row tile
+    of padding per expert."""
     from ..ops.moe import moe_capacity
 
     e, f, ne, k = cfg.d_model, cfg.dim_feedforward, cfg.n_experts, cfg.experts_per_token
     t = tokens if tokens is not None else 8 * cfg.seq_len
-    rows = ne * moe_capacity(t, ne, k, cfg.capacity_factor) / t
+    if cfg.expert_gemm == "grouped":
+        rows = k + 64.0 * ne / t
+    else:
+        rows = ne * moe_capacity(t, ne, k, cfg.capacity_factor) / t
     router = 3.0 * (2 * e * ne) + 3.0 * 10 * ne
     experts = rows * (3.0 * (2 * e * 2 * f) + 3.0 * 10 * f + 3.0 * (2 * e * f))
     passes = 3.0 * 10 * e + 3.0 * 5 * e * (rows + k)
