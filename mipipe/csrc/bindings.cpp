@@ -1737,14 +1737,15 @@ void fill_qkv(AttnArgs& a, const Tensor& q, const Tensor& k, const Tensor& v) {
            q.scalar_type(), " (bf16: S % 64 == 0, D in {64,128,256}; fp32: S % 32 == 0, D in {64,128})");
 }
 
-// bf16 D = 64, S >= 256 run the long-sequence kernels (attention_long.hip);
-// MIPIPE_ATTN_LONG=0 selects the previous kernels (A/B runs).
-bool use_long(const Tensor& q, int S, int D) {
+// bf16 D = 64, S >= 256 without a window, cap, document bounds or sinks run the long-sequence kernels
+// (attention_long.hip); MIPIPE_ATTN_LONG=0 selects the previous kernels (A/B runs).
+bool runs_long(const AttnArgs& a, const Tensor& q) {
   static const int on = [] {
     const char* e = getenv("MIPIPE_ATTN_LONG");
     return e == nullptr ? 1 : atoi(e);
   }();
-  return on && q.scalar_type() == at::kBFloat16 && attention_long_supported(S, D);
+  return on && a.window == 0 && a.softcap == 0.f && a.doc_start == nullptr && a.sinks == nullptr &&
+         q.scalar_type() == at::kBFloat16 && attention_long_supported(a.S, a.D);
 }
 
 // Sliding-window attention (`window` keys per query, the query's own included; 0 = none): causal bf16 only,
@@ -1804,6 +1805,18 @@ void attn_sinks(AttnArgs& a, const char* who, const std::optional<Tensor>& sinks
   a.sinks = static_cast<const float*>(t.data_ptr());
 }
 
+// The options of both entry points (`who`, for the messages), checked and filled into `a` after fill_qkv.
+void fill_options(AttnArgs& a, const char* who, const Tensor& q, bool causal, int64_t kv_len, int64_t window,
+                  double softcap, const std::optional<Tensor>& doc_bounds, const std::optional<Tensor>& sinks) {
+  attn_docs(a, who, doc_bounds, causal, q);
+  attn_sinks(a, who, sinks, q);
+  a.window = attn_window(who, window, causal, q, a.S);
+  a.softcap = attn_softcap(who, softcap, q);
+  MP_CHECK(kv_len == 0 || (q.scalar_type() == at::kFloat && kv_len > 0 && kv_len <= a.S), who,
+           ": kv_len (a key-length bound) is for fp32, 0 < kv_len <= S");
+  a.kv_len = (int)kv_len;
+}
+
 // Returns (o, lse, seed, offset, dropout keep bits): the bits tensor (int32
 // [B*H, S/32, S]) is non-empty only for the long-sequence kernels with p > 0
 // and must be handed back to attention_bwd.  A windowed call (0 < window < S) or a soft-capped one returns none.
@@ -1817,14 +1830,8 @@ std::tuple<Tensor, Tensor, int64_t, int64_t, Tensor> py_attention_fwd(Tensor q, 
                                                                       std::optional<Tensor> sinks) {
   AttnArgs a;
   fill_qkv(a, q, k, v);
-  attn_docs(a, "attention", doc_bounds, causal, q);
-  attn_sinks(a, "attention", sinks, q);
-  a.window = attn_window("attention", window, causal, q, a.S);
-  a.softcap = attn_softcap("attention", softcap, q);
+  fill_options(a, "attention", q, causal, kv_len, window, softcap, doc_bounds, sinks);
   MP_CHECK(p >= 0.0 && p < 1.0, "attention: bad dropout p");
-  MP_CHECK(kv_len == 0 || (q.scalar_type() == at::kFloat && kv_len > 0 && kv_len <= a.S),
-           "attention: kv_len (a key-length bound) is for fp32, 0 < kv_len <= S");
-  a.kv_len = (int)kv_len;
   at::hip::HIPGuardMasqueradingAsCUDA guard(q.device());
   auto o = at::empty({a.B, a.S, a.H, a.D}, q.options());
   auto lse = at::empty({a.B, a.H, a.S}, q.options().dtype(at::kFloat));
@@ -1836,8 +1843,7 @@ std::tuple<Tensor, Tensor, int64_t, int64_t, Tensor> py_attention_fwd(Tensor q, 
   Tensor bits = at::empty({0}, q.options().dtype(at::kInt));
   if (q.scalar_type() == at::kFloat) {
     attention_f32_fwd(a, cur_stream(q));
-  } else if (a.window == 0 && a.softcap == 0.f && a.doc_start == nullptr && a.sinks == nullptr &&
-             use_long(q, a.S, a.D)) {
+  } else if (runs_long(a, q)) {
     bool reuse = false;
     if (p > 0.0) {
       const std::vector<int64_t> shape = {(int64_t)a.B * a.H, a.S / 32, a.S};
@@ -1862,8 +1868,7 @@ void py_attention_bwd(Tensor dout, Tensor q, Tensor k, Tensor v, Tensor o, Tenso
                       bool dsinks_accumulate) {
   AttnArgs a;
   fill_qkv(a, q, k, v);
-  attn_docs(a, "attention_bwd", doc_bounds, causal, q);
-  attn_sinks(a, "attention_bwd", sinks, q);
+  fill_options(a, "attention_bwd", q, causal, kv_len, window, softcap, doc_bounds, sinks);
   const bool want_dsinks = dsinks && dsinks->defined();
   if (want_dsinks) {
     MP_CHECK(a.sinks != nullptr, "attention_bwd: dsinks without sinks");
@@ -1871,11 +1876,6 @@ void py_attention_bwd(Tensor dout, Tensor q, Tensor k, Tensor v, Tensor o, Tenso
                  dsinks->is_contiguous() && dsinks->device() == q.device(),
              "attention_bwd: dsinks must be a contiguous fp32 [H] = [", a.H, "] on q's device");
   }
-  a.window = attn_window("attention_bwd", window, causal, q, a.S);
-  a.softcap = attn_softcap("attention_bwd", softcap, q);
-  MP_CHECK(kv_len == 0 || (q.scalar_type() == at::kFloat && kv_len > 0 && kv_len <= a.S),
-           "attention_bwd: kv_len (a key-length bound) is for fp32, 0 < kv_len <= S");
-  a.kv_len = (int)kv_len;
   check_bshd(o, "o");
   check_bshd(dout, "dout");
   MP_CHECK(o.strides() == dout.strides() && o.sizes() == dout.sizes(), "attention_bwd: o/dout layout differs");
@@ -1914,8 +1914,7 @@ void py_attention_bwd(Tensor dout, Tensor q, Tensor k, Tensor v, Tensor o, Tenso
   a.scale = (float)scale; a.p = (float)p; a.seed = (uint64_t)seed; a.offset = (uint64_t)offset; a.causal = causal;
   if (q.scalar_type() == at::kFloat) {
     attention_f32_bwd(a, cur_stream(q));
-  } else if (a.window == 0 && a.softcap == 0.f && a.doc_start == nullptr && a.sinks == nullptr &&
-             use_long(q, a.S, a.D)) {
+  } else if (runs_long(a, q)) {
     if (p > 0.0) {
       MP_CHECK(bits && bits->is_cuda() && bits->scalar_type() == at::kInt &&
                    bits->numel() == (int64_t)a.B * a.H * (a.S / 32) * a.S,

@@ -19,6 +19,8 @@
 // skipped entirely; attention dropout uses Philox keyed by (batch*head,
 // query/4, key) -- word (query & 3) -- so forward, dQ and dK/dV regenerate the
 // same mask without storing it.
+#include <type_traits>
+
 #include "common.h"
 #include "kernels.h"
 
@@ -1608,99 +1610,40 @@ void run_bwd(const AttnArgs& a, hipStream_t s) {
   hipLaunchKernelGGL((attn_dq_kernel<D, CAUSAL>), dim3(a.S / kRows, a.B * a.H), dim3(kThreads), sm, s, a);
 }
 
-// Sliding window (0 < a.window < a.S, causal): always the generic 64-row kernels, whatever S and D -- the
-// S = 128, wide D = 64 and long-sequence kernels know no window.
-template <int D>
-void run_fwd_window(const AttnArgs& a, hipStream_t s) {
+// A sliding window (0 < a.window < a.S, causal), a soft cap (a.softcap > 0), document masks (a.doc_start set, causal)
+// and sinks (a.sinks set) always run the generic 64-row kernels, whatever S and D and in any combination -- the
+// S = 128, wide D = 64 and long-sequence kernels know none of them.  Under documents the window is merged at run
+// time (a.window = S when there is none), so there is no WINDOW && DOCS instantiation.
+template <int D, bool CAUSAL, bool WINDOW, bool SOFTCAP, bool DOCS, bool SINK>
+void launch_fwd_generic(const AttnArgs& a, hipStream_t s) {
   const size_t sm = fwd_smem<D>();
   static bool once = false;
-  if (!once) { set_smem(attn_fwd_kernel<D, true, true>, sm); once = true; }
-  hipLaunchKernelGGL((attn_fwd_kernel<D, true, true>), dim3(a.S / kRows, a.B * a.H), dim3(kThreads), sm, s, a);
+  if (!once) { set_smem(attn_fwd_kernel<D, CAUSAL, WINDOW, SOFTCAP, DOCS, SINK>, sm); once = true; }
+  hipLaunchKernelGGL((attn_fwd_kernel<D, CAUSAL, WINDOW, SOFTCAP, DOCS, SINK>), dim3(a.S / kRows, a.B * a.H),
+                     dim3(kThreads), sm, s, a);
 }
 
-template <int D>
-void run_bwd_window(const AttnArgs& a, hipStream_t s) {
+// The generic backward: delta from attn_delta_mfma_kernel on every path (a one-token document gives dS = 0
+// exactly), then dK/dV and dQ.  SINK multiplies the forward kernel only: the backward of a call with sinks runs
+// the sinkless instantiations on the forward's lse -- with sinks alone, the plain <D, CAUSAL> kernels.
+template <int D, bool CAUSAL, bool WINDOW, bool SOFTCAP, bool DOCS>
+void launch_bwd_generic(const AttnArgs& a, hipStream_t s) {
   const size_t sm = fwd_smem<D>(), sm2 = dkdv_smem<D>();
   static bool once = false;
   if (!once) {
-    set_smem(attn_dq_kernel<D, true, true>, sm);
-    set_smem(attn_dkdv_kernel<D, true, true>, sm2);
+    set_smem(attn_dq_kernel<D, CAUSAL, WINDOW, SOFTCAP, DOCS>, sm);
+    set_smem(attn_dkdv_kernel<D, CAUSAL, WINDOW, SOFTCAP, DOCS>, sm2);
     once = true;
   }
-  hipLaunchKernelGGL((attn_delta_mfma_kernel<D>), dim3(a.S / kRows, a.B * a.H), dim3(kThreads), 0, s, a);
-  hipLaunchKernelGGL((attn_dkdv_kernel<D, true, true>), dim3(a.S / kRows, a.B * a.H), dim3(kThreads), sm2, s, a);
-  hipLaunchKernelGGL((attn_dq_kernel<D, true, true>), dim3(a.S / kRows, a.B * a.H), dim3(kThreads), sm, s, a);
+  const dim3 grid(a.S / kRows, a.B * a.H);
+  hipLaunchKernelGGL((attn_delta_mfma_kernel<D>), grid, dim3(kThreads), 0, s, a);
+  hipLaunchKernelGGL((attn_dkdv_kernel<D, CAUSAL, WINDOW, SOFTCAP, DOCS>), grid, dim3(kThreads), sm2, s, a);
+  hipLaunchKernelGGL((attn_dq_kernel<D, CAUSAL, WINDOW, SOFTCAP, DOCS>), grid, dim3(kThreads), sm, s, a);
 }
 
 // A window that covers the sequence (or a non-causal call, which has none) is no window.
 void normalise_window(AttnArgs& a) {
   if (!a.causal || a.window < 0 || a.window >= a.S) a.window = 0;
-}
-
-// Logit soft-capping (a.softcap > 0): always the generic 64-row kernels too, at every S and D, non-causal,
-// causal, or causal with a window -- the S = 128, wide D = 64 and long-sequence kernels know no cap.
-template <int D, bool CAUSAL, bool WINDOW>
-void run_fwd_softcap(const AttnArgs& a, hipStream_t s) {
-  const size_t sm = fwd_smem<D>();
-  static bool once = false;
-  if (!once) { set_smem(attn_fwd_kernel<D, CAUSAL, WINDOW, true>, sm); once = true; }
-  hipLaunchKernelGGL((attn_fwd_kernel<D, CAUSAL, WINDOW, true>), dim3(a.S / kRows, a.B * a.H), dim3(kThreads), sm, s,
-                     a);
-}
-
-// delta from attn_delta_mfma_kernel on every path, as the windowed backward takes it.
-template <int D, bool CAUSAL, bool WINDOW>
-void run_bwd_softcap(const AttnArgs& a, hipStream_t s) {
-  const size_t sm = fwd_smem<D>(), sm2 = dkdv_smem<D>();
-  static bool once = false;
-  if (!once) {
-    set_smem(attn_dq_kernel<D, CAUSAL, WINDOW, true>, sm);
-    set_smem(attn_dkdv_kernel<D, CAUSAL, WINDOW, true>, sm2);
-    once = true;
-  }
-  const dim3 grid(a.S / kRows, a.B * a.H);
-  hipLaunchKernelGGL((attn_delta_mfma_kernel<D>), grid, dim3(kThreads), 0, s, a);
-  hipLaunchKernelGGL((attn_dkdv_kernel<D, CAUSAL, WINDOW, true>), grid, dim3(kThreads), sm2, s, a);
-  hipLaunchKernelGGL((attn_dq_kernel<D, CAUSAL, WINDOW, true>), grid, dim3(kThreads), sm, s, a);
-}
-
-// Document masks (a.doc_start set, causal): always the generic 64-row kernels too, with or without a cap; the
-// window is merged at run time (a.window = S when there is none).  delta from attn_delta_mfma_kernel, as under a
-// window: a one-token document gives dS = 0 exactly.
-template <int D, bool SOFTCAP>
-void run_fwd_docs(const AttnArgs& a, hipStream_t s) {
-  const size_t sm = fwd_smem<D>();
-  static bool once = false;
-  if (!once) { set_smem(attn_fwd_kernel<D, true, false, SOFTCAP, true>, sm); once = true; }
-  hipLaunchKernelGGL((attn_fwd_kernel<D, true, false, SOFTCAP, true>), dim3(a.S / kRows, a.B * a.H), dim3(kThreads),
-                     sm, s, a);
-}
-
-template <int D, bool SOFTCAP>
-void run_bwd_docs(const AttnArgs& a, hipStream_t s) {
-  const size_t sm = fwd_smem<D>(), sm2 = dkdv_smem<D>();
-  static bool once = false;
-  if (!once) {
-    set_smem(attn_dq_kernel<D, true, false, SOFTCAP, true>, sm);
-    set_smem(attn_dkdv_kernel<D, true, false, SOFTCAP, true>, sm2);
-    once = true;
-  }
-  const dim3 grid(a.S / kRows, a.B * a.H);
-  hipLaunchKernelGGL((attn_delta_mfma_kernel<D>), grid, dim3(kThreads), 0, s, a);
-  hipLaunchKernelGGL((attn_dkdv_kernel<D, true, false, SOFTCAP, true>), grid, dim3(kThreads), sm2, s, a);
-  hipLaunchKernelGGL((attn_dq_kernel<D, true, false, SOFTCAP, true>), grid, dim3(kThreads), sm, s, a);
-}
-
-template <int D>
-void fwd_docs(const AttnArgs& a, hipStream_t s) {
-  if (a.softcap > 0.f) run_fwd_docs<D, true>(a, s);
-  else run_fwd_docs<D, false>(a, s);
-}
-
-template <int D>
-void bwd_docs(const AttnArgs& a, hipStream_t s) {
-  if (a.softcap > 0.f) run_bwd_docs<D, true>(a, s);
-  else run_bwd_docs<D, false>(a, s);
 }
 
 // Documents need the causal mask and both bounds; the kernels take "no window" as a window of S.
@@ -1713,61 +1656,43 @@ bool normalise_docs(AttnArgs& a) {
   return true;
 }
 
-template <int D>
-void fwd_softcap(const AttnArgs& a, hipStream_t s) {
-  if (a.window > 0) run_fwd_softcap<D, true, true>(a, s);
-  else if (a.causal) run_fwd_softcap<D, true, false>(a, s);
-  else run_fwd_softcap<D, false, false>(a, s);
+// The arguments as the launchers below read them: late fields resolved, window and documents normalised.
+AttnArgs prepared(const AttnArgs& ai) {
+  AttnArgs a = attn_resolved(ai);
+  a.threshold = dropout_threshold(a.p);
+  normalise_window(a);
+  normalise_docs(a);
+  return a;
 }
 
-template <int D>
-void bwd_softcap(const AttnArgs& a, hipStream_t s) {
-  if (a.window > 0) run_bwd_softcap<D, true, true>(a, s);
-  else if (a.causal) run_bwd_softcap<D, true, false>(a, s);
-  else run_bwd_softcap<D, false, false>(a, s);
+bool is_generic(const AttnArgs& a) {
+  return a.doc_start != nullptr || a.window > 0 || a.softcap > 0.f || a.sinks != nullptr;
 }
 
-// Attention sinks (a.sinks set): always the generic 64-row kernels too, under every mask above -- the S = 128,
-// wide D = 64 and long-sequence kernels know no sink.  SINK multiplies the forward kernel only: the backward runs
-// the sinkless instantiations on the forward's lse (run_bwd_window, run_bwd_softcap, run_bwd_docs as they are).
-template <int D, bool CAUSAL, bool WINDOW, bool SOFTCAP, bool DOCS>
-void run_fwd_sink(const AttnArgs& a, hipStream_t s) {
-  const size_t sm = fwd_smem<D>();
-  static bool once = false;
-  if (!once) { set_smem(attn_fwd_kernel<D, CAUSAL, WINDOW, SOFTCAP, DOCS, true>, sm); once = true; }
-  hipLaunchKernelGGL((attn_fwd_kernel<D, CAUSAL, WINDOW, SOFTCAP, DOCS, true>), dim3(a.S / kRows, a.B * a.H),
-                     dim3(kThreads), sm, s, a);
+// Run-time values as template arguments: f gets them as std::integral_constant tags.
+template <typename F>
+void with_d(int D, F&& f) {
+  if (D == 64) f(std::integral_constant<int, 64>{});
+  else if (D == 128) f(std::integral_constant<int, 128>{});
+  else f(std::integral_constant<int, 256>{});
 }
 
-template <int D, bool SOFTCAP>
-void fwd_sink_masks(const AttnArgs& a, hipStream_t s, bool docs) {
-  if (docs) run_fwd_sink<D, true, false, SOFTCAP, true>(a, s);
-  else if (a.window > 0) run_fwd_sink<D, true, true, SOFTCAP, false>(a, s);
-  else if (a.causal) run_fwd_sink<D, true, false, SOFTCAP, false>(a, s);
-  else run_fwd_sink<D, false, false, SOFTCAP, false>(a, s);
+template <typename F>
+void with_flag(bool on, F&& f) {
+  if (on) f(std::true_type{});
+  else f(std::false_type{});
 }
 
-template <int D>
-void fwd_sink(const AttnArgs& a, hipStream_t s, bool docs) {
-  if (a.softcap > 0.f) fwd_sink_masks<D, true>(a, s, docs);
-  else fwd_sink_masks<D, false>(a, s, docs);
-}
-
-// The backward of a call with sinks and no window, cap or documents: the generic dK/dV and dQ kernels at every S
-// and D, with delta from attn_delta_mfma_kernel, as under a window.
-template <int D, bool CAUSAL>
-void run_bwd_sink(const AttnArgs& a, hipStream_t s) {
-  const size_t sm = fwd_smem<D>(), sm2 = dkdv_smem<D>();
-  static bool once = false;
-  if (!once) {
-    set_smem(attn_dq_kernel<D, CAUSAL>, sm);
-    set_smem(attn_dkdv_kernel<D, CAUSAL>, sm2);
-    once = true;
-  }
-  const dim3 grid(a.S / kRows, a.B * a.H);
-  hipLaunchKernelGGL((attn_delta_mfma_kernel<D>), grid, dim3(kThreads), 0, s, a);
-  hipLaunchKernelGGL((attn_dkdv_kernel<D, CAUSAL>), grid, dim3(kThreads), sm2, s, a);
-  hipLaunchKernelGGL((attn_dq_kernel<D, CAUSAL>), grid, dim3(kThreads), sm, s, a);
+// The mask mode of prepared() arguments, for the forward and the backward alike: documents (which carry the
+// window) over a window over the causal mask over none.  f(CAUSAL, WINDOW, DOCS).
+template <typename F>
+void with_mask(const AttnArgs& a, F&& f) {
+  using Y = std::true_type;
+  using N = std::false_type;
+  if (a.doc_start != nullptr) f(Y{}, N{}, Y{});
+  else if (a.window > 0) f(Y{}, Y{}, N{});
+  else if (a.causal) f(Y{}, N{}, N{});
+  else f(N{}, N{}, N{});
 }
 
 }  // namespace
@@ -1782,89 +1707,42 @@ void attention_dsink(const float* lse, const float* delta, const float* sinks, f
 
 bool attention_supported(int S, int D) { return S > 0 && S % kRows == 0 && (D == 64 || D == 128 || D == 256); }
 
+// run_fwd / run_bwd are the plain paths (S = 128, wide D = 64 and the generic fallback); every option takes the
+// generic launchers.
 void attention_fwd(const AttnArgs& ai, hipStream_t s) {
-  AttnArgs a = attn_resolved(ai);
-  a.threshold = dropout_threshold(a.p);
-  normalise_window(a);
-  if (a.sinks != nullptr) {
-    const bool docs = normalise_docs(a);
-    if (a.D == 64) fwd_sink<64>(a, s, docs);
-    else if (a.D == 128) fwd_sink<128>(a, s, docs);
-    else fwd_sink<256>(a, s, docs);
-    return;
-  }
-  if (normalise_docs(a)) {
-    if (a.D == 64) fwd_docs<64>(a, s);
-    else if (a.D == 128) fwd_docs<128>(a, s);
-    else fwd_docs<256>(a, s);
-    return;
-  }
-  if (a.softcap > 0.f) {
-    if (a.D == 64) fwd_softcap<64>(a, s);
-    else if (a.D == 128) fwd_softcap<128>(a, s);
-    else fwd_softcap<256>(a, s);
-    return;
-  }
-  if (a.window > 0) {
-    if (a.D == 64) run_fwd_window<64>(a, s);
-    else if (a.D == 128) run_fwd_window<128>(a, s);
-    else run_fwd_window<256>(a, s);
-    return;
-  }
-  if (a.causal) {
-    if (a.D == 64) run_fwd<64, true>(a, s);
-    else if (a.D == 128) run_fwd<128, true>(a, s);
-    else run_fwd<256, true>(a, s);
-  } else {
-    if (a.D == 64) run_fwd<64, false>(a, s);
-    else if (a.D == 128) run_fwd<128, false>(a, s);
-    else run_fwd<256, false>(a, s);
-  }
+  const AttnArgs a = prepared(ai);
+  with_d(a.D, [&](auto d) {
+    constexpr int D = decltype(d)::value;
+    if (!is_generic(a)) {
+      with_flag(a.causal, [&](auto causal) { run_fwd<D, decltype(causal)::value>(a, s); });
+      return;
+    }
+    with_mask(a, [&](auto causal, auto window, auto docs) {
+      with_flag(a.softcap > 0.f, [&](auto cap) {
+        with_flag(a.sinks != nullptr, [&](auto sink) {
+          launch_fwd_generic<D, decltype(causal)::value, decltype(window)::value, decltype(cap)::value,
+                             decltype(docs)::value, decltype(sink)::value>(a, s);
+        });
+      });
+    });
+  });
 }
 
 void attention_bwd(const AttnArgs& ai, hipStream_t s) {
-  AttnArgs a = attn_resolved(ai);
-  a.threshold = dropout_threshold(a.p);
-  normalise_window(a);
-  if (normalise_docs(a)) {
-    if (a.D == 64) bwd_docs<64>(a, s);
-    else if (a.D == 128) bwd_docs<128>(a, s);
-    else bwd_docs<256>(a, s);
-    return;
-  }
-  if (a.softcap > 0.f) {
-    if (a.D == 64) bwd_softcap<64>(a, s);
-    else if (a.D == 128) bwd_softcap<128>(a, s);
-    else bwd_softcap<256>(a, s);
-    return;
-  }
-  if (a.window > 0) {
-    if (a.D == 64) run_bwd_window<64>(a, s);
-    else if (a.D == 128) run_bwd_window<128>(a, s);
-    else run_bwd_window<256>(a, s);
-    return;
-  }
-  if (a.sinks != nullptr) {  // the forward ran the generic kernel: so does the backward, at every S and D
-    if (a.causal) {
-      if (a.D == 64) run_bwd_sink<64, true>(a, s);
-      else if (a.D == 128) run_bwd_sink<128, true>(a, s);
-      else run_bwd_sink<256, true>(a, s);
-    } else {
-      if (a.D == 64) run_bwd_sink<64, false>(a, s);
-      else if (a.D == 128) run_bwd_sink<128, false>(a, s);
-      else run_bwd_sink<256, false>(a, s);
+  const AttnArgs a = prepared(ai);
+  with_d(a.D, [&](auto d) {
+    constexpr int D = decltype(d)::value;
+    if (!is_generic(a)) {
+      with_flag(a.causal, [&](auto causal) { run_bwd<D, decltype(causal)::value>(a, s); });
+      return;
     }
-    return;
-  }
-  if (a.causal) {
-    if (a.D == 64) run_bwd<64, true>(a, s);
-    else if (a.D == 128) run_bwd<128, true>(a, s);
-    else run_bwd<256, true>(a, s);
-  } else {
-    if (a.D == 64) run_bwd<64, false>(a, s);
-    else if (a.D == 128) run_bwd<128, false>(a, s);
-    else run_bwd<256, false>(a, s);
-  }
+    with_mask(a, [&](auto causal, auto window, auto docs) {
+      with_flag(a.softcap > 0.f, [&](auto cap) {
+        launch_bwd_generic<D, decltype(causal)::value, decltype(window)::value, decltype(cap)::value,
+                           decltype(docs)::value>(a, s);
+      });
+    });
+  });
 }
 
 }  // namespace mipipe

@@ -12,83 +12,92 @@ Three entry points:
   ``Hkv == H`` this is ``attention_packed``'s layout byte for byte.  On the
   bf16 kernels the K/V heads are read in place (no repeated copy) and the
   backward sums each group's dK / dV partials in one extra kernel; everything
-  else (fp32, the CPU, the padded shapes of ``_run_shape``) repeats the K/V
-  heads into ``[B, S, 3, H, D]`` and calls :func:`attention_packed`, autograd
+  else (fp32, the CPU, the padded shapes of ``_plan``) repeats the K/V heads
+  into ``[B, S, 3, H, D]`` and runs as :func:`attention_packed`, autograd
   summing the group.
 * :func:`attention` -- the usual ``q, k, v [B, H, S, D]`` API (views are
   permuted, not copied); ``k`` and ``v`` may have ``Hkv | H`` heads (repeated).
 
 Causal masking and attention dropout are supported; the dropout mask is
 regenerated from Philox (seed, offset) in backward, so checkpoint recompute
-replays it exactly.  Supported on the GPU path: bf16 with ``S % 64 == 0`` and
-``D in {64, 128, 256}`` (attention.hip), fp32 with ``S % 32 == 0`` and
-``D in {64, 128}`` (attention_f32.hip, the reference's own precision); the
-CPU path is eager math.  Any smaller head dim (e.g. 32, 80, 96, 160) runs on
-the kernels zero-padded to the next supported one (the scale stays that of the
-real head dim; the padded columns are sliced off), and a non-causal sequence of
-an unsupported length runs padded too when its head dim leaves a spare padded
-feature to mask the padded keys with (bf16), or with the kernels' own key bound
-(fp32: ``kv_len``, so the reference's fp32 D=64 tail window runs on the kernels;
-``_run_shape``).  A CAUSAL sequence of any other length (the
-reference's ``get_batch`` tail window, /root/reference/main.py:108-113) is
-zero-padded at the end to the next supported length: under the causal mask
-no real query sees a padded key, so the real rows are exact; the padded rows
-are sliced off (and get no gradient).
+replays it exactly.  The kernels tile bf16 with ``S % 64 == 0`` and ``D in {64,
+128, 256}`` (attention.hip) and fp32 with ``S % 32 == 0`` and ``D in {64, 128}``
+(attention_f32.hip, the reference's own precision).  The CPU is the eager math
+of :func:`attention_reference`.  On the GPU one function, :func:`_plan`, says
+for every entry point and every option at which shape a call runs on the
+kernels, or that it has no native form and runs the eager math as well (noted
+once per shape); its docstring is the table.  It chooses among three ways to
+fit a shape the kernels do not tile:
 
-Sliding-window attention: every entry point takes a keyword-only ``window=W``
-(an int >= 1, with ``causal=True``): query ``i`` attends the ``W`` keys ``i - W
-< j <= i``, its own included -- the Hugging Face / Mistral ``sliding_window``
-convention (flash-attn's ``window_size=(W - 1, 0)``).  ``window=None`` or ``W >=
-S`` is plain causal attention, on the code path it always took.  A bf16 call on
-the GPU with ``W < S`` runs attention.hip's generic kernels, which skip the
-64-key tiles wholly below the band as well as those above the diagonal (about
-``S * W`` work instead of ``S^2 / 2``); grouped-query heads are read in place
-as without a window, and the dropout mask is the causal call's restricted to
-the band.  The padded shapes above stay native too: padded keys lie after
-every real query and padded features add 0.  fp32 sliding-window attention is
-not native: it, the CPU and the shapes ``_run_shape`` rejects use the eager
-math of :func:`attention_reference` with the band mask.
+* Feature padding.  Any smaller head dim (e.g. 32, 80, 96, 160) is zero-padded
+  to the next supported one: the padded features add 0 to every raw score (the
+  scale stays that of the real head dim) and the padded columns are sliced off.
+* Causal end padding.  A CAUSAL sequence of any other length (the reference's
+  ``get_batch`` tail window) is zero-padded at the end to the next supported
+  length: under the causal mask no real query sees a padded key, so the real
+  rows are exact; the padded rows are sliced off (and get no gradient).
+* A key mask or key bound.  A non-causal sequence of an unsupported length runs
+  padded too: in bf16 when its head dim leaves a spare padded feature to mask
+  the padded keys with (1 in every query, 0 in every real key, -32768 in every
+  padded key, which then scores ``-32768 * scale`` and gets weight 0), in fp32
+  with the kernels' own key bound (``kv_len``, so the reference's fp32 D=64 tail
+  window runs on the kernels).
 
-Logit soft-capping: every entry point takes a keyword-only ``softcap=c`` (a
-finite number > 0; ``None`` is no cap and the code path it always was): the
-scaled scores become ``c * tanh(s / c)`` before the masks and the softmax --
-flash-attn's ``softcap``, Gemma-2's ``attn_logit_softcapping``.  A bf16 call on
-the GPU runs attention.hip's generic kernels (non-causal, causal, or causal
-with a window), whatever S and D; grouped-query heads are read in place and
-the dropout mask is the uncapped call's.  Causal end padding and head-dim
-padding stay native (padded features add 0 to the raw score, before the cap).
-A non-causal sequence of an unsupported length does not: the spare-feature key
-mask scores a padded key at ``-32768 * scale`` and the cap would bring that
-back to ``-c``, so that shape, fp32 and the CPU use :func:`attention_reference`.
-The kernels take ``tanh`` as ``1 - 2 / (1 + exp2(.))`` in fp32: its absolute
-error of about 2e-7 is an error of about ``c * 2e-7`` in the capped score, so
-it grows with ``c`` (nothing at 30 or 50; 1e-3 in the exponent at 5000).
+A window ``< S``, a soft cap, document bounds or sinks make a call generic: in
+bf16 on the GPU it runs attention.hip's generic 64-row kernels, whatever S and D
+(the S = 128, wide D = 64 and long-sequence kernels know none of the options);
+grouped-query heads are read in place as without an option and the dropout mask
+is the plain call's, restricted to the visible keys.  Feature padding and causal
+end padding stay native (padded keys lie after every real query and padded
+features add 0 to the raw score, before a cap); fp32, the CPU and the shapes
+``_plan`` rejects use :func:`attention_reference` with the same options.  Every
+entry point takes the options keyword-only, ``None`` being the code path it
+always was:
 
-Document masks (packed sequences): every entry point takes a keyword-only ``doc_bounds`` -- int32 ``[B, 2, S]``,
-``[b, 0, i]`` the index of the first token of token ``i``'s document and ``[b, 1, i]`` one past its last
-(``utils.data.document_bounds``), with ``causal=True``: query ``i`` attends key ``j`` iff ``start[i] <= j <= i``
-(and ``j > i - W`` under a window).  ``None`` is the code path it always was.  A bf16 call on the GPU runs
-attention.hip's generic kernels with the window merged at run time; they skip the key tiles before a query
-tile's first document and the query tiles after a key tile's last one, grouped-query heads are read in place
-and the dropout mask is the causal call's restricted to the visible keys.  Causal end padding and head-dim
-padding stay native (the pad tokens become one trailing document); fp32, the CPU and the shapes that cannot be
-padded use :func:`attention_reference` with the document mask.  The contract on the values (``start[i] <= i <
-end[i]``, both rows non-decreasing) is the caller's: :func:`check_doc_bounds` validates it on the host, with a
-sync, and is never called on the hot path; the kernels clamp the loop bounds they take from the tensor.
-:func:`use_documents` sets the bounds for the calling thread (``AttentionCore`` reads them).
+Sliding-window attention, ``window=W`` (an int >= 1, with ``causal=True``): query
+``i`` attends the ``W`` keys ``i - W < j <= i``, its own included -- the Hugging
+Face / Mistral ``sliding_window`` convention (flash-attn's ``window_size=(W - 1,
+0)``).  ``W >= S`` is plain causal attention, on the code path it always took.
+The kernels skip the 64-key tiles wholly below the band as well as those above
+the diagonal (about ``S * W`` work instead of ``S^2 / 2``).
 
-Attention sinks: every entry point takes a keyword-only ``sinks`` -- a ``[H]`` tensor, one learned logit per query
-head (also under grouped-query attention), fp32 or the activations' dtype.  The sink joins the softmax's
-normalisation after the cap and the masks, neither scaled nor capped, and has no value vector: ``p_ij = exp(s_ij -
-m) / (exp(sink_h - m) + sum_j exp(s_ij - m))`` -- Hugging Face gpt-oss's ``softmax(cat([scores, sinks], -1))[...,
-:-1]``.  ``None`` is the code path it always was; ``-inf`` is "no sink for this head".  It works with
-``causal=False`` too, and dropout acts on the real keys' ``p_ij`` only, with the sinkless call's mask.  A bf16 call
-on the GPU runs attention.hip's generic kernels whatever S and D: the sink is folded in once after the forward's
-key loop, the three backward kernels are the sinkless ones reading the forward's ``lse``, and ``dsinks[h] = -sum
-exp(sink_h - lse) * delta`` comes from one small fixed-order reduction (the same bits on every run; it goes
-straight into the parameter's fp32 ``main_grad`` where there is one).  Every padded shape stays native, the
-non-causal key mask included (a padded key still underflows against a running max the sink can only raise) unless
-there is a cap as well; fp32, the CPU and the shapes that cannot be padded use :func:`attention_reference`.
+Logit soft-capping, ``softcap=c`` (a finite number > 0): the scaled scores become
+``c * tanh(s / c)`` before the masks and the softmax -- flash-attn's ``softcap``,
+Gemma-2's ``attn_logit_softcapping`` -- non-causal, causal, or causal with a
+window.  A non-causal sequence of an unsupported length is not native: the
+spare-feature key mask scores a padded key at ``-32768 * scale`` and the cap
+would bring that back to ``-c``.  The kernels take ``tanh`` as ``1 - 2 / (1 +
+exp2(.))`` in fp32: its absolute error of about 2e-7 is an error of about ``c *
+2e-7`` in the capped score, so it grows with ``c`` (nothing at 30 or 50; 1e-3 in
+the exponent at 5000).
+
+Document masks (packed sequences), ``doc_bounds`` -- int32 ``[B, 2, S]``, ``[b, 0,
+i]`` the index of the first token of token ``i``'s document and ``[b, 1, i]`` one
+past its last (``utils.data.document_bounds``), with ``causal=True``: query ``i``
+attends key ``j`` iff ``start[i] <= j <= i`` (and ``j > i - W`` under a window,
+which the kernels merge at run time).  They skip the key tiles before a query
+tile's first document and the query tiles after a key tile's last one.  Under
+causal end padding the pad tokens become one trailing document.  The contract on
+the values (``start[i] <= i < end[i]``, both rows non-decreasing) is the caller's:
+:func:`check_doc_bounds` validates it on the host, with a sync, and is never
+called on the hot path; the kernels clamp the loop bounds they take from the
+tensor.  :func:`use_documents` sets the bounds for the calling thread
+(``AttentionCore`` reads them).
+
+Attention sinks, ``sinks`` -- a ``[H]`` tensor, one learned logit per query head
+(also under grouped-query attention), fp32 or the activations' dtype; ``-inf`` is
+"no sink for this head".  The sink joins the softmax's normalisation after the
+cap and the masks, neither scaled nor capped, and has no value vector: ``p_ij =
+exp(s_ij - m) / (exp(sink_h - m) + sum_j exp(s_ij - m))`` -- Hugging Face
+gpt-oss's ``softmax(cat([scores, sinks], -1))[..., :-1]``.  It works with
+``causal=False`` too, and dropout acts on the real keys' ``p_ij`` only, with the
+sinkless call's mask.  The sink is folded in once after the forward's key loop,
+the three backward kernels are the sinkless ones reading the forward's ``lse``,
+and ``dsinks[h] = -sum exp(sink_h - lse) * delta`` comes from one small
+fixed-order reduction (the same bits on every run; it goes straight into the
+parameter's fp32 ``main_grad`` where there is one).  Every padded shape stays
+native, the non-causal key mask included (a padded key still underflows against
+a running max the sink can only raise), unless there is a cap as well.
 """
 from __future__ import annotations
 
@@ -279,12 +288,10 @@ def clear_keep_words() -> None:
 
 def _attention_fwd(kern, q, k, v, causal, p, scale, kv_len, window=0, softcap=0.0, docs=None, sinks=None):
     global _keep_bytes
-    if sinks is not None:  # the generic kernels, as below
-        return kern.attention_fwd(q, k, v, causal, p, scale, kv_len, None, 0, 0, window, softcap, docs, sinks)
-    if docs is not None:  # the generic kernels, as below
-        return kern.attention_fwd(q, k, v, causal, p, scale, kv_len, None, 0, 0, window, softcap, docs)
-    if window or softcap:  # the generic kernels: the mask is regenerated from Philox, there are no keep words
-        return kern.attention_fwd(q, k, v, causal, p, scale, kv_len, None, 0, 0, window, softcap)
+    if window or softcap or docs is not None or sinks is not None:
+        # the generic kernels: the mask is regenerated from Philox, there are no keep words
+        return kern.attention_fwd(q, k, v, causal, p, scale, kv_len, window=window, softcap=softcap, doc_bounds=docs,
+                                  sinks=sinks)
     reuse = _KEEP_REUSE and p > 0 and q.is_cuda and q.dtype == torch.bfloat16 and kv_len == 0
     words = key = None
     if reuse and is_recomputing():
@@ -331,34 +338,54 @@ def _dsinks_grad(sinks: Optional[Tensor], ds: Optional[Tensor], accumulated: boo
     return None if ds is None or accumulated else ds.to(sinks.dtype)
 
 
+def _forward(ctx, inputs, q, k, v, causal, p, scale, kv_len, window, softcap, docs, sinks):
+    """The Functions' forward: runs the kernel on the views ``q, k, v`` of ``inputs``, saves ``inputs`` with the
+    results and stashes the scalars."""
+    sk = _kernel_sinks(sinks)
+    o, lse, seed, offset, bits = _attention_fwd(kernels_for(q), q, k, v, causal, p, scale, kv_len, window, softcap,
+                                                docs, sk)
+    ctx.save_for_backward(*inputs, o, lse, bits, docs, sinks, sk)
+    ctx.scalars = (causal, p, scale, seed, offset, kv_len, window, softcap)
+    return o
+
+
+def _backward(ctx, do, views):
+    """The Functions' backward: one gradient buffer per saved input, of which ``views`` gives the q, k, v views as
+    it does of the inputs.  Returns the buffers and the sinks' gradient (``sinks`` is each forward's last
+    argument)."""
+    *inputs, o, lse, bits, docs, sinks, sk = ctx.saved_tensors
+    causal, p, scale, seed, offset, kv_len, window, softcap = ctx.scalars
+    if do.stride() != o.stride():
+        do = do.contiguous()
+    grads = [torch.empty_like(t) for t in inputs]
+    ds, acc = _dsinks_out(sinks, sk, sinks is not None and ctx.needs_input_grad[-1])
+    kernels_for(do).attention_bwd(do, *views(*inputs), o, lse, causal, p, scale, seed, offset, *views(*grads),
+                                  bits if bits.numel() else None, kv_len, window, softcap, docs, sk, ds, acc)
+    return grads, _dsinks_grad(sinks, ds, acc)
+
+
+def _heads(qkv: Tensor, n_kv: int) -> Tuple[Tensor, Tensor, Tensor]:
+    """The Q, K and V head slices of a packed ``[B, S, H + 2 Hkv, D]``."""
+    H = qkv.shape[2] - 2 * n_kv
+    return qkv.narrow(2, 0, H), qkv.narrow(2, H, n_kv), qkv.narrow(2, H + n_kv, n_kv)
+
+
 class _AttentionPacked(torch.autograd.Function):
-    """``qkv [B, S, 3, H, D]`` (contiguous) in, ``o [B, S, H, D]`` out; the
-    backward produces the packed ``dqkv`` in one buffer."""
+    """``qkv [B, S, H + 2 Hkv, D]`` (contiguous) in, ``o [B, S, H, D]`` out.  Q, K and V are head slices of the
+    one buffer (same strides, fewer K/V heads when ``n_kv < H``: bf16 only); ``[B, S, 3, H, D]`` is the same bytes
+    with ``n_kv = H``.  The backward writes dQ and the group-summed dK / dV into one packed ``dqkv`` of the same
+    layout (the binding owns the per-query-head scratch)."""
 
     @staticmethod
-    def forward(ctx, qkv, causal, p, scale, kv_len=0, window=0, softcap=0.0, docs=None,  # type: ignore[override]
-                sinks=None):
-        kern = kernels_for(qkv)
-        q, k, v = qkv.select(2, 0), qkv.select(2, 1), qkv.select(2, 2)
-        sk = _kernel_sinks(sinks)
-        o, lse, seed, offset, bits = _attention_fwd(kern, q, k, v, causal, p, scale, kv_len, window, softcap, docs, sk)
-        ctx.save_for_backward(qkv, o, lse, bits, docs, sinks, sk)
-        ctx.causal, ctx.p, ctx.scale, ctx.seed, ctx.offset, ctx.kv_len = causal, p, scale, seed, offset, kv_len
-        ctx.window, ctx.softcap = window, softcap
-        return o
+    def forward(ctx, qkv, n_kv, causal, p, scale, kv_len=0, window=0, softcap=0.0,  # type: ignore[override]
+                docs=None, sinks=None):
+        ctx.n_kv = n_kv
+        return _forward(ctx, (qkv,), *_heads(qkv, n_kv), causal, p, scale, kv_len, window, softcap, docs, sinks)
 
     @staticmethod
     def backward(ctx, do):  # type: ignore[override]
-        qkv, o, lse, bits, docs, sinks, sk = ctx.saved_tensors
-        kern = kernels_for(do)
-        if do.stride() != o.stride():
-            do = do.contiguous()
-        dqkv = torch.empty_like(qkv)
-        ds, acc = _dsinks_out(sinks, sk, sinks is not None and ctx.needs_input_grad[8])
-        kern.attention_bwd(do, qkv.select(2, 0), qkv.select(2, 1), qkv.select(2, 2), o, lse, ctx.causal, ctx.p,
-                           ctx.scale, ctx.seed, ctx.offset, dqkv.select(2, 0), dqkv.select(2, 1), dqkv.select(2, 2),
-                           bits if bits.numel() else None, ctx.kv_len, ctx.window, ctx.softcap, docs, sk, ds, acc)
-        return dqkv, None, None, None, None, None, None, None, _dsinks_grad(sinks, ds, acc)
+        (dqkv,), dsinks = _backward(ctx, do, lambda t: _heads(t, ctx.n_kv))
+        return dqkv, None, None, None, None, None, None, None, None, dsinks
 
 
 class _Attention(torch.autograd.Function):
@@ -367,114 +394,56 @@ class _Attention(torch.autograd.Function):
     @staticmethod
     def forward(ctx, q, k, v, causal, p, scale, kv_len=0, window=0, softcap=0.0, docs=None,  # type: ignore[override]
                 sinks=None):
-        kern = kernels_for(q)
-        sk = _kernel_sinks(sinks)
-        o, lse, seed, offset, bits = _attention_fwd(kern, q, k, v, causal, p, scale, kv_len, window, softcap, docs, sk)
-        ctx.save_for_backward(q, k, v, o, lse, bits, docs, sinks, sk)
-        ctx.causal, ctx.p, ctx.scale, ctx.seed, ctx.offset, ctx.kv_len = causal, p, scale, seed, offset, kv_len
-        ctx.window, ctx.softcap = window, softcap
-        return o
+        return _forward(ctx, (q, k, v), q, k, v, causal, p, scale, kv_len, window, softcap, docs, sinks)
 
     @staticmethod
     def backward(ctx, do):  # type: ignore[override]
-        q, k, v, o, lse, bits, docs, sinks, sk = ctx.saved_tensors
-        kern = kernels_for(do)
-        if do.stride() != o.stride():
-            do = do.contiguous()
-        dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
-        ds, acc = _dsinks_out(sinks, sk, sinks is not None and ctx.needs_input_grad[10])
-        kern.attention_bwd(do, q, k, v, o, lse, ctx.causal, ctx.p, ctx.scale, ctx.seed, ctx.offset, dq, dk, dv,
-                           bits if bits.numel() else None, ctx.kv_len, ctx.window, ctx.softcap, docs, sk, ds, acc)
-        return dq, dk, dv, None, None, None, None, None, None, None, _dsinks_grad(sinks, ds, acc)
-
-
-class _AttentionGqaPacked(torch.autograd.Function):
-    """``qkv [B, S, H + 2 Hkv, D]`` (contiguous, bf16) in, ``o [B, S, H, D]`` out.  Q, K and V are head
-    slices of the one buffer (same strides, fewer K/V heads); the backward writes dQ and the group-summed
-    dK / dV into one packed ``dqkv`` of the same layout (the binding owns the per-query-head scratch)."""
-
-    @staticmethod
-    def forward(ctx, qkv, n_kv, causal, p, scale, window=0, softcap=0.0, docs=None,  # type: ignore[override]
-                sinks=None):
-        kern = kernels_for(qkv)
-        H = qkv.shape[2] - 2 * n_kv
-        q, k, v = qkv[:, :, :H], qkv[:, :, H:H + n_kv], qkv[:, :, H + n_kv:]
-        sk = _kernel_sinks(sinks)
-        o, lse, seed, offset, bits = _attention_fwd(kern, q, k, v, causal, p, scale, 0, window, softcap, docs, sk)
-        ctx.save_for_backward(qkv, o, lse, bits, docs, sinks, sk)
-        ctx.n_kv, ctx.causal, ctx.p, ctx.scale, ctx.seed, ctx.offset = n_kv, causal, p, scale, seed, offset
-        ctx.window, ctx.softcap = window, softcap
-        return o
-
-    @staticmethod
-    def backward(ctx, do):  # type: ignore[override]
-        qkv, o, lse, bits, docs, sinks, sk = ctx.saved_tensors
-        kern = kernels_for(do)
-        if do.stride() != o.stride():
-            do = do.contiguous()
-        n_kv = ctx.n_kv
-        H = qkv.shape[2] - 2 * n_kv
-        dqkv = torch.empty_like(qkv)
-        ds, acc = _dsinks_out(sinks, sk, sinks is not None and ctx.needs_input_grad[8])
-        kern.attention_bwd(do, qkv[:, :, :H], qkv[:, :, H:H + n_kv], qkv[:, :, H + n_kv:], o, lse, ctx.causal, ctx.p,
-                           ctx.scale, ctx.seed, ctx.offset, dqkv[:, :, :H], dqkv[:, :, H:H + n_kv],
-                           dqkv[:, :, H + n_kv:], bits if bits.numel() else None, 0, ctx.window, ctx.softcap, docs,
-                           sk, ds, acc)
-        return dqkv, None, None, None, None, None, None, None, _dsinks_grad(sinks, ds, acc)
+        (dq, dk, dv), dsinks = _backward(ctx, do, lambda q, k, v: (q, k, v))
+        return dq, dk, dv, None, None, None, None, None, None, None, dsinks
 
 
 _noted = set()
 
 
 def _note_math_path(S: int, D: int, dtype, window: Optional[int] = None, softcap: Optional[float] = None,
-                    docs: bool = False, sinks: bool = False) -> None:
+                    docs: bool = False, sinks: bool = False, stacklevel: int = 3) -> None:
     """Shapes outside the kernels' tiling use the eager math path; say so once per shape."""
-    key = (S, D, dtype) if window is None else (S, D, dtype, "window")
-    if softcap is not None:
-        key += ("softcap",)
-    if docs:
-        key += ("documents",)
-    if sinks:
-        key += ("sinks",)
+    # (set, key tag, the call's words, the warning's tail) per option, in the key's order
+    notes = [
+        (window is not None, "window", f" window={window}",
+         ".  fp32 sliding-window attention is not native: the window runs on the bf16 kernels only"),
+        (softcap is not None, "softcap", f" softcap={softcap}",
+         ".  Soft-capped attention is native in bf16 only, and not for a non-causal sequence of an unsupported "
+         "length"),
+        (docs, "documents", " doc_bounds", ".  Document-masked attention is native in bf16 only"),
+        (sinks, "sinks", " sinks", ".  Attention with sinks is native in bf16 only"),
+    ]
+    notes = [n for n in notes if n[0]]
+    key = (S, D, dtype) + tuple(n[1] for n in notes)
     if key not in _noted:
         _noted.add(key)
         import warnings
 
-        extra = "" if window is None else f" window={window}"
-        tail = "" if window is None else ".  fp32 sliding-window attention is not native: the window runs on the bf16 kernels only"
-        if softcap is not None:
-            extra += f" softcap={softcap}"
-            tail += (".  Soft-capped attention is native in bf16 only, and not for a non-causal sequence of an "
-                     "unsupported length")
-        if docs:
-            extra += " doc_bounds"
-            tail += ".  Document-masked attention is native in bf16 only"
-        if sinks:
-            extra += " sinks"
-            tail += ".  Attention with sinks is native in bf16 only"
+        extra, tail = "".join(n[2] for n in notes), "".join(n[3] for n in notes)
         warnings.warn(f"mipipe attention: S={S} D={D} {dtype}{extra} runs the eager math path (HIP kernels: bf16 "
                       "with S % 64 == 0, D in {64, 128, 256}; fp32 with S % 32 == 0, D in {64, 128})" + tail,
-                      stacklevel=3)
+                      stacklevel=stacklevel)
 
 
-def _window_native(t: Tensor) -> bool:
-    """A windowed call runs on the kernels only in bf16 on the GPU."""
-    return t.is_cuda and t.dtype == torch.bfloat16
-
-
-def _gpu_ok(t: Tensor, S: int, D: int) -> bool:
-    if t.dtype == torch.bfloat16:
-        return kernels_for(t).attention_supported(S, D)
-    if t.dtype == torch.float32:
-        return kernels_for(t).attention_f32_supported(S, D)
+def _gpu_ok(dtype: torch.dtype, S: int, D: int) -> bool:
+    """The kernels tile (S, D) in ``dtype`` as it is: the one place the plan asks the extension."""
+    if dtype == torch.bfloat16:
+        return kernels_for().attention_supported(S, D)
+    if dtype == torch.float32:
+        return kernels_for().attention_f32_supported(S, D)
     return False
 
 
-def _causal_pad(t: Tensor, S: int, D: int) -> Optional[int]:
+def _causal_pad(dtype: torch.dtype, S: int, D: int) -> Optional[int]:
     """The padded length a causal sequence of S runs at on the kernels (None: none fits)."""
-    step = 64 if t.dtype == torch.bfloat16 else 32
+    step = 64 if dtype == torch.bfloat16 else 32
     for sp in (-(-S // step) * step, max(128, -(-S // step) * step)):
-        if sp != S and _gpu_ok(t, sp, D):
+        if sp != S and _gpu_ok(dtype, sp, D):
             return sp
     return None
 
@@ -482,63 +451,48 @@ def _causal_pad(t: Tensor, S: int, D: int) -> Optional[int]:
 _KEY_MASK = -32768.0  # exact in bf16; times the query's 1 and any scale >= 2^-8: exp underflows to 0
 
 
-def _run_shape(t: Tensor, S: int, D: int, causal: bool, scale: float) -> Optional[Tuple[int, int, int]]:
-    """(sequence length, head dim, key bound) the kernels run a (S, D) attention
-    at, or None (eager path).  The key bound (``kv_len``, 0 = none) is set for a
-    non-causal fp32 sequence padded at the end: the fp32 kernels mask keys past
-    it themselves.
+def _plan(dtype: torch.dtype, S: int, D: int, causal: bool, scale: float, *, generic: bool,
+          softcap: Optional[float], sinks: bool) -> Optional[Tuple[int, int, int, bool]]:
+    """``(sp, dp, kv_len, key_mask)`` a GPU call of (S, D) runs at on the kernels, or None (the eager path).
+    ``generic``: the call has a window ``< S``, a cap, document bounds or sinks.  ``sp`` / ``dp`` are the padded
+    sequence length and head dim, ``kv_len`` (0 = none) the key bound the fp32 kernels mask past themselves, and
+    ``key_mask`` says that the caller masks the padded keys through the spare feature ``D`` (the module doc).
 
-    * A head dim the kernels do not tile is zero-padded to the next one they do: the
-      padded features add 0 to every score (the softmax scale stays 1/sqrt(D) of the
-      real head dim) and give output / gradient columns that are sliced off.
-    * A causal sequence of an unsupported length is zero-padded at the end (see the
-      module doc).
-    * A non-causal one too, when a padded feature is free to mask the padded keys:
-      feature D is 1 in every query, 0 in every real key and -32768 in every padded
-      key, so a padded key scores -32768 * scale below any real one and gets weight 0
-      (its V rows are 0 as well)."""
-    dims = [D] + [d for d in ((64, 128, 256) if t.dtype == torch.bfloat16 else (64, 128)) if d > D]
-    for dp in dims:
-        if _gpu_ok(t, S, dp):
-            return S, dp, 0
-        if t.dtype == torch.float32 and not causal:  # key bound inside the kernel
-            sp = _causal_pad(t, S, dp)
-            if sp is not None:
-                return sp, dp, S
-            continue
-        # the spare-feature key mask needs exp(-32768 * scale) to underflow to 0
-        sp = _causal_pad(t, S, dp) if (causal or (dp > D and scale >= 2.0 ** -8)) else None
-        if sp is not None:
-            return sp, dp, 0
-    return None
-
-
-def _generic_shape(t: Tensor, S: int, D: int, causal: bool, scale: float) -> Optional[Tuple[int, int]]:
-    """(sequence length, head dim) a windowed or soft-capped bf16 call runs at on the generic kernels, or None.
-    End padding of a causal sequence and feature padding only: a soft-capped non-causal sequence of an
-    unsupported length has no native form, because the spare-feature key mask of :func:`_run_shape` scores a
-    padded key at ``-32768 * scale`` and the cap would bring that back to ``-softcap``."""
-    if _gpu_ok(t, S, D):
-        return S, D
-    run = _run_shape(t, S, D, causal, scale)
-    if run is None or (not causal and run[0] != S):
+    ====================  ===========================================================================
+    call                  runs at
+    ====================  ===========================================================================
+    any, (S, D) tiled     ``(S, D)`` as it is (generic: bf16 only)
+    plain                 the first ``dp`` in ``D`` and the supported head dims above it with: ``S``
+                          tiled -> ``(S, dp)``; fp32 non-causal -> end padding with ``kv_len = S``;
+                          causal -> end padding; bf16 non-causal with ``dp > D`` and ``scale >= 2^-8``
+                          (``exp(-32768 * scale)`` must underflow to 0) -> end padding with the key
+                          mask.  End padding is to the next multiple of 64 (fp32: 32), or 128.
+    generic               bf16 only; the plain answer unless it needs the key mask (a cap would bring
+                          a masked key's score back to ``-softcap``; a window and document bounds are
+                          causal anyway)
+    generic with sinks    bf16 only; the plain answer, the key mask included unless there is a cap
+                          (the sink only raises the row's running max, so a masked key underflows as
+                          it does without one)
+    ====================  ===========================================================================
+    """
+    bf16 = dtype == torch.bfloat16
+    if generic and not bf16:
         return None
-    return run[0], run[1]
-
-
-def _sink_shape(t: Tensor, S: int, D: int, causal: bool, scale: float,
-                softcap: Optional[float]) -> Optional[Tuple[int, int, bool]]:
-    """(sequence length, head dim, key mask) a bf16 call with sinks runs at on the generic kernels, or None:
-    :func:`_generic_shape`, and without a cap also :func:`_run_shape`'s non-causal sequence end-padded behind the
-    spare-feature key mask (key mask True: the caller sets the feature).  The sink only raises the row's running
-    max, so a padded key's ``-32768 * scale`` underflows as it does without one."""
-    run = _generic_shape(t, S, D, causal, scale)
-    if run is not None:
-        return run[0], run[1], False
-    if softcap is None and not causal:
-        full = _run_shape(t, S, D, causal, scale)
-        if full is not None:
-            return full[0], full[1], True
+    if _gpu_ok(dtype, S, D):
+        return S, D, 0, False
+    for dp in [D] + [d for d in ((64, 128, 256) if bf16 else (64, 128)) if d > D]:
+        if _gpu_ok(dtype, S, dp):
+            return S, dp, 0, False
+        if dtype == torch.float32 and not causal:  # key bound inside the kernel
+            sp = _causal_pad(dtype, S, dp)
+            if sp is not None:
+                return sp, dp, S, False
+        elif causal or (dp > D and scale >= 2.0 ** -8):
+            sp = _causal_pad(dtype, S, dp)
+            if sp is not None:
+                if not causal and generic and not (sinks and softcap is None):
+                    return None
+                return sp, dp, 0, not causal
     return None
 
 
@@ -554,44 +508,54 @@ def _pad_docs(docs: Tensor, S: int, sp: int) -> Tensor:
     return out
 
 
-def _packed_generic(qkv: Tensor, S: int, D: int, causal: bool, p: float, scale: float, window: Optional[int],
-                    softcap: Optional[float], docs: Optional[Tensor] = None,
-                    sinks: Optional[Tensor] = None) -> Tensor:
-    """:func:`attention_packed` with a window ``< S`` (causal), a soft cap, document bounds and / or sinks."""
-    if sinks is not None and _window_native(qkv):
-        run = _sink_shape(qkv, S, D, causal, scale, softcap)
-        if run is not None:
-            sp, dp, key_mask = run
-            if docs is not None:
-                docs = _pad_docs(docs.to(qkv.device), S, sp)
-            if (sp, dp) == (S, D):
-                return _AttentionPacked.apply(qkv.contiguous(), causal, p, scale, 0, window or 0, softcap or 0.0, docs,
-                                              sinks)
-            padded = F.pad(qkv, (0, dp - D, 0, 0, 0, 0, 0, sp - S))
-            if key_mask:  # mask the padded keys through the spare feature D, as attention_packed does
-                c = torch.zeros_like(padded)
-                c[:, :, 0, :, D] = 1.0
-                c[:, S:, 1, :, D] = _KEY_MASK
-                padded = padded + c
-            return _AttentionPacked.apply(padded, causal, p, scale, 0, window or 0, softcap or 0.0, docs,
-                                          sinks)[:, :S, :, :D]
-    elif _window_native(qkv):
-        run = _generic_shape(qkv, S, D, causal, scale)
-        if docs is not None and run is not None:
-            docs = _pad_docs(docs.to(qkv.device), S, run[0])
-        if run == (S, D):
-            return _AttentionPacked.apply(qkv.contiguous(), causal, p, scale, 0, window or 0, softcap or 0.0, docs)
-        if run is not None:  # bf16: end padding (causal) and feature padding only (no key bound)
-            sp, dp = run
-            padded = F.pad(qkv, (0, dp - D, 0, 0, 0, 0, 0, sp - S))
-            return _AttentionPacked.apply(padded, causal, p, scale, 0, window or 0, softcap or 0.0,
-                                          docs)[:, :S, :, :D]
-    q, k, v = qkv.select(2, 0), qkv.select(2, 1), qkv.select(2, 2)
-    if qkv.is_cuda:
-        _note_math_path(S, D, qkv.dtype, window, softcap, docs is not None, sinks is not None)
-    o = attention_reference(q.transpose(1, 2), k.transpose(1, 2), v.transpose(1, 2), causal, p, scale, window=window,
-                            softcap=softcap, doc_bounds=docs, sinks=sinks)
-    return o.transpose(1, 2)
+def _run_padded(run, ts, seq: int, heads: int, S: int, D: int, sp: int, dp: int, key_mask) -> Tensor:
+    """``run(*ts)`` with every tensor of ``ts`` zero-padded to ``sp`` along axis ``seq`` and to ``dp`` along the
+    last, and the result (same axes) sliced back to ``S`` and ``D``.  ``key_mask``, where the plan asks for one:
+    ``((i, h), (j, g))`` -- the queries are the heads ``h`` (a slice of axis ``heads``) of ``ts[i]``, the keys the
+    heads ``g`` of ``ts[j]`` -- sets the spare feature ``D`` to 1 in every query and to -32768 in every padded key."""
+    if (sp, dp) == (S, D):
+        return run(*ts)
+    ts = [F.pad(t, (0, dp - D) + (0, 0) * (t.dim() - 2 - seq) + (0, sp - S)) for t in ts]
+    if key_mask:
+        (qi, qh), (ki, kh) = key_mask
+        marks = {i: torch.zeros_like(ts[i]) for i in (qi, ki)}
+        at = [slice(None)] * ts[qi].dim()
+        at[heads], at[-1] = qh, D
+        marks[qi][tuple(at)] = 1.0
+        at[heads], at[seq] = kh, slice(S, None)
+        marks[ki][tuple(at)] = _KEY_MASK
+        for i, c in marks.items():
+            ts[i] = ts[i] + c
+    cut = [slice(None)] * 4
+    cut[seq], cut[-1] = slice(0, S), slice(0, D)
+    return run(*ts)[tuple(cut)]
+
+
+def _is_generic(window, softcap, docs, sinks) -> bool:
+    return window is not None or softcap is not None or docs is not None or sinks is not None
+
+
+def _packed(qkv: Tensor, n_kv: int, causal: bool, p: float, scale: float, window: Optional[int],
+            softcap: Optional[float], docs: Optional[Tensor], sinks: Optional[Tensor]) -> Tensor:
+    """The packed entry points after validation: ``qkv [B, S, H + 2 n_kv, D]`` -> ``o [B, S, H, D]``.  With
+    ``n_kv < H`` the caller has made sure the shape runs as it is."""
+    B, S, heads, D = qkv.shape
+    H = heads - 2 * n_kv
+    plan = _plan(qkv.dtype, S, D, causal, scale, generic=_is_generic(window, softcap, docs, sinks), softcap=softcap,
+                 sinks=sinks is not None) if qkv.is_cuda else None
+    if plan is None:
+        if qkv.is_cuda:
+            _note_math_path(S, D, qkv.dtype, window, softcap, docs is not None, sinks is not None, stacklevel=4)
+        q, k, v = (t.transpose(1, 2) for t in _heads(qkv, n_kv))
+        o = attention_reference(q, k, v, causal, p, scale, window=window, softcap=softcap, doc_bounds=docs,
+                                sinks=sinks)
+        return o.transpose(1, 2)
+    sp, dp, kv_len, key_mask = plan
+    if docs is not None:
+        docs = _pad_docs(docs.to(qkv.device), S, sp)
+    return _run_padded(lambda t: _AttentionPacked.apply(t.contiguous(), n_kv, causal, p, scale, kv_len, window or 0,
+                                                        softcap or 0.0, docs, sinks),
+                       (qkv,), 1, 2, S, D, sp, dp, ((0, slice(0, H)), (0, slice(H, H + n_kv))) if key_mask else None)
 
 
 def attention_packed(qkv: Tensor, causal: bool = False, dropout_p: float = 0.0, training: bool = True,
@@ -602,46 +566,22 @@ def attention_packed(qkv: Tensor, causal: bool = False, dropout_p: float = 0.0, 
     soft-capping, ``doc_bounds``: document masks, ``sinks``: attention sinks (module doc)."""
     B, S, three, H, D = qkv.shape
     assert three == 3
+    causal = bool(causal)
     p = float(dropout_p) if training else 0.0
     scale = float(scale) if scale is not None else 1.0 / math.sqrt(D)
-    window = _check_window(window, bool(causal), S)
+    window = _check_window(window, causal, S)
     softcap = _check_softcap(softcap)
-    docs = _check_docs(doc_bounds, bool(causal), B, S)
+    docs = _check_docs(doc_bounds, causal, B, S)
     sinks = _check_sinks(sinks, H, qkv.dtype)
-    if window is not None or softcap is not None or docs is not None or sinks is not None:
-        return _packed_generic(qkv, S, D, bool(causal), p, scale, window, softcap, docs, sinks)
-    if qkv.is_cuda and _gpu_ok(qkv, S, D):
-        return _AttentionPacked.apply(qkv.contiguous(), bool(causal), p, scale)
-    run = _run_shape(qkv, S, D, bool(causal), scale) if qkv.is_cuda else None
-    if run is not None:
-        sp, dp, kv_len = run
-        padded = F.pad(qkv, (0, dp - D, 0, 0, 0, 0, 0, sp - S))
-        if kv_len:  # the kernel masks keys >= S itself
-            return _AttentionPacked.apply(padded, bool(causal), p, scale, kv_len)[:, :S, :, :D]
-        if sp != S and not causal:  # mask the padded keys through the spare feature D
-            # [B, S, 3, H, D]: index (b, s, which, h, d) -> q = which 0, k = which 1, sequence dim 1
-            c = torch.zeros_like(padded)
-            c[:, :, 0, :, D] = 1.0
-            c[:, S:, 1, :, D] = _KEY_MASK
-            padded = padded + c
-        return _AttentionPacked.apply(padded, bool(causal), p, scale)[:, :S, :, :D]
-    q, k, v = qkv.select(2, 0), qkv.select(2, 1), qkv.select(2, 2)
-    if qkv.is_cuda:
-        _note_math_path(S, D, qkv.dtype)
-    o = attention_reference(q.transpose(1, 2), k.transpose(1, 2), v.transpose(1, 2), causal, p, scale)
-    return o.transpose(1, 2)
+    return _packed(qkv.reshape(B, S, 3 * H, D), H, causal, p, scale, window, softcap, docs, sinks)
 
 
 def _expand_kv(qkv: Tensor, n_kv: int) -> Tensor:
-    """``[B, S, H + 2 Hkv, D]`` -> ``[B, S, 3, H, D]`` with every K/V head repeated over its group
+    """``[B, S, H + 2 Hkv, D]`` -> ``[B, S, 3 H, D]`` with every K/V head repeated over its group
     (differentiable: the backward sums the group)."""
-    B, S, heads, D = qkv.shape
-    H = heads - 2 * n_kv
-    g = H // n_kv
-    q = qkv[:, :, :H]
-    k = qkv[:, :, H:H + n_kv].repeat_interleave(g, dim=2)
-    v = qkv[:, :, H + n_kv:].repeat_interleave(g, dim=2)
-    return torch.stack((q, k, v), dim=2)
+    q, k, v = _heads(qkv, n_kv)
+    g = q.shape[2] // n_kv
+    return torch.cat((q, k.repeat_interleave(g, dim=2), v.repeat_interleave(g, dim=2)), dim=2)
 
 
 def attention_gqa_packed(qkv: Tensor, n_kv_heads: int, causal: bool = False, dropout_p: float = 0.0,
@@ -659,28 +599,18 @@ def attention_gqa_packed(qkv: Tensor, n_kv_heads: int, causal: bool = False, dro
     if n_kv <= 0 or H <= 0 or H % n_kv != 0:
         raise ValueError(f"attention_gqa_packed: {heads} packed heads do not split into H + 2 * {n_kv} with "
                          f"{n_kv} dividing H")
-    window = _check_window(window, bool(causal), S)
+    causal = bool(causal)
+    p = float(dropout_p) if training else 0.0
+    scale = float(scale) if scale is not None else 1.0 / math.sqrt(D)
+    window = _check_window(window, causal, S)
     softcap = _check_softcap(softcap)
-    docs = _check_docs(doc_bounds, bool(causal), B, S)
+    docs = _check_docs(doc_bounds, causal, B, S)
     sinks = _check_sinks(sinks, H, qkv.dtype)
-    if n_kv == H:  # plain multi-head attention: the same bytes as [B, S, 3, H, D]
-        return attention_packed(qkv.reshape(B, S, 3, H, D), causal, dropout_p, training, scale, window=window,
-                                softcap=softcap, doc_bounds=docs, sinks=sinks)
-    if qkv.is_cuda and qkv.dtype == torch.bfloat16 and _gpu_ok(qkv, S, D):
-        p = float(dropout_p) if training else 0.0
-        scale = float(scale) if scale is not None else 1.0 / math.sqrt(D)
-        if sinks is not None:
-            return _AttentionGqaPacked.apply(qkv.contiguous(), n_kv, bool(causal), p, scale, window or 0,
-                                             softcap or 0.0,
-                                             None if docs is None else docs.to(qkv.device).contiguous(), sinks)
-        if docs is not None:
-            return _AttentionGqaPacked.apply(qkv.contiguous(), n_kv, bool(causal), p, scale, window or 0,
-                                             softcap or 0.0, docs.to(qkv.device).contiguous())
-        return _AttentionGqaPacked.apply(qkv.contiguous(), n_kv, bool(causal), p, scale, window or 0,
-                                         softcap or 0.0)
-    # the repeated-head fallback: sinks are per query head already
-    return attention_packed(_expand_kv(qkv, n_kv), causal, dropout_p, training, scale, window=window,
-                            softcap=softcap, doc_bounds=docs, sinks=sinks)
+    # Hkv == H is plain multi-head attention, the same bytes as [B, S, 3, H, D]; fewer K/V heads are read in place
+    # by the bf16 kernels at a shape they tile as it is, and repeated otherwise (sinks are per query head already)
+    if n_kv != H and not (qkv.is_cuda and qkv.dtype == torch.bfloat16 and _gpu_ok(qkv.dtype, S, D)):
+        qkv, n_kv = _expand_kv(qkv, n_kv), H
+    return _packed(qkv, n_kv, causal, p, scale, window, softcap, docs, sinks)
 
 
 def attention(
@@ -697,73 +627,31 @@ def attention(
             raise ValueError(f"attention: {k.shape[1]} / {v.shape[1]} K/V heads do not divide {q.shape[1]} query heads")
         g = q.shape[1] // k.shape[1]
         k, v = k.repeat_interleave(g, dim=1), v.repeat_interleave(g, dim=1)
+    B, _, S, D = q.shape
+    causal = bool(causal)
     p = float(dropout_p) if training else 0.0
-    scale = float(scale) if scale is not None else 1.0 / math.sqrt(q.shape[-1])
-    window = _check_window(window, bool(causal), q.shape[2])
+    scale = float(scale) if scale is not None else 1.0 / math.sqrt(D)
+    window = _check_window(window, causal, S)
     softcap = _check_softcap(softcap)
-    docs = _check_docs(doc_bounds, bool(causal), q.shape[0], q.shape[2])
+    docs = _check_docs(doc_bounds, causal, B, S)
     sinks = _check_sinks(sinks, q.shape[1], q.dtype)
-    if not q.is_cuda:
+    plan = _plan(q.dtype, S, D, causal, scale, generic=_is_generic(window, softcap, docs, sinks), softcap=softcap,
+                 sinks=sinks is not None) if q.is_cuda else None
+    if plan is None:
+        if q.is_cuda:
+            _note_math_path(S, D, q.dtype, window, softcap, docs is not None, sinks is not None)
         return attention_reference(q, k, v, causal, p, scale, window=window, softcap=softcap, doc_bounds=docs,
                                    sinks=sinks)
-    S, D = q.shape[2], q.shape[3]
-    if sinks is not None:
-        causal = bool(causal)
-        run = _sink_shape(q, S, D, causal, scale, softcap) if _window_native(q) else None
-        if run is None:
-            _note_math_path(S, D, q.dtype, window, softcap, docs is not None, True)
-            return attention_reference(q, k, v, causal, p, scale, window=window, softcap=softcap, doc_bounds=docs,
-                                       sinks=sinks)
-        sp, dp, key_mask = run
-        if docs is not None:
-            docs = _pad_docs(docs.to(q.device), S, sp)
-        pad = (lambda t: F.pad(t, (0, dp - D, 0, sp - S))) if (sp, dp) != (S, D) else (lambda t: t)  # noqa: E731
-        qp, kp, vp = pad(q), pad(k), pad(v)
-        if key_mask:  # mask the padded keys through the spare feature D, as below
-            cq, ck = torch.zeros_like(qp), torch.zeros_like(kp)
-            cq[..., D] = 1.0
-            ck[:, :, S:, D] = _KEY_MASK
-            qp, kp = qp + cq, kp + ck
-        qs, ks, vs = (t.transpose(1, 2) for t in (qp, kp, vp))
-        if not (qs.stride() == ks.stride() == vs.stride()) or qs.stride(3) != 1:
+    sp, dp, kv_len, key_mask = plan
+    if docs is not None:
+        docs = _pad_docs(docs.to(q.device), S, sp)
+
+    def run(q, k, v):
+        qs, ks, vs = (t.transpose(1, 2) for t in (q, k, v))
+        # (the fp32 key-bound path has always run on contiguous copies)
+        if kv_len or not (qs.stride() == ks.stride() == vs.stride()) or qs.stride(3) != 1:
             qs, ks, vs = (t.contiguous() for t in (qs, ks, vs))
-        o = _Attention.apply(qs, ks, vs, causal, p, scale, 0, window or 0, softcap or 0.0, docs, sinks)
-        return o.transpose(1, 2)[:, :, :S, :D]
-    if window is not None or softcap is not None or docs is not None:
-        causal = bool(causal)
-        run = _generic_shape(q, S, D, causal, scale) if _window_native(q) else None
-        if run is None:
-            _note_math_path(S, D, q.dtype, window, softcap, docs is not None)
-            return attention_reference(q, k, v, causal, p, scale, window=window, softcap=softcap, doc_bounds=docs)
-        sp, dp = run  # bf16: end padding (causal) and feature padding only (no key bound)
-        if docs is not None:
-            docs = _pad_docs(docs.to(q.device), S, sp)
-        pad = (lambda t: F.pad(t, (0, dp - D, 0, sp - S))) if (sp, dp) != (S, D) else (lambda t: t)  # noqa: E731
-        qs, ks, vs = (pad(t).transpose(1, 2) for t in (q, k, v))
-        if not (qs.stride() == ks.stride() == vs.stride()) or qs.stride(3) != 1:
-            qs, ks, vs = (t.contiguous() for t in (qs, ks, vs))
-        o = _Attention.apply(qs, ks, vs, causal, p, scale, 0, window or 0, softcap or 0.0, docs)
-        return o.transpose(1, 2)[:, :, :S, :D]
-    if not _gpu_ok(q, S, D):
-        run = _run_shape(q, S, D, bool(causal), scale)
-        if run is None:
-            _note_math_path(S, D, q.dtype)
-            return attention_reference(q, k, v, causal, p, scale)
-        sp, dp, kv_len = run
-        pad = lambda t: F.pad(t, (0, dp - D, 0, sp - S))  # noqa: E731
-        qp, kp = pad(q), pad(k)
-        if kv_len:  # the kernel masks keys >= S itself
-            qs, ks, vs = (t.transpose(1, 2) for t in (qp, kp, pad(v)))
-            qs, ks, vs = (t.contiguous() for t in (qs, ks, vs))
-            return _Attention.apply(qs, ks, vs, bool(causal), p, scale, kv_len).transpose(1, 2)[:, :, :S, :D]
-        if sp != S and not causal:  # mask the padded keys through the spare feature D ([B, H, S, D])
-            cq, ck = torch.zeros_like(qp), torch.zeros_like(kp)
-            cq[..., D] = 1.0
-            ck[:, :, S:, D] = _KEY_MASK
-            qp, kp = qp + cq, kp + ck
-        return attention(qp, kp, pad(v), causal, dropout_p, training, scale)[:, :, :S, :D]
-    qs, ks, vs = (t.transpose(1, 2) for t in (q, k, v))
-    if not (qs.stride() == ks.stride() == vs.stride()) or qs.stride(3) != 1:
-        qs, ks, vs = (t.contiguous() for t in (qs, ks, vs))
-    o = _Attention.apply(qs, ks, vs, bool(causal), p, scale)
-    return o.transpose(1, 2)
+        o = _Attention.apply(qs, ks, vs, causal, p, scale, kv_len, window or 0, softcap or 0.0, docs, sinks)
+        return o.transpose(1, 2)
+
+    return _run_padded(run, (q, k, v), 2, 1, S, D, sp, dp, ((0, slice(None)), (1, slice(None))) if key_mask else None)
