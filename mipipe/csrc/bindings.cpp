@@ -1296,9 +1296,6 @@ void gemm_run(at::ScalarType t, const GemmArgs& g, hipStream_t s) {
   else gemm_bf16(g, s);
 }
 
-bool py_gemm_supported(int64_t M, int64_t N, int64_t K) { return gemm_supported(M, N, K); }
-bool py_gemm_f32_supported(int64_t M, int64_t N, int64_t K) { return gemm_f32_supported(M, N, K); }
-
 // y[M,N] = act(x[M,K] . w[N,K]^T + bias) with dropout; optional pre-activation.
 // xt (optional, bf16 [K, M]): also written with x^T by the same GEMM (its
 // blocks transpose the x tiles they stage anyway), the K-contiguous operand of
@@ -1361,18 +1358,18 @@ std::tuple<Tensor, std::optional<Tensor>, int64_t, int64_t> py_linear_fwd(Tensor
              "linear_fwd: bits must be uint8 [M, N / 8] with unit column stride");
     g.bits = bits->data_ptr();
     g.ldbits = bits->stride(0);
-    MP_CHECK(dt == at::kBFloat16 && gemm_bits_ok(g), "linear_fwd: this launch cannot write bits (gemm_bits_ok)");
+    MP_CHECK(dt == at::kBFloat16 && gemm_plan(g).bits_ok, "linear_fwd: this launch cannot write bits (GemmPlan::bits_ok)");
   }
   gemm_run(dt, g, cur_stream(x));
   return {y, pre, (int64_t)seed, (int64_t)offset};
 }
 
-// Split-K (bf16 GEMMs on under-filled grids, gemm_splitk_factor): the fp32
+// Split-K (bf16 GEMMs on under-filled grids, GemmPlan::k_splits): the fp32
 // partials' workspace, from the stream-ordered caching allocator (released
 // after the kernels queued on this stream that use it).  Empty when unsplit.
 Tensor split_k_workspace(GemmArgs& g, at::ScalarType dt, const Tensor& like) {
   if (dt != at::kBFloat16) return Tensor();
-  const int splits = gemm_splitk_factor(g);
+  const int splits = gemm_plan(g).k_splits;
   if (splits <= 1) return Tensor();
   Tensor ws = at::empty({splits, (int64_t)g.M, (int64_t)g.N}, like.options().dtype(at::kFloat));
   g.k_splits = splits;
@@ -1544,6 +1541,48 @@ void py_column_sum_segments(std::vector<Tensor> xs, Tensor out, bool accumulate)
   reduce_parts(ptr<float>(part), nullptr, total, (int)cols, out.data_ptr(), nullptr, out_f32, accumulate, s);
 }
 
+// The launches of a deferred weight gradient: `base` with up to GemmArgs::kMaxSegs micro-batches of as / bs as the
+// K-segments of A / B each; the first one overwrites main_grad when !accumulate.  The bias gradient (optional, fp32
+// [N]) is folded in through `fold_to` when the plan of every launch allows it (`fold_ok`); returns whether it was.
+bool run_wgrad_segments(const char* name, const GemmArgs& base, const std::vector<Tensor>& as,
+                        const std::vector<Tensor>& bs, bool accumulate, at::ScalarType dt, const Tensor& main_grad,
+                        const std::optional<Tensor>& bias_grad, int64_t N, bool GemmPlan::*fold_ok,
+                        float* GemmArgs::*fold_to) {
+  const int total = (int)as.size();
+  auto args_for = [&](int first) {
+    const int n = std::min(GemmArgs::kMaxSegs, total - first);
+    GemmArgs g = base;
+    g.C = main_grad.data_ptr();
+    g.K = base.seg_k * n;
+    g.epi = (accumulate || first > 0) ? kEpiAccumF32 : kEpiStoreF32;
+    for (int i = 0; i < n; ++i) {
+      g.a_seg[i] = as[first + i].data_ptr();
+      g.b_seg[i] = bs[first + i].data_ptr();
+    }
+    g.A = g.a_seg[0]; g.B = g.b_seg[0];
+    return g;
+  };
+  bool fold = bias_grad && dt == at::kBFloat16;
+  if (fold) {
+    check_cuda(*bias_grad, "bias_grad");
+    MP_CHECK(bias_grad->scalar_type() == at::kFloat && bias_grad->numel() == N && bias_grad->is_contiguous(), name,
+             ": bias_grad must be a contiguous fp32 [N]");
+    for (int first = 0; first < total && fold; first += GemmArgs::kMaxSegs) fold = gemm_plan(args_for(first)).*fold_ok;
+  }
+  for (int first = 0; first < total; first += GemmArgs::kMaxSegs) {
+    GemmArgs g = args_for(first);
+    if (fold) g.*fold_to = bias_grad->data_ptr<float>();
+    Tensor ws = split_k_workspace(g, dt, main_grad);
+    Tensor cws;
+    if (g.colsum != nullptr && g.k_splits > 1) {  // per-split column sums, reduced after
+      cws = at::empty({(int64_t)g.k_splits, N}, main_grad.options());
+      g.colsum_ws = cws.data_ptr<float>();
+    }
+    gemm_run(dt, g, cur_stream(main_grad));
+  }
+  return fold;
+}
+
 // Deferred weight gradient over the micro-batches of a step:
 //   main_grad[N, K] += sum_i dy_i^T . x_i
 // as K-segmented GEMMs (up to GemmArgs::kMaxSegs micro-batches per launch),
@@ -1574,36 +1613,10 @@ bool py_linear_wgrad_segments(std::vector<Tensor> dys, std::vector<Tensor> xs, T
     MP_CHECK(row_stride(dys[i], "dy") == lda && row_stride(xs[i], "x") == ldb,
              "linear_wgrad_segments: every micro-batch needs the same row strides");
   at::hip::HIPGuardMasqueradingAsCUDA guard(main_grad.device());
-  const int total = (int)dys.size();
-  auto args_for = [&](int first) {
-    const int n = std::min(GemmArgs::kMaxSegs, total - first);
-    GemmArgs g;
-    g.C = main_grad.data_ptr();
-    g.lda = lda; g.ldb = ldb; g.ldc = K; g.M = (int)N; g.N = (int)K; g.K = (int)(T * n);
-    g.a_kc = false; g.b_kc = false; g.epi = (accumulate || first > 0) ? kEpiAccumF32 : kEpiStoreF32;
-    g.seg_k = (int)T;
-    for (int i = 0; i < n; ++i) {
-      g.a_seg[i] = dys[first + i].data_ptr();
-      g.b_seg[i] = xs[first + i].data_ptr();
-    }
-    g.A = g.a_seg[0]; g.B = g.b_seg[0];
-    return g;
-  };
-  bool fold = false;
-  if (bias_grad && dt == at::kBFloat16) {
-    check_cuda(*bias_grad, "bias_grad");
-    MP_CHECK(bias_grad->scalar_type() == at::kFloat && bias_grad->numel() == N && bias_grad->is_contiguous(),
-             "linear_wgrad_segments: bias_grad must be a contiguous fp32 [N]");
-    fold = true;
-    for (int first = 0; first < total && fold; first += GemmArgs::kMaxSegs) fold = gemm_rowsum_ok(args_for(first));
-  }
-  for (int first = 0; first < total; first += GemmArgs::kMaxSegs) {
-    GemmArgs g = args_for(first);
-    if (fold) g.rowsum = bias_grad->data_ptr<float>();
-    Tensor ws = split_k_workspace(g, dt, main_grad);
-    gemm_run(dt, g, cur_stream(main_grad));
-  }
-  return fold;
+  GemmArgs g;
+  g.lda = lda; g.ldb = ldb; g.ldc = K; g.M = (int)N; g.N = (int)K; g.a_kc = false; g.b_kc = false; g.seg_k = (int)T;
+  return run_wgrad_segments("linear_wgrad_segments", g, dys, xs, accumulate, dt, main_grad, bias_grad, N,
+                            &GemmPlan::rowsum_ok, &GemmArgs::rowsum);
 }
 
 // The same deferred weight gradient from the transposed inputs x_i^T [K, T]
@@ -1635,42 +1648,11 @@ bool py_linear_wgrad_xt_segments(std::vector<Tensor> dys, std::vector<Tensor> xt
     MP_CHECK(row_stride(dys[i], "dy") == ldb && row_stride(xts[i], "xt") == lda,
              "linear_wgrad_xt_segments: every micro-batch needs the same row strides");
   at::hip::HIPGuardMasqueradingAsCUDA guard(main_grad.device());
-  const int total = (int)dys.size();
-  auto args_for = [&](int first) {
-    const int n = std::min(GemmArgs::kMaxSegs, total - first);
-    GemmArgs g;
-    g.C = main_grad.data_ptr();
-    g.lda = lda; g.ldb = ldb; g.ldc = K; g.M = (int)K; g.N = (int)N; g.K = (int)(T * n);
-    g.a_kc = true; g.b_kc = false; g.trans_c = true;
-    g.epi = (accumulate || first > 0) ? kEpiAccumF32 : kEpiStoreF32;
-    g.seg_k = (int)T;
-    for (int i = 0; i < n; ++i) {
-      g.a_seg[i] = xts[first + i].data_ptr();
-      g.b_seg[i] = dys[first + i].data_ptr();
-    }
-    g.A = g.a_seg[0]; g.B = g.b_seg[0];
-    return g;
-  };
-  bool fold = false;
-  if (bias_grad) {
-    check_cuda(*bias_grad, "bias_grad");
-    MP_CHECK(bias_grad->scalar_type() == at::kFloat && bias_grad->numel() == N && bias_grad->is_contiguous(),
-             "linear_wgrad_xt_segments: bias_grad must be a contiguous fp32 [N]");
-    fold = true;
-    for (int first = 0; first < total && fold; first += GemmArgs::kMaxSegs) fold = gemm_colsum_ok(args_for(first));
-  }
-  for (int first = 0; first < total; first += GemmArgs::kMaxSegs) {
-    GemmArgs g = args_for(first);
-    if (fold) g.colsum = bias_grad->data_ptr<float>();
-    Tensor ws = split_k_workspace(g, at::kBFloat16, main_grad);
-    Tensor cws;
-    if (fold && g.k_splits > 1) {
-      cws = at::empty({(int64_t)g.k_splits, N}, main_grad.options());
-      g.colsum_ws = cws.data_ptr<float>();
-    }
-    gemm_bf16(g, cur_stream(main_grad));
-  }
-  return fold;
+  GemmArgs g;
+  g.lda = lda; g.ldb = ldb; g.ldc = K; g.M = (int)K; g.N = (int)N; g.a_kc = true; g.b_kc = false; g.trans_c = true;
+  g.seg_k = (int)T;
+  return run_wgrad_segments("linear_wgrad_xt_segments", g, xts, dys, accumulate, at::kBFloat16, main_grad, bias_grad,
+                            N, &GemmPlan::colsum_ok, &GemmArgs::colsum);
 }
 
 // Generic test entry: C[M,N] (fp32) = A . B with A given [M,K] (a_kc) or [K,M],
@@ -1693,6 +1675,23 @@ Tensor py_gemm_f32(Tensor a, Tensor b, bool a_kc, bool b_kc) {
   g.a_kc = a_kc; g.b_kc = b_kc; g.epi = kEpiStoreF32;
   gemm_run(dt, g, cur_stream(a));
   return c;
+}
+
+// gemm_plan of a bf16 GEMM given by scalars and flags (a flag: that operand or output is present): GemmPlan's
+// fields in their declaration order.
+py::tuple py_gemm_plan(int64_t M, int64_t N, int64_t K, bool a_kc, bool b_kc, int64_t epi, int64_t act, double p,
+                       bool bias, bool aux, bool res, bool at, bool trans_c, bool rowsum, bool colsum, bool bits,
+                       int64_t dact, int64_t seg_k, int64_t width, int64_t k_splits) {
+  static float present[1];  // never read or written: the plan looks at which pointers are set
+  const auto ptr_if = [](bool on) { return on ? present : nullptr; };
+  GemmArgs g;
+  g.M = (int)M; g.N = (int)N; g.K = (int)K; g.a_kc = a_kc; g.b_kc = b_kc; g.epi = (int)epi; g.act = (int)act;
+  g.p = (float)p; g.trans_c = trans_c; g.seg_k = (int)seg_k; g.width = (int)width; g.k_splits = (int)k_splits;
+  g.bias = ptr_if(bias); g.aux = ptr_if(aux); g.res = ptr_if(res); g.at = ptr_if(at); g.bits = ptr_if(bits);
+  g.rowsum = ptr_if(rowsum); g.colsum = ptr_if(colsum); g.dact_in = ptr_if(dact != kActNone); g.dact = (int)dact;
+  const GemmPlan pl = gemm_plan(g);
+  return py::make_tuple(pl.big, pl.k_splits, pl.width, pl.extra, pl.x, pl.side, pl.kernel, pl.by_rounds, pl.along_n,
+                        pl.per, pl.chunks, pl.rowsum_ok, pl.colsum_ok, pl.bits_ok);
 }
 
 // ------------------------------------------------------------------ attention
@@ -2199,8 +2198,8 @@ PYBIND11_MODULE(_C, m) {
   m.def("attention_long_set_fused_rng", &attention_long_set_fused_rng,
         "long-sequence attention: make the dropout keep words inside the forward kernel (true, default) or in a "
         "kernel of their own before it (false)");
-  m.def("gemm_supported", &py_gemm_supported);
-  m.def("gemm_f32_supported", &py_gemm_f32_supported);
+  m.def("gemm_supported", &gemm_supported);
+  m.def("gemm_f32_supported", &gemm_f32_supported);
   m.def("attention_set_fused_bwd", &attention_set_fused_bwd);
   m.def("gemm_set_rounds", &gemm_set_rounds,
         "multi-round GEMM grids whose last round is at most half full: 0 one launch, 1 (default) one launch per round "
@@ -2210,12 +2209,19 @@ PYBIND11_MODULE(_C, m) {
   m.def("linear_fwd", &py_linear_fwd, py::arg("x"), py::arg("w"), py::arg("bias"), py::arg("act"), py::arg("p"),
         py::arg("save_preact"), py::arg("res") = py::none(), py::arg("xt") = py::none(),
         py::arg("aux_grad") = false, py::arg("bits") = py::none());
+  m.def("gemm_plan", &py_gemm_plan, py::arg("M"), py::arg("N"), py::arg("K"), py::arg("a_kc") = true,
+        py::arg("b_kc") = true, py::arg("epi") = 0, py::arg("act") = 0, py::arg("p") = 0.0, py::arg("bias") = false,
+        py::arg("aux") = false, py::arg("res") = false, py::arg("at") = false, py::arg("trans_c") = false,
+        py::arg("rowsum") = false, py::arg("colsum") = false, py::arg("bits") = false, py::arg("dact") = 0,
+        py::arg("seg_k") = 0, py::arg("width") = 0, py::arg("k_splits") = 1,
+        "how the bf16 GEMM launches these arguments: (big, k_splits, width, extra, x, side, kernel, by_rounds, along_n, "
+        "per, chunks, rowsum_ok, colsum_ok, bits_ok), see GemmPlan");
   m.def("linear_bits_ok",
         [](int64_t M, int64_t N, int64_t K, int64_t act, double p) {
           GemmArgs g;
           g.M = (int)M; g.N = (int)N; g.K = (int)K; g.act = (int)act; g.p = (float)p;
           g.a_kc = true; g.b_kc = true; g.epi = kEpiStoreAct;
-          return gemm_supported(M, N, K) && gemm_bits_ok(g);
+          return gemm_supported(M, N, K) && gemm_plan(g).bits_ok;
         },
         py::arg("M"), py::arg("N"), py::arg("K"), py::arg("act"), py::arg("p"),
         "whether linear_fwd can also write the ReLU output's nonzero mask as bits (kActReluBits)");

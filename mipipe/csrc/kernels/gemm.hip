@@ -23,9 +23,9 @@
 // split into segments living in different buffers (deferred weight gradients).
 // Block ids are remapped so consecutive tiles of an 8-row group share an XCD's
 // L2 (T1, bijective form).  Grids that would leave CUs idle get a 256x128 block
-// (big_width) or, with a long K, split-K: 2-8 blocks per tile writing fp32
-// partials that one reduction adds (gemm_splitk_factor).  A 128x128
-// register-staged kernel serves small exact-multiple grids.
+// or, with a long K, split-K: 2-8 blocks per tile writing fp32 partials that
+// one reduction adds.  A 128x128 register-staged kernel serves small
+// exact-multiple grids.  Which of these a call gets is one table: gemm_plan.
 // Epilogues (all results leave through LDS as 16-byte row stores, staged_store):
 //   kEpiStoreBf16 -- + bias, activation (ReLU/GELU), dropout (Philox mask in
 //                    the "column-quad" layout shared with the elementwise
@@ -35,7 +35,6 @@
 //   kEpiAccumF32  -- C(fp32) += acc  (weight gradients straight into main_grad);
 //   kEpiStoreF32  -- fp32 store (first write of a step, split-K partials).
 #include <algorithm>
-#include <cstdlib>
 #include <stdexcept>
 #include <type_traits>
 
@@ -1385,36 +1384,124 @@ __global__ void __launch_bounds__(kThreads, 1) gemm256_kernel(GemmArgs g) {
 
 int big_tiles(const GemmArgs& g, int w) { return ((g.M + big::BM - 1) / big::BM) * ((g.N + w - 1) / w); }
 
-// The 256-row kernel handles every shape (edge tiles masked); the 128x128 one
-// only exact multiples of 128, where it is kept for grids too small to fill
-// the 256 CUs with 256x256 tiles.
-// Chunks of a per-round launch stay on it too: the last chunk of e.g.
-// GPT-2-XL's fc1 forward (18432 x 6400, 7 rounds + 2 tile rows) ran on the
-// 128x128 kernel at ~250 TF/s.
-bool use_big(const GemmArgs& g) {
+// ------------------------------------------------------------ the launch plan
+// How a GemmArgs is launched is decided once, by gemm_plan() below, in this order; every later rule reads the earlier
+// decisions, none is re-derived anywhere else.  The three knobs select between live paths (tests, A/B tools); nothing
+// here reads the environment.
+//
+// 1. big: the 256-row kernel handles every shape (edge tiles masked); the 128x128 one only exact multiples of 128,
+//    where it is kept for grids too small to fill the 256 CUs with 256x256 tiles (< 128 of them).  Segmented K, the
+//    A^T emission, a transposed output and the two bias-gradient folds exist on the 256-row kernel only.  Chunks of a
+//    per-round launch stay on it too: the last chunk of e.g. GPT-2-XL's fc1 forward (18432 x 6400, 7 rounds + 2 tile
+//    rows) ran on the 128x128 kernel at ~250 TF/s.
+// 2. k_splits, the factor the caller may ask for -- split-K for grids that leave CUs idle while K is long: the T =
+//    2048 LM-head dgrad (2048 x 4096 x 28928 = 128 256x256 tiles), GPT-2-XL's weight gradients (1600 x 1600 = 49
+//    tiles, 6400 x 1600 = 175, K = 4 x 8192).  s blocks per tile, each a contiguous share of the K-tiles, write fp32
+//    partials; one reduction adds them (+ the residual / into main_grad).  s minimises rounds(tiles * s) / s of the
+//    tile time (a round = 256 blocks, one per CU; a 256x256 tile at ~4.5 TFLOP/s per CU) plus the partials' HBM
+//    traffic, (2 s + 1) * 4 * M * N bytes at ~4 TB/s.  Plain bf16 output (no bias / activation / dropout / aux: those
+//    stay in the GEMM epilogue) or an fp32 weight gradient, on the 256-row kernel, K >= 8192, at least 16 K-tiles per
+//    split.  Knob splitk: 0 off, 1 this rule, n >= 2 forces n (still capped by the K-tiles).  The caller allocates ws
+//    (and colsum_ws) and sets g.k_splits; everything below is decided for the g.k_splits it is given.
+// 3. width of the 256-row kernel: the knob's 128 / 256, else g.width's, else 256 under split-K, else 128 when the
+//    grid of 256x256 tiles quantises badly onto the 256 CUs -- rounds of 256 tiles, a round of 256x128 tiles costing
+//    ~0.73 of a 256x256 round (measured, 2048 x 12288 x 4096).  E.g. T = 2048: 2048 x 4096 is 128 256x256 tiles,
+//    half the chip idle, or 256 256x128 tiles (1.2x faster, profiles/gemm_vs_hipblaslt.txt).
+// 4. the kernel variant.  extra: dropout and / or the pre-activation output, the staged-layout epilogue of the bf16
+//    store pass.  side, for the bf16 store pass without extra: the addend (res) for forward GEMMs (y = res + act(x
+//    W^T + b), both operands K-contiguous) and dgrads, the two activation-backward modes (dact_in: the ReLU bit mask,
+//    or a saved tensor) for dgrads (A K-contiguous, B not; no bias, no activation of their own, no A^T).  Any other
+//    side operand has no kernel: kernel = false, and gemm_bf16 throws.  x: the A^T emission of a forward GEMM --
+//    compiled into every forward variant but the GELU one with extra, which would spill its main loop's registers
+//    (scratch reloads inside the K loop; gemm_emit_ok) -- or the column-sum fold of the transposed weight gradient.
+//    (The compared-and-lost main loops and the 4-wave kernel are gone: see above gemm256_kernel.)
+// 5. per-round launches: grids of several rounds whose last round is at most half full are launched one round of
+//    tiles at a time: the LM head (4096 x 28928 x 4096, 1808 tiles = 7 rounds + 16 tiles) 812 -> 786 us, 2048 x 12288
+//    x 4096 (384 tiles) 176 -> 167 us (hipBLASLt's time).  Whole rounds (4096 x 12288: 768 tiles, 292 vs 296 us) and
+//    a last round over half full (2048 x 28928: 904 tiles, 407 vs 415 us) stay one launch
+//    (tools/gemm_rounds_probe.py, warm clocks, arms alternated).  Only unsplit 256-wide grids; the grid is cut along
+//    its longer tile dimension into at most 16 chunks of floor(256 / other) tiles, and never across a fold: the row
+//    slices of rowsum need every tile column of a tile row, the column slices of colsum every tile row of a tile
+//    column.  Short main loops (K < 4096: GPT-2-XL's K = 1600 GEMMs) go as ONE launch: a CU that finishes its tile
+//    starts the next round's while the others store, so the fixed per-tile prologue / epilogue overlaps across rounds
+//    (GPT-2-XL PP=1 64.7-64.8k -> 66.2-66.3k tok/s on one box; enc12, all K = 4096: unchanged).  Knob rounds: 0 one
+//    launch, 1 this rule, 2 per round at any K.
+// 6. what the caller may ask for.  rowsum_ok: the wgrad layout (A read as [K, M]), fp32 output, no split-K, and >= 16
+//    tile columns (one 16-row slice per block of a tile row).  colsum_ok: A K-contiguous and B not, fp32 output, and
+//    2 slices of <= 128 columns per block covering the width as launched, i.e. at the split factor of rule 2
+//    (split-K: per-split partials, reduced after).  bits_ok: the extra epilogue with ReLU and dropout on the 256-row
+//    kernel, unsplit, whole bytes of columns.
+struct GemmKnobs {
+  int width = 0;   // gemm_set_width: 0 rule 3, or 128 / 256
+  int rounds = 1;  // gemm_set_rounds: 0 one launch, 1 rule 5, 2 per round at any K
+  int splitk = 1;  // gemm_set_splitk: 0 off, 1 rule 2, n >= 2 forced n ways
+};
+GemmKnobs g_knobs;
+
+bool plan_big(const GemmArgs& g) {
   return g.round_chunk || g.seg_k > 0 || g.at != nullptr || g.trans_c || g.colsum != nullptr || g.rowsum != nullptr ||
          g.M % BM != 0 || g.N % BN != 0 || big_tiles(g, 256) >= 128;
 }
 
-// Block width of the 256-row kernel: 256, or 128 when the grid of 256x256
-// tiles quantises badly onto the 256 CUs -- rounds of 256 tiles, a round of
-// 256x128 tiles costing ~0.73 of a 256x256 round (measured, 2048 x 12288 x
-// 4096).  E.g. T = 2048: 2048 x 4096 is 128 256x256 tiles, half the chip
-// idle, or 256 256x128 tiles (1.2x faster, profiles/gemm_vs_hipblaslt.txt).
-// gemm_set_width(128 / 256) or MIPIPE_GEMM_W forces one (A/B, tests).
-int g_gemm_width = -1;  // -1: not read from the environment yet, 0: auto
-int g_gemm_rounds = -1;  // MIPIPE_GEMM_ROUNDS: 0 one launch, 1 per round at K >= 4096 (default), 2 per round; -1 unread
-
-int big_width(const GemmArgs& g) {
-  if (g_gemm_width < 0) {
-    const char* e = getenv("MIPIPE_GEMM_W");
-    g_gemm_width = e ? atoi(e) : 0;
+int plan_splits(const GemmArgs& g, bool big) {
+  if (g_knobs.splitk == 0) return 1;
+  const bool plain_bf16 = g.epi == kEpiStoreBf16 && g.act == kActNone && g.bias == nullptr && g.p <= 0.f &&
+                          g.aux == nullptr && g.dact_in == nullptr;
+  const bool f32_out = g.epi == kEpiAccumF32 || g.epi == kEpiStoreF32;
+  if (!(plain_bf16 || f32_out) || !big || g.K < 8192) return 1;
+  const int tiles = big_tiles(g, 256);
+  const int kt = g.K / BK;
+  if (g_knobs.splitk >= 2) return std::max(1, std::min(g_knobs.splitk, kt / 16));
+  const double t_tile = 2.0 * 256 * 256 * (double)g.K / 4.5e12;
+  const double mn = (double)g.M * g.N;
+  int best = 1;
+  double best_t = (double)((tiles + 255) / 256) * t_tile;
+  for (int sp = 2; sp <= 8 && kt / sp >= 16; ++sp) {
+    const double t = (double)((tiles * sp + 255) / 256) * t_tile / sp + (2.0 * sp + 1.0) * 4.0 * mn / 4.0e12;
+    if (t < 0.97 * best_t) {
+      best = sp;
+      best_t = t;
+    }
   }
-  if (g_gemm_width == 128 || g_gemm_width == 256) return g_gemm_width;
+  return best;
+}
+
+int plan_width(const GemmArgs& g, int splits) {
+  if (g_knobs.width == 128 || g_knobs.width == 256) return g_knobs.width;
   if (g.width == 128 || g.width == 256) return g.width;
-  if (g.k_splits > 1) return 256;
+  if (splits > 1) return 256;
   const int r256 = (big_tiles(g, 256) + 255) / 256, r128 = (big_tiles(g, 128) + 255) / 256;
   return 0.75 * r128 < 1.0 * r256 ? 128 : 256;
+}
+
+// Run-time values as template arguments: f gets them as std::integral_constant tags.
+template <typename F>
+void with_flag(bool on, F&& f) {
+  if (on) f(std::true_type{});
+  else f(std::false_type{});
+}
+
+// The first of V, Vs... equal to v; the last one also stands for every other value.
+template <int V, int... Vs, typename F>
+void with_int(int v, F&& f) {
+  if constexpr (sizeof...(Vs) == 0) f(std::integral_constant<int, V>{});
+  else if (v == V) f(std::integral_constant<int, V>{});
+  else with_int<Vs...>(v, std::forward<F>(f));
+}
+
+// The variants of gemm256_kernel that are compiled (rule 4): the launcher instantiates these and no others.
+template <bool A_KC, bool B_KC, int EPI, int ACT, bool EXTRA, int X, int SIDE>
+constexpr bool has_kernel() {
+  constexpr bool bf16 = EPI == kEpiStoreBf16;
+  if (EXTRA && !bf16) return false;
+  if (SIDE != big::kSideNone) {
+    if (!bf16 || EXTRA) return false;
+    if (A_KC && B_KC) return SIDE == big::kSideRes && X != big::kXColsum;
+    return A_KC && !B_KC && ACT == kActNone && X == 0;
+  }
+  if (X == big::kXEmit) return A_KC && B_KC && bf16 && !(ACT == kActGelu && EXTRA);
+  if (X == big::kXColsum) return A_KC && !B_KC && !bf16;
+  return true;
 }
 
 template <bool A_KC, bool B_KC, int EPI, int ACT, int W, bool EXTRA, int X = 0, int SIDE = big::kSideNone>
@@ -1431,79 +1518,32 @@ void launch_big(const GemmArgs& g, hipStream_t s) {
                      dim3(big::kThreads), smem, s, g);
 }
 
-template <bool A_KC, bool B_KC, int EPI, int ACT, bool EXTRA, int X = 0, int SIDE = big::kSideNone>
-void launch_big_width(const GemmArgs& g, hipStream_t s) {
-  if (big_width(g) == 128) launch_big<A_KC, B_KC, EPI, ACT, 128, EXTRA, X, SIDE>(g, s);
-  else launch_big<A_KC, B_KC, EPI, ACT, 256, EXTRA, X, SIDE>(g, s);
-}
-
-// One kernel, 256 or 128 wide, plus its two main-loop extras (the compared-
-// and-lost loops and the 4-wave kernel are gone: see above gemm256_kernel)
-// and, for the bf16 store pass without dropout / aux, its side-operand mode
-// (big::kSide*).  The modes are compiled for the layouts that use them: the
-// addend for forward GEMMs (y = res + act(x W^T + b)) and dgrads, the two
-// activation-backward modes for dgrads (no bias, no activation of their own).
-template <bool A_KC, bool B_KC, int EPI, int ACT, bool EXTRA>
-void launch_big_w(const GemmArgs& g, hipStream_t s) {
-  if constexpr (EPI == kEpiStoreBf16 && !EXTRA) {
-    const int side = g.dact_in != nullptr ? (g.dact == kActReluBits ? big::kSideBits : big::kSideSaved)
-                                          : (g.res != nullptr ? big::kSideRes : big::kSideNone);
-    if (side != big::kSideNone) {
-      if constexpr (A_KC && B_KC) {
-        if (side == big::kSideRes) {
-          if (g.at != nullptr) launch_big_width<A_KC, B_KC, EPI, ACT, EXTRA, big::kXEmit, big::kSideRes>(g, s);
-          else launch_big_width<A_KC, B_KC, EPI, ACT, EXTRA, 0, big::kSideRes>(g, s);
-          return;
-        }
-      }
-      if constexpr (A_KC && !B_KC && ACT == kActNone) {
-        if (g.at == nullptr && g.bias == nullptr) {
-          if (side == big::kSideRes) launch_big_width<A_KC, B_KC, EPI, ACT, EXTRA, 0, big::kSideRes>(g, s);
-          else if (side == big::kSideBits) launch_big_width<A_KC, B_KC, EPI, ACT, EXTRA, 0, big::kSideBits>(g, s);
-          else launch_big_width<A_KC, B_KC, EPI, ACT, EXTRA, 0, big::kSideSaved>(g, s);
-          return;
-        }
-      }
-      throw std::runtime_error("gemm_bf16: no kernel with this side operand (res / dact_in) for this operand layout");
-    }
-  }
-  if constexpr (A_KC && B_KC && EPI == kEpiStoreBf16 && !(ACT == kActGelu && EXTRA)) {
-    if (g.at != nullptr) {  // forward GEMM that also writes A^T (gemm_emit_ok)
-      launch_big_width<A_KC, B_KC, EPI, ACT, EXTRA, big::kXEmit>(g, s);
-      return;
-    }
-  }
-  if constexpr (A_KC && !B_KC && EPI != kEpiStoreBf16 && !EXTRA) {
-    if (g.colsum != nullptr) {  // transposed weight gradient with the bias fold
-      launch_big_width<A_KC, B_KC, EPI, ACT, EXTRA, big::kXColsum>(g, s);
-      return;
-    }
-  }
-  launch_big_width<A_KC, B_KC, EPI, ACT, EXTRA>(g, s);
-}
-
-int g_gemm_group = -1;  // MIPIPE_GEMM_G: tile-rows per ordering group (A/B); -1 unread, 0 default
-
+// One launch of g, or of one of its per-round chunks, as the plan says.
 template <bool A_KC, bool B_KC, int EPI, int ACT>
-void launch(const GemmArgs& gi, hipStream_t s) {
-  if (g_gemm_group < 0) {
-    const char* e = getenv("MIPIPE_GEMM_G");
-    g_gemm_group = e ? atoi(e) : 0;
-  }
-  GemmArgs g = gi;
-  if (g_gemm_group > 0) g.group_m = g_gemm_group;
-  if (use_big(g)) {
-    if constexpr (EPI == kEpiStoreBf16) {
-      if (g.p > 0.f || g.aux != nullptr) {
-        launch_big_w<A_KC, B_KC, EPI, ACT, true>(g, s);
-        return;
-      }
-    }
-    launch_big_w<A_KC, B_KC, EPI, ACT, false>(g, s);
+void launch_one(const GemmPlan& p, const GemmArgs& g, hipStream_t s) {
+  if (!p.big) {
+    const int blocks = (g.M / BM) * (g.N / BN);
+    hipLaunchKernelGGL((gemm_kernel<A_KC, B_KC, EPI, ACT>), dim3(blocks), dim3(kThreads), kSmemBytes, s, g);
     return;
   }
-  const int blocks = (g.M / BM) * (g.N / BN);
-  hipLaunchKernelGGL((gemm_kernel<A_KC, B_KC, EPI, ACT>), dim3(blocks), dim3(kThreads), kSmemBytes, s, g);
+  const auto no_kernel = [] {
+    throw std::runtime_error("gemm_bf16: no kernel with this side operand (res / dact_in) for this operand layout");
+  };
+  if (!p.kernel) no_kernel();
+  // of the chunks of a grid cut along N only the first emits A^T (every chunk holds the whole A)
+  const int x = p.x == big::kXEmit && g.at == nullptr ? 0 : p.x;
+  with_flag(p.extra, [&](auto extra) {
+    with_int<big::kXEmit, big::kXColsum, 0>(x, [&](auto xm) {
+      with_int<big::kSideRes, big::kSideBits, big::kSideSaved, big::kSideNone>(p.side, [&](auto side) {
+        with_int<128, 256>(p.width, [&](auto w) {
+          constexpr bool EXTRA = decltype(extra)::value;
+          constexpr int X = decltype(xm)::value, SIDE = decltype(side)::value, W = decltype(w)::value;
+          if constexpr (has_kernel<A_KC, B_KC, EPI, ACT, EXTRA, X, SIDE>()) launch_big<A_KC, B_KC, EPI, ACT, W, EXTRA, X, SIDE>(g, s);
+          else no_kernel();
+        });
+      });
+    });
+  });
 }
 
 // C[M, N] (bf16, row stride ldc) = sum of the k_splits fp32 partials [s][M][N]
@@ -1578,45 +1618,76 @@ __global__ void __launch_bounds__(256) colsum_splits_kernel(const float* __restr
   colsum[n] += v;
 }
 
-int g_gemm_splitk = -1;  // MIPIPE_GEMM_SPLITK: 0 off, 1 auto (default), n >= 2 forced n ways (A/B); -1 unread
+const char* byte_off(const void* p, int64_t bytes) {
+  return p == nullptr ? nullptr : reinterpret_cast<const char*>(p) + bytes;
+}
 
-template <bool A_KC, bool B_KC, int EPI>
-void launch_act(const GemmArgs& g, hipStream_t s) {
-  switch (g.act) {
-    case kActRelu: launch<A_KC, B_KC, EPI, kActRelu>(g, s); break;
-    case kActGelu: launch<A_KC, B_KC, EPI, kActGelu>(g, s); break;
-    default: launch<A_KC, B_KC, EPI, kActNone>(g, s); break;
+// One chunk of a per-round launch of g (rule 5): p.per tiles of the cut dimension, every operand and output moved to
+// the chunk's corner of the full matrices.
+GemmArgs round_chunk(const GemmArgs& g, const GemmPlan& p, int chunk) {
+  const int t0 = chunk * p.per;
+  const int cbytes = g.epi == kEpiStoreBf16 ? 2 : 4;
+  GemmArgs c = g;
+  c.round_chunk = true;
+  c.width = 256;  // the full grid's width: the rowsum fold's slices assume its tile-column count
+  const int lo = t0 * 256, hi = std::min((t0 + p.per) * 256, p.along_n ? g.N : g.M);
+  c.mask_ld = g.mask_ld > 0 ? g.mask_ld : g.N;
+  if (p.along_n) {
+    c.N = hi - lo;
+    c.mask_col0 = g.mask_col0 + lo;
+    const int64_t boff = (g.b_kc ? (int64_t)lo * g.ldb : (int64_t)lo) * 2;
+    c.B = byte_off(g.B, boff);
+    for (int i = 0; i < GemmArgs::kMaxSegs; ++i) c.b_seg[i] = byte_off(g.b_seg[i], boff);
+    c.C = const_cast<char*>(byte_off(g.C, (g.trans_c ? (int64_t)lo * g.ldc : (int64_t)lo) * cbytes));
+    if (g.colsum != nullptr) c.colsum = g.colsum + lo;
+    if (t0 > 0) c.at = nullptr;  // every chunk holds the whole A: the first one emits A^T
+    c.bias = byte_off(g.bias, (int64_t)lo * 2);
+    c.aux = const_cast<char*>(byte_off(g.aux, (int64_t)lo * 2));
+    c.res = byte_off(g.res, (int64_t)lo * 2);
+    c.dact_in = byte_off(g.dact_in, g.dact == kActReluBits ? (int64_t)lo / 8 : (int64_t)lo * 2);
+    c.bits = const_cast<char*>(byte_off(g.bits, (int64_t)lo / 8));
+  } else {
+    c.M = hi - lo;
+    c.mask_row0 = g.mask_row0 + lo;
+    if (g.rowsum != nullptr) c.rowsum = g.rowsum + lo;
+    const int64_t aoff = (g.a_kc ? (int64_t)lo * g.lda : (int64_t)lo) * 2;
+    c.A = byte_off(g.A, aoff);
+    for (int i = 0; i < GemmArgs::kMaxSegs; ++i) c.a_seg[i] = byte_off(g.a_seg[i], aoff);
+    c.C = const_cast<char*>(byte_off(g.C, (g.trans_c ? (int64_t)lo : (int64_t)lo * g.ldc) * cbytes));
+    c.at = const_cast<char*>(byte_off(g.at, (int64_t)lo * 2));  // A^T columns of this chunk's rows
+    c.aux = const_cast<char*>(byte_off(g.aux, (int64_t)lo * g.ldc * 2));
+    c.res = byte_off(g.res, (int64_t)lo * g.ldr * 2);
+    c.dact_in = byte_off(g.dact_in, (int64_t)lo * g.ldd * (g.dact == kActReluBits ? 1 : 2));
+    c.bits = const_cast<char*>(byte_off(g.bits, (int64_t)lo * g.ldbits));
   }
+  return c;
+}
+
+// Every launch of g the plan asks for: one, or one per chunk.  Only the bf16 store pass has an activation.
+void launch_planned(const GemmArgs& g, hipStream_t s) {
+  const GemmPlan p = gemm_plan(g);
+  with_layout(g.a_kc, g.b_kc, [&](auto a_kc, auto b_kc) {
+    with_int<kEpiStoreBf16, kEpiAccumF32, kEpiStoreF32>(g.epi, [&](auto epi) {
+      constexpr int EPI = decltype(epi)::value;
+      with_int<kActRelu, kActGelu, kActNone>(EPI == kEpiStoreBf16 ? g.act : kActNone, [&](auto act) {
+        constexpr int ACT = decltype(act)::value;
+        if constexpr (EPI == kEpiStoreBf16 || ACT == kActNone) {
+          constexpr bool A_KC = decltype(a_kc)::value, B_KC = decltype(b_kc)::value;
+          if (!p.by_rounds) launch_one<A_KC, B_KC, EPI, ACT>(p, g, s);
+          for (int i = 0; p.by_rounds && i < p.chunks; ++i) launch_one<A_KC, B_KC, EPI, ACT>(p, round_chunk(g, p, i), s);
+        }
+      });
+    });
+  });
 }
 
 }  // namespace
 
-void gemm_set_width(int w) { g_gemm_width = w; }
-void gemm_set_rounds(int on) { g_gemm_rounds = on; }
-void gemm_set_splitk(int n) { g_gemm_splitk = n; }
-
-bool gemm_rowsum_ok(const GemmArgs& g) {
-  return !g.a_kc && (g.epi == kEpiAccumF32 || g.epi == kEpiStoreF32) && use_big(g) && gemm_splitk_factor(g) <= 1 &&
-         (g.N + big_width(g) - 1) / big_width(g) >= 16;
-}
-
-// The A^T emission is compiled into every forward variant but the GELU one
-// with an extra epilogue (dropout / pre-activation output): that one would
-// spill its main loop's registers (scratch reloads inside the K loop).
-bool gemm_bits_ok(const GemmArgs& g) {
-  // the staged EXTRA epilogue of the 256-row kernel (dropout), one launch or per-round chunks of whole tiles
-  return g.epi == kEpiStoreBf16 && g.act == kActRelu && g.p > 0.f && g.k_splits <= 1 && g.N % 8 == 0 && use_big(g);
-}
+void gemm_set_width(int w) { g_knobs.width = w; }
+void gemm_set_rounds(int on) { g_knobs.rounds = on; }
+void gemm_set_splitk(int n) { g_knobs.splitk = n; }
 
 bool gemm_emit_ok(int act, float p, bool aux) { return !(act == kActGelu && (p > 0.f || aux)); }
-
-bool gemm_colsum_ok(const GemmArgs& g) {
-  if (g.b_kc || !g.a_kc || !(g.epi == kEpiAccumF32 || g.epi == kEpiStoreF32)) return false;
-  GemmArgs b = g;
-  b.k_splits = gemm_splitk_factor(g);  // as launched (split-K: per-split partials, reduced after)
-  const int w = big_width(b);
-  return 2 * ((g.M + big::BM - 1) / big::BM) * 128 >= w;  // 2 slices of <= 128 columns per block
-}
 
 bool gemm_supported(int64_t M, int64_t N, int64_t K) {
   // 16-byte operand chunks along M/N (I-contiguous layouts) and whole 64-deep K tiles.
@@ -1625,115 +1696,46 @@ bool gemm_supported(int64_t M, int64_t N, int64_t K) {
          N < (1LL << 30) && M * K < (1LL << 31) && N * K < (1LL << 31);
 }
 
-// Split-K for grids that leave CUs idle while K is long: the T = 2048 LM-head
-// dgrad (2048 x 4096 x 28928 = 128 256x256 tiles), GPT-2-XL's weight
-// gradients (1600 x 1600 = 49 tiles, 6400 x 1600 = 175, K = 4 x 8192).
-// s blocks per tile, each a contiguous share of the K-tiles, write fp32
-// partials; one reduction adds them (+ the residual / into main_grad).  s
-// minimises rounds(tiles * s) / s of the tile time (a round = 256 blocks, one
-// per CU; a 256x256 tile at ~4.5 TFLOP/s per CU) plus the partials' HBM
-// traffic, (2 s + 1) * 4 * M * N bytes at ~4 TB/s.  Plain bf16 output (no
-// bias / activation / dropout / aux: those stay in the GEMM epilogue) or an
-// fp32 weight gradient.
-int gemm_splitk_factor(const GemmArgs& g) {
-  if (g_gemm_splitk < 0) {
-    const char* e = getenv("MIPIPE_GEMM_SPLITK");
-    g_gemm_splitk = e ? atoi(e) : 1;
-  }
-  if (g_gemm_splitk == 0) return 1;
-  const bool plain_bf16 = g.epi == kEpiStoreBf16 && g.act == kActNone && g.bias == nullptr && g.p <= 0.f &&
-                          g.aux == nullptr && g.dact_in == nullptr;
-  const bool f32_out = g.epi == kEpiAccumF32 || g.epi == kEpiStoreF32;
-  if (!(plain_bf16 || f32_out) || !use_big(g) || g.K < 8192) return 1;
-  const int tiles = big_tiles(g, 256);
-  const int kt = g.K / BK;
-  if (g_gemm_splitk >= 2) return std::max(1, std::min(g_gemm_splitk, kt / 16));  // forced (gemm_set_splitk, A/B)
-  const double t_tile = 2.0 * 256 * 256 * (double)g.K / 4.5e12;
-  const double mn = (double)g.M * g.N;
-  int best = 1;
-  double best_t = (double)((tiles + 255) / 256) * t_tile;
-  for (int sp = 2; sp <= 8 && kt / sp >= 16; ++sp) {
-    const double t = (double)((tiles * sp + 255) / 256) * t_tile / sp + (2.0 * sp + 1.0) * 4.0 * mn / 4.0e12;
-    if (t < 0.97 * best_t) {
-      best = sp;
-      best_t = t;
-    }
-  }
-  return best;
-}
-
-// Grids of several rounds whose last round is at most half full -- and whose
-// K is >= 4096 (below) -- are launched one round of tiles at a time: the LM head (4096 x 28928 x 4096, 1808 tiles =
-// 7 rounds + 16 tiles) 812 -> 786 us, 2048 x 12288 x 4096 (384 tiles) 176 ->
-// 167 us (hipBLASLt's time).  Whole rounds (4096 x 12288: 768 tiles, 292 vs
-// 296 us) and a last round over half full (2048 x 28928: 904 tiles, 407 vs
-// 415 us) stay one launch (tools/gemm_rounds_probe.py, warm clocks, arms
-// alternated).  The grid is cut along its longer tile dimension into chunks of
-// floor(256 / other) tiles.
-
-static const char* byte_off(const void* p, int64_t bytes) {
-  return p == nullptr ? nullptr : reinterpret_cast<const char*>(p) + bytes;
-}
-
-template <typename F>
-bool launch_by_rounds(const GemmArgs& g, F&& run) {
-  if (g_gemm_rounds < 0) {
-    const char* e = getenv("MIPIPE_GEMM_ROUNDS");
-    g_gemm_rounds = e ? atoi(e) : 1;
-  }
-  if (g_gemm_rounds == 0 || g.k_splits > 1 || !use_big(g) || big_width(g) != 256) return false;
-  // short main loops (K < 4096: GPT-2-XL's K = 1600 GEMMs) go as ONE launch: a CU
-  // that finishes its tile starts the next round's while the others store, so
-  // the fixed per-tile prologue / epilogue overlaps across rounds (GPT-2-XL PP=1
-  // 64.7-64.8k -> 66.2-66.3k tok/s on one box; enc12, all K = 4096: unchanged)
-  if (g_gemm_rounds == 1 && g.K < 4096) return false;
+// The rules, and the measurements behind them, are in the table above GemmKnobs.
+GemmPlan gemm_plan(const GemmArgs& g) {
+  const bool bf16 = g.epi == kEpiStoreBf16, f32_out = g.epi == kEpiAccumF32 || g.epi == kEpiStoreF32;
   const int tm = (g.M + 255) / 256, tn = (g.N + 255) / 256;
-  // only when the last round is at most half full (see above)
-  if (tm * tn <= 256 || (tm * tn) % 256 == 0 || (tm * tn) % 256 > 128) return false;
-  const bool along_n = tn >= tm;
-  if (along_n && g.rowsum != nullptr) return false;  // the row slices need every tile column of a tile row
-  if (!along_n && g.colsum != nullptr) return false;  // the column slices need every tile row of a tile column
-  const int other = along_n ? tm : tn, along = along_n ? tn : tm;
-  const int per = 256 / other;  // tiles of the split dimension per launch
-  if (per < 1 || (along + per - 1) / per > 16) return false;
-  const int cbytes = g.epi == kEpiStoreBf16 ? 2 : 4;
-  for (int t0 = 0; t0 < along; t0 += per) {
-    GemmArgs c = g;
-    c.round_chunk = true;
-    c.width = 256;  // the full grid's width: the rowsum fold's slices assume its tile-column count
-    const int lo = t0 * 256, hi = std::min((t0 + per) * 256, along_n ? g.N : g.M);
-    c.mask_ld = g.mask_ld > 0 ? g.mask_ld : g.N;
-    if (along_n) {
-      c.N = hi - lo;
-      c.mask_col0 = g.mask_col0 + lo;
-      const int64_t boff = (g.b_kc ? (int64_t)lo * g.ldb : (int64_t)lo) * 2;
-      c.B = byte_off(g.B, boff);
-      for (int i = 0; i < GemmArgs::kMaxSegs; ++i) c.b_seg[i] = byte_off(g.b_seg[i], boff);
-      c.C = const_cast<char*>(byte_off(g.C, (g.trans_c ? (int64_t)lo * g.ldc : (int64_t)lo) * cbytes));
-      if (g.colsum != nullptr) c.colsum = g.colsum + lo;
-      if (t0 > 0) c.at = nullptr;  // every chunk holds the whole A: the first one emits A^T
-      c.bias = byte_off(g.bias, (int64_t)lo * 2);
-      c.aux = const_cast<char*>(byte_off(g.aux, (int64_t)lo * 2));
-      c.res = byte_off(g.res, (int64_t)lo * 2);
-      c.dact_in = byte_off(g.dact_in, g.dact == kActReluBits ? (int64_t)lo / 8 : (int64_t)lo * 2);
-      c.bits = const_cast<char*>(byte_off(g.bits, (int64_t)lo / 8));
-    } else {
-      c.M = hi - lo;
-      c.mask_row0 = g.mask_row0 + lo;
-      if (g.rowsum != nullptr) c.rowsum = g.rowsum + lo;
-      const int64_t aoff = (g.a_kc ? (int64_t)lo * g.lda : (int64_t)lo) * 2;
-      c.A = byte_off(g.A, aoff);
-      for (int i = 0; i < GemmArgs::kMaxSegs; ++i) c.a_seg[i] = byte_off(g.a_seg[i], aoff);
-      c.C = const_cast<char*>(byte_off(g.C, (g.trans_c ? (int64_t)lo : (int64_t)lo * g.ldc) * cbytes));
-      c.at = const_cast<char*>(byte_off(g.at, (int64_t)lo * 2));  // A^T columns of this chunk's rows
-      c.aux = const_cast<char*>(byte_off(g.aux, (int64_t)lo * g.ldc * 2));
-      c.res = byte_off(g.res, (int64_t)lo * g.ldr * 2);
-      c.dact_in = byte_off(g.dact_in, (int64_t)lo * g.ldd * (g.dact == kActReluBits ? 1 : 2));
-      c.bits = const_cast<char*>(byte_off(g.bits, (int64_t)lo * g.ldbits));
+  GemmPlan p;
+  p.big = plan_big(g);                  // 1
+  p.k_splits = plan_splits(g, p.big);   // 2
+  p.width = plan_width(g, g.k_splits);  // 3
+  if (p.big) {                          // 4
+    p.extra = bf16 && (g.p > 0.f || g.aux != nullptr);
+    if (bf16 && !p.extra)
+      p.side = g.dact_in != nullptr ? (g.dact == kActReluBits ? big::kSideBits : big::kSideSaved)
+                                    : (g.res != nullptr ? big::kSideRes : big::kSideNone);
+    if (p.side != big::kSideNone) {
+      const bool fwd = g.a_kc && g.b_kc && p.side == big::kSideRes;
+      const bool dgrad = g.a_kc && !g.b_kc && g.act == kActNone && g.at == nullptr && g.bias == nullptr;
+      p.kernel = fwd || dgrad;
+      if (fwd && g.at != nullptr) p.x = big::kXEmit;
+    } else if (g.at != nullptr && g.a_kc && g.b_kc && bf16 && gemm_emit_ok(g.act, g.p, g.aux != nullptr)) {
+      p.x = big::kXEmit;
+    } else if (g.colsum != nullptr && g.a_kc && !g.b_kc && !bf16) {
+      p.x = big::kXColsum;
     }
-    run(c);
   }
-  return true;
+  const int last = (tm * tn) % 256;     // 5
+  if (g_knobs.rounds != 0 && g.k_splits <= 1 && p.big && p.width == 256 && !(g_knobs.rounds == 1 && g.K < 4096) &&
+      tm * tn > 256 && last != 0 && last <= 128) {
+    const bool along_n = tn >= tm;
+    const int per = 256 / (along_n ? tm : tn), chunks = per < 1 ? 0 : ((along_n ? tn : tm) + per - 1) / per;
+    if ((along_n ? g.rowsum : g.colsum) == nullptr && per >= 1 && chunks <= 16) {
+      p.by_rounds = true;
+      p.along_n = along_n;
+      p.per = per;
+      p.chunks = chunks;
+    }
+  }
+  p.rowsum_ok = !g.a_kc && f32_out && p.big && p.k_splits <= 1 && (g.N + p.width - 1) / p.width >= 16;  // 6
+  p.colsum_ok = g.a_kc && !g.b_kc && f32_out && 2 * tm * 128 >= plan_width(g, p.k_splits);
+  p.bits_ok = bf16 && g.act == kActRelu && g.p > 0.f && g.k_splits <= 1 && g.N % 8 == 0 && p.big;
+  return p;
 }
 
 void gemm_bf16(const GemmArgs& gi, hipStream_t s) {
@@ -1741,55 +1743,33 @@ void gemm_bf16(const GemmArgs& gi, hipStream_t s) {
   g.threshold = dropout_threshold(g.p);
   if (g.ldr == 0) g.ldr = g.ldc;
   if (g.ldd == 0) g.ldd = g.ldc;
-  if (g.k_splits > 1) {
-    // fp32 partials into the caller's workspace, then one reduction (+ res)
-    GemmArgs p = g;
-    p.epi = kEpiStoreF32;
-    p.C = g.ws;
-    p.ldc = g.N;
-    p.res = nullptr;
-    p.trans_c = false;  // partials row-major; the reduction transposes
-    p.rowsum = nullptr;
-    p.colsum = g.colsum != nullptr ? g.colsum_ws : nullptr;  // per-split column sums [k_splits][N]
-    if (p.a_kc && p.b_kc) launch<true, true, kEpiStoreF32, kActNone>(p, s);
-    else if (p.a_kc && !p.b_kc) launch<true, false, kEpiStoreF32, kActNone>(p, s);
-    else if (!p.a_kc && !p.b_kc) launch<false, false, kEpiStoreF32, kActNone>(p, s);
-    else launch<false, true, kEpiStoreF32, kActNone>(p, s);
-    if (g.epi == kEpiStoreBf16) {
-      const int64_t chunks = (int64_t)g.M * (g.N / 8);
-      hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)((chunks + 255) / 256)), dim3(256), 0, s, g.ws,
-                         g.k_splits, g.M, g.N, g.ldc, reinterpret_cast<const bf16_t*>(g.res), g.ldr,
-                         reinterpret_cast<bf16_t*>(g.C));
-    } else {
-      const int64_t chunks = (int64_t)g.M * (g.N / 4);  // = (M / 4) * N items when transposed
-      hipLaunchKernelGGL(splitk_reduce_f32_kernel, dim3((unsigned)((chunks + 255) / 256)), dim3(256), 0, s, g.ws,
-                         g.k_splits, g.M, g.N, g.ldc, g.epi == kEpiAccumF32, g.trans_c,
-                         reinterpret_cast<float*>(g.C));
-      if (g.colsum != nullptr)
-        hipLaunchKernelGGL(colsum_splits_kernel, dim3((unsigned)((g.N + 255) / 256)), dim3(256), 0, s, g.colsum_ws,
-                           g.k_splits, g.N, g.colsum);
-    }
+  if (g.k_splits <= 1) {
+    launch_planned(g, s);
     return;
   }
-  auto dispatch = [s](const GemmArgs& g) {
-    if (g.epi == kEpiStoreBf16) {
-      if (g.a_kc && g.b_kc) launch_act<true, true, kEpiStoreBf16>(g, s);
-      else if (g.a_kc && !g.b_kc) launch_act<true, false, kEpiStoreBf16>(g, s);
-      else if (!g.a_kc && !g.b_kc) launch_act<false, false, kEpiStoreBf16>(g, s);
-      else launch_act<false, true, kEpiStoreBf16>(g, s);
-    } else if (g.epi == kEpiAccumF32) {
-      if (g.a_kc && g.b_kc) launch<true, true, kEpiAccumF32, kActNone>(g, s);
-      else if (g.a_kc && !g.b_kc) launch<true, false, kEpiAccumF32, kActNone>(g, s);
-      else if (!g.a_kc && !g.b_kc) launch<false, false, kEpiAccumF32, kActNone>(g, s);
-      else launch<false, true, kEpiAccumF32, kActNone>(g, s);
-    } else {
-      if (g.a_kc && g.b_kc) launch<true, true, kEpiStoreF32, kActNone>(g, s);
-      else if (g.a_kc && !g.b_kc) launch<true, false, kEpiStoreF32, kActNone>(g, s);
-      else if (!g.a_kc && !g.b_kc) launch<false, false, kEpiStoreF32, kActNone>(g, s);
-      else launch<false, true, kEpiStoreF32, kActNone>(g, s);
-    }
-  };
-  if (!launch_by_rounds(g, dispatch)) dispatch(g);
+  // fp32 partials into the caller's workspace, then one reduction (+ res)
+  GemmArgs p = g;
+  p.epi = kEpiStoreF32;
+  p.C = g.ws;
+  p.ldc = g.N;
+  p.res = nullptr;
+  p.trans_c = false;  // partials row-major; the reduction transposes
+  p.rowsum = nullptr;
+  p.colsum = g.colsum != nullptr ? g.colsum_ws : nullptr;  // per-split column sums [k_splits][N]
+  launch_planned(p, s);
+  if (g.epi == kEpiStoreBf16) {
+    const int64_t chunks = (int64_t)g.M * (g.N / 8);
+    hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)((chunks + 255) / 256)), dim3(256), 0, s, g.ws,
+                       g.k_splits, g.M, g.N, g.ldc, reinterpret_cast<const bf16_t*>(g.res), g.ldr,
+                       reinterpret_cast<bf16_t*>(g.C));
+  } else {
+    const int64_t chunks = (int64_t)g.M * (g.N / 4);  // = (M / 4) * N items when transposed
+    hipLaunchKernelGGL(splitk_reduce_f32_kernel, dim3((unsigned)((chunks + 255) / 256)), dim3(256), 0, s, g.ws,
+                       g.k_splits, g.M, g.N, g.ldc, g.epi == kEpiAccumF32, g.trans_c, reinterpret_cast<float*>(g.C));
+    if (g.colsum != nullptr)
+      hipLaunchKernelGGL(colsum_splits_kernel, dim3((unsigned)((g.N + 255) / 256)), dim3(256), 0, s, g.colsum_ws,
+                         g.k_splits, g.N, g.colsum);
+  }
 }
 
 }  // namespace mipipe

@@ -304,42 +304,16 @@ void launch_cfg(const GemmArgs& g, hipStream_t s) {
                      dim3(64 * WM * WN), 0, s, g);
 }
 
-// MIPIPE_GEMM_F32_CFG: 0 auto; 1: 128x128 (4 waves, 2x2 tiles each); 2: 64x128
-// (8 waves, 1 tile each); 3: 128x64 (8 waves); 4: 64x128 (4 waves, 1x2 tiles);
-// 5: 128x128 (8 waves, 1x2 tiles); 6: 128x128 (8 waves, 2x1); 7: 256x128 and
-// 8: 128x256 (8 waves, 2x2 tiles).
-int g_f32_cfg = -1;
-
-int f32_cfg() {
-  if (g_f32_cfg < 0) {
-    const char* e = getenv("MIPIPE_GEMM_F32_CFG");
-    g_f32_cfg = e ? atoi(e) : 0;
-  }
-  return g_f32_cfg;
-}
-
+// Three tiles: 128x128 (8 waves of 32x64) when it fills the machine as well as
+// the small ones (fewer operand bytes per FLOP), else the better-filling of
+// 64x128 and 128x64 (8 waves of 32x32).  profiles/gemm_f32_vs_hipblaslt.txt:
+// these were the best big tile and the best small ones of the eight tried.
 template <bool A_KC, bool B_KC, int EPI, int ACT>
 void launch(const GemmArgs& g, hipStream_t s) {
-  int c = f32_cfg();
-  if (c == 0) {
-    // the big tile when it fills the machine as well as the small ones (fewer
-    // operand bytes per FLOP), else the best-filling 64-row / 64-column tile
-    // (profiles/gemm_f32_vs_hipblaslt.txt: 128x128 with 8 waves of 32x64 is the
-    // best big tile; 64x128 / 128x64 with 8 waves of 32x32 the best small ones)
-    const double f5 = fill<4, 2, 1, 2>(g), f2 = fill<2, 4, 1, 1>(g), f3 = fill<4, 2, 1, 1>(g);
-    if (f5 >= 0.95 * f2 && f5 >= 0.95 * f3) c = 5;
-    else c = f2 >= f3 ? 2 : 3;
-  }
-  switch (c) {
-    case 2: launch_cfg<2, 4, 1, 1, A_KC, B_KC, EPI, ACT>(g, s); break;
-    case 3: launch_cfg<4, 2, 1, 1, A_KC, B_KC, EPI, ACT>(g, s); break;
-    case 4: launch_cfg<2, 2, 1, 2, A_KC, B_KC, EPI, ACT>(g, s); break;
-    case 5: launch_cfg<4, 2, 1, 2, A_KC, B_KC, EPI, ACT>(g, s); break;
-    case 6: launch_cfg<2, 4, 2, 1, A_KC, B_KC, EPI, ACT>(g, s); break;
-    case 7: launch_cfg<4, 2, 2, 2, A_KC, B_KC, EPI, ACT>(g, s); break;
-    case 8: launch_cfg<2, 4, 2, 2, A_KC, B_KC, EPI, ACT>(g, s); break;
-    default: launch_cfg<2, 2, 2, 2, A_KC, B_KC, EPI, ACT>(g, s); break;
-  }
+  const double f_big = fill<4, 2, 1, 2>(g), f_wide = fill<2, 4, 1, 1>(g), f_tall = fill<4, 2, 1, 1>(g);
+  if (f_big >= 0.95 * f_wide && f_big >= 0.95 * f_tall) launch_cfg<4, 2, 1, 2, A_KC, B_KC, EPI, ACT>(g, s);
+  else if (f_wide >= f_tall) launch_cfg<2, 4, 1, 1, A_KC, B_KC, EPI, ACT>(g, s);
+  else launch_cfg<4, 2, 1, 1, A_KC, B_KC, EPI, ACT>(g, s);
 }
 
 template <bool A_KC, bool B_KC, int EPI>
@@ -357,10 +331,9 @@ void launch_act(const GemmArgs& g, hipStream_t s) {
 
 template <int EPI>
 void launch_layout(const GemmArgs& g, hipStream_t s) {
-  if (g.a_kc && g.b_kc) launch_act<true, true, EPI>(g, s);
-  else if (g.a_kc && !g.b_kc) launch_act<true, false, EPI>(g, s);
-  else if (!g.a_kc && !g.b_kc) launch_act<false, false, EPI>(g, s);
-  else launch_act<false, true, EPI>(g, s);
+  with_layout(g.a_kc, g.b_kc, [&](auto a_kc, auto b_kc) {
+    launch_act<decltype(a_kc)::value, decltype(b_kc)::value, EPI>(g, s);
+  });
 }
 
 }  // namespace

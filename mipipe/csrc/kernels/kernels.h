@@ -8,6 +8,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 namespace mipipe {
 
 typedef uint16_t bf16_t;
@@ -281,8 +283,8 @@ struct GemmArgs {
   // position in the full output, so the dropout mask (Philox counter
   // (row >> 2) * mask_ld + col) is the full matrix's.  mask_ld = 0: N.
   int mask_row0 = 0, mask_col0 = 0, mask_ld = 0;
-  bool round_chunk = false;  // a launch_by_rounds chunk: stays on the 256-row kernel even when small
-  int width = 0;             // 256-row kernel block width forced by the caller (0: big_width's rule)
+  bool round_chunk = false;  // a chunk of a per-round launch: stays on the 256-row kernel even when small
+  int width = 0;             // 256-row kernel block width forced by the caller (0: gemm_plan's rule)
   // K-segmented operands (deferred weight gradients: one GEMM over the
   // micro-batches of a step without concatenating them).  seg_k > 0: K-rows
   // [s*seg_k, (s+1)*seg_k) of A / B live at a_seg[s] / b_seg[s] (leading
@@ -293,12 +295,12 @@ struct GemmArgs {
   // rowsum[m] += sum_k A[k][m], fp32.  The 256 rows of a tile row are split
   // into 16-row slices summed by the blocks tn = 0..15 of that tile row, each
   // over the whole K (one writer per row: deterministic).  Needs
-  // ceil(N / block width) >= 16 and k_splits == 1 (gemm_rowsum_ok).
+  // ceil(N / block width) >= 16 and k_splits == 1 (GemmPlan::rowsum_ok).
   float* rowsum = nullptr;
   // The same fold on the B side for the transposed weight-gradient GEMM
   // (C^T = X^T . dY, B = dY read as [K=T, N]): colsum[n] += sum_k B[k][n];
   // the W/16 16-column slices of a tile column are spread over its tile
-  // rows, 2 per block (gemm_colsum_ok: >= W/32 tile rows); with split-K
+  // rows, 2 per block (GemmPlan::colsum_ok: >= W/32 tile rows); with split-K
   // each split writes colsum_ws and one reduction adds them.
   float* colsum = nullptr;
   float* colsum_ws = nullptr;  // split-K: [k_splits][N] per-split column sums (the caller's workspace)
@@ -315,29 +317,48 @@ struct GemmArgs {
   void* at = nullptr;
   int64_t ldat = 0;
   // Forward ReLU + dropout (the EXTRA epilogue): also write the output's nonzero mask as bits (kActReluBits),
-  // [M][ldbits bytes]; gemm_bits_ok(g) says whether this launch can.
+  // [M][ldbits bytes]; GemmPlan::bits_ok says whether this launch can.
   void* bits = nullptr;
   int64_t ldbits = 0;
   const void* a_seg[kMaxSegs] = {};
   const void* b_seg[kMaxSegs] = {};
 };
 bool gemm_supported(int64_t M, int64_t N, int64_t K);
-// True if gemm_bf16 can fold g.rowsum into g (the wgrad layout, no split-K, >= 16 tile columns).
-bool gemm_rowsum_ok(const GemmArgs& g);
-// True if this forward GEMM (ReLU, dropout, the staged EXTRA epilogue) can write GemmArgs::bits.
-bool gemm_bits_ok(const GemmArgs& g);
 // True if the forward GEMM with this epilogue can write A^T (GemmArgs::at).
 bool gemm_emit_ok(int act, float p, bool aux);
-// True if gemm_bf16 can fold g.colsum into g (B I-contiguous, fp32 out, no split-K, >= W/16 tile rows).
-bool gemm_colsum_ok(const GemmArgs& g);
-// Split-K factor gemm_bf16 would use for g (1 = none); the caller provides
-// g.ws with k_splits * M * N floats when it is > 1.
-int gemm_splitk_factor(const GemmArgs& g);
+// How gemm_bf16 launches g, decided once and in one order (the rule table is in gemm.hip, above GemmKnobs).
+struct GemmPlan {
+  bool big = false;   // the 256-row kernel (else the 128x128 one)
+  int k_splits = 1;   // the split-K factor the caller may ask for (1 = none): it then provides g.ws with
+                      // k_splits * M * N floats (and colsum_ws) and sets g.k_splits
+  // the launch of g as given, its k_splits included
+  int width = 256;    // block width of the 256-row kernel: 128 or 256
+  bool extra = false;  // the staged epilogue: dropout and / or the pre-activation output
+  int x = 0;          // 0, 1: also writes A^T (GemmArgs::at), 2: folds GemmArgs::colsum
+  int side = 0;       // side operand of the bf16 store pass: 0 none, 1 res, 2 ReLU bit mask, 3 saved tensor
+  bool kernel = true;  // false: no kernel takes this side operand in this operand layout (gemm_bf16 throws)
+  bool by_rounds = false;  // one launch per round of tiles: `chunks` launches of `per` tile columns (along_n) or rows
+  bool along_n = false;
+  int per = 0, chunks = 0;
+  // what the caller may ask for
+  bool rowsum_ok = false;  // GemmArgs::rowsum can be folded (the wgrad layout, no split-K, >= 16 tile columns)
+  bool colsum_ok = false;  // GemmArgs::colsum can be folded (B I-contiguous, fp32 out, >= W/32 tile rows)
+  bool bits_ok = false;    // GemmArgs::bits can be written (forward ReLU + dropout, the staged epilogue)
+};
+GemmPlan gemm_plan(const GemmArgs& g);
+// The operand layout as template arguments: f(a_kc, b_kc) gets two std::bool_constant tags.
+template <typename F>
+void with_layout(bool a_kc, bool b_kc, F&& f) {
+  if (a_kc && b_kc) f(std::true_type{}, std::true_type{});
+  else if (a_kc) f(std::true_type{}, std::false_type{});
+  else if (b_kc) f(std::false_type{}, std::true_type{});
+  else f(std::false_type{}, std::false_type{});
+}
 // The 256-row GEMM has one main loop, the whole-tile ping-pong (gemm.hip, above gemm256_kernel, also
-// names what it was compared against); the switches below select between live paths.
+// names what it was compared against); the switches below select between live paths (tests, A/B tools).
 void gemm_set_width(int w);    // 256-row GEMM block width: 0 auto, 128, 256
 void gemm_set_rounds(int on);  // 1: multi-round grids launched one round at a time (default), 0: one launch
-void gemm_set_splitk(int n);  // split-K factor: 0 off, 1 auto (gemm_splitk_factor), n >= 2 forced (A/B tools)
+void gemm_set_splitk(int n);  // split-K factor: 0 off, 1 auto (GemmPlan::k_splits), n >= 2 forced (A/B tools)
 void gemm_bf16(const GemmArgs& g, hipStream_t s);
 // Grouped GEMMs over expert-sorted rows (gemm_grouped.hip): R rows in 128-row tiles, tile_expert [R / 128] the
 // expert of a tile (-1: the tile stores zeros), wptr [Ne] a device table of the experts' bf16 weight pointers.

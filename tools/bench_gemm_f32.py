@@ -4,7 +4,6 @@ kernel (gemm_f32.hip) vs hipBLASLt fp32 (torch.matmul), interleaved, one process
 
     python tools/bench_gemm_f32.py [T] > profiles/gemm_f32_vs_hipblaslt.txt
 """
-import os
 import statistics
 import sys
 
@@ -36,8 +35,7 @@ def timeit(fn, iters=20):
 def main(T=int(sys.argv[1]) if len(sys.argv) > 1 else 1024):
     E = 2048
     shapes = [("qkv", T, 3 * E, E), ("out", T, E, E), ("ffn", T, E, E), ("dec", T, 28928, E)]
-    cfg = os.environ.get("MIPIPE_GEMM_F32_CFG", "0 (auto)")
-    print(f"# fp32 GEMM, T={T}, MIPIPE_GEMM_F32_CFG={cfg}; TF/s = 2MNK / time; fp32 MFMA peak 157 TF/s")
+    print(f"# fp32 GEMM, T={T}; TF/s = 2MNK / time; fp32 MFMA peak 157 TF/s")
     print(f"{'case':12s} {'M':>6s} {'N':>6s} {'K':>6s} | {'mipipe ms':>9s} {'TF/s':>7s} | {'hipBLASLt ms':>12s} {'TF/s':>7s}")
     tot_m = tot_h = 0.0
     for name, M, N, K in shapes:
