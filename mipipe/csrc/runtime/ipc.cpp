@@ -59,6 +59,9 @@ struct DeviceGuard {
 };
 
 int64_t flag_bytes(int64_t nslots) { return nslots * kFlagStride; }
+// The ring allocation: the full flags, then one more line whose first word is the release counter (device mode's
+// `freed`).  In the receiver's device memory like the flags, so one IPC handle exports both.
+int64_t ring_bytes(int64_t nslots) { return flag_bytes(nslots) + kFlagStride; }
 
 // The full flag of a slot carries the LAP of the message in it (message s is lap s / nslots of slot s % nslots) as
 // one bit per lap parity; the consumer waits for its lap's bit (hipStreamWaitValueAnd).  The previous lap's value
@@ -88,9 +91,10 @@ struct Shared {
   std::atomic<uint32_t> pad1;
   std::atomic<uint64_t> sent;                // messages the sender has enqueued
   std::atomic<uint64_t> released;            // messages the receiver has released (enqueued)
-  // messages [0, freed) released and their releases EXECUTED: in device mode
-  // written by the receiver's GPU (hipStreamWriteValue64 through the
-  // registered mapping of this block), polled by the sender's host
+  // messages [0, freed) released and their releases EXECUTED.  Host mode: the
+  // counter itself.  Device mode: the receiver's GPU writes the counter in the
+  // ring allocation (hipStreamWriteValue64); this word is the sender's copy of
+  // the last value it read there
   alignas(64) std::atomic<uint64_t> freed;
   uint8_t pad2[56];
   hipIpcMemHandle_t ring;                    // receiver's full flags (device mode)
@@ -174,18 +178,14 @@ std::unique_ptr<Link> Link::create(const std::string& name, int device, int64_t 
     L->ring_ = reinterpret_cast<char*>(p) + header_size();
   } else {
     DeviceGuard g(device);
-    // the release counter lives in this (host) block: the receiver's GPU writes it, the sender's host reads it
-    check(hipHostRegister(p, header_size(), hipHostRegisterMapped), "hipHostRegister(shared block)");
-    L->registered_ = true;
-    void* dp = nullptr;
-    check(hipHostGetDevicePointer(&dp, p, 0), "hipHostGetDevicePointer(shared block)");
-    L->freed_dev_ = reinterpret_cast<uint64_t*>(static_cast<char*>(dp) + offsetof(Shared, freed));
     void* d = nullptr;
-    check(hipMalloc(&d, size_t(flag_bytes(nslots))), "hipMalloc(full flags)");
-    check(hipMemset(d, 0, size_t(flag_bytes(nslots))), "hipMemset(full flags)");
+    check(hipMalloc(&d, size_t(ring_bytes(nslots))), "hipMalloc(full flags)");
+    check(hipMemset(d, 0, size_t(ring_bytes(nslots))), "hipMemset(full flags)");
     check(hipDeviceSynchronize(), "hipDeviceSynchronize(ring)");
     L->ring_ = static_cast<char*>(d);
     L->owns_ring_ = true;
+    // the release counter: this GPU writes it, the sender reads it through its mapping of the ring
+    L->freed_dev_ = reinterpret_cast<uint64_t*>(L->ring_ + flag_bytes(nslots));
     check(hipIpcGetMemHandle(&sh->ring, d), "hipIpcGetMemHandle(full flags)");
     const int64_t spc = std::max<int64_t>(1, std::min<int64_t>(nslots, kChunkBytes / slot_bytes));
     const int64_t nch = (nslots + spc - 1) / spc;  // <= nslots <= kMaxChunks
@@ -252,6 +252,14 @@ std::unique_ptr<Link> Link::attach(const std::string& name, int device, int engi
     IPC_TRACE("attach %s: opening the ring handle", name.c_str());
     check(hipIpcOpenMemHandle(&d, sh->ring, hipIpcMemLazyEnablePeerAccess), "hipIpcOpenMemHandle(full flags)");
     L->ring_ = static_cast<char*>(d);
+    // the receiver's release counter, read with small copies into a pinned word on a stream of this link's own
+    // (never the compute stream: a poll must not queue behind the step's work)
+    L->freed_dev_ = reinterpret_cast<uint64_t*>(L->ring_ + flag_bytes(sh->nslots));
+    void* h = nullptr;
+    check(hipHostMalloc(&h, sizeof(uint64_t), hipHostMallocDefault), "hipHostMalloc(release counter)");
+    L->freed_host_ = static_cast<uint64_t*>(h);
+    *L->freed_host_ = 0;
+    check(hipStreamCreateWithFlags(&L->poll_stream_, hipStreamNonBlocking), "hipStreamCreate(release counter)");
     for (int c = 0; c < sh->nchunks; ++c) {
       void* q = nullptr;
       check(hipIpcOpenMemHandle(&q, sh->chunk[c], hipIpcMemLazyEnablePeerAccess), "hipIpcOpenMemHandle(slot chunk)");
@@ -296,6 +304,11 @@ Link::~Link() {
         throw std::runtime_error("undrained");
       }
       if (sender_) {
+        // a poll still in flight (it timed out behind a stuck queue) keeps its stream and landing word
+        if (poll_stream_ && hipStreamQuery(poll_stream_) != hipErrorNotReady) {
+          (void)hipStreamDestroy(poll_stream_);
+          if (freed_host_) (void)hipHostFree(freed_host_);
+        }
         if (ring_) (void)hipIpcCloseMemHandle(ring_);
         for (char* q : chunk_) (void)hipIpcCloseMemHandle(q);
         sh_->sender_detached.store(1, std::memory_order_release);
@@ -310,7 +323,6 @@ Link::~Link() {
           (void)hipFree(ring_);
           for (char* q : chunk_) (void)hipFree(q);
         }
-        if (registered_) (void)hipHostUnregister(sh_);
         IPC_TRACE("  ring %s", mapped ? "left mapped by the peer (not freed)" : "freed");
       }
       if (events_)
@@ -431,6 +443,43 @@ void Link::wait_counter(const char* what, const void* counter, uint64_t need, do
   }
 }
 
+void Link::wait_freed(uint64_t need, double timeout_s) {
+  if (host_mode()) {
+    wait_counter("a free slot", &sh_->freed, need, timeout_s);
+    return;
+  }
+  // Device mode: the counter is in the receiver's device memory.  It only grows, so the last value read (kept in
+  // the shared block, for describe() too) answers without a copy whenever it already covers `need`.
+  if (sh_->freed.load(std::memory_order_acquire) >= need) return;
+  DeviceGuard g(device_);
+  const auto deadline = std::chrono::steady_clock::now() + std::chrono::duration<double>(timeout_s);
+  auto give_up = [&](const char* why) {
+    std::ostringstream o;
+    o << "mipipe ipc: " << describe() << ": " << why << " waiting for a free slot (need " << need << ", have "
+      << sh_->freed.load() << ")";
+    throw std::runtime_error(o.str());
+  };
+  for (int spin = 0;; ++spin) {
+    check(hipMemcpyAsync(freed_host_, freed_dev_, sizeof(uint64_t), hipMemcpyDeviceToHost, poll_stream_),
+          "hipMemcpyAsync(release counter)");
+    for (;;) {
+      const hipError_t e = hipStreamQuery(poll_stream_);
+      if (e == hipSuccess) break;
+      if (e != hipErrorNotReady) check(e, "hipStreamQuery(release counter)");
+      if (sh_->aborted.load(std::memory_order_acquire)) give_up("the link was aborted while");
+      if (std::chrono::steady_clock::now() > deadline) give_up("timed out");
+      std::this_thread::sleep_for(std::chrono::microseconds(5));
+    }
+    const uint64_t have = *static_cast<volatile uint64_t*>(freed_host_);
+    // abort() never touches the counter's line, so the value is a message count
+    if (have > sh_->freed.load(std::memory_order_relaxed)) sh_->freed.store(have, std::memory_order_release);
+    if (have >= need) return;
+    if (sh_->aborted.load(std::memory_order_acquire)) give_up("the link was aborted while");
+    if (std::chrono::steady_clock::now() > deadline) give_up("timed out");
+    std::this_thread::sleep_for(std::chrono::microseconds(spin > 2000 ? 200 : 5));
+  }
+}
+
 void Link::dma(void* dst, const void* src, size_t bytes, hipStream_t s, const char* what) {
   // the copy engines only: hipMemcpyDeviceToDevice may pick a blit kernel (CUs
   // taken from compute, profiles/cu_hold_r5.txt); NoCU never does
@@ -458,8 +507,8 @@ uint64_t Link::send(const void* src, size_t bytes, hipStream_t producer, double 
   SlotCtl& c = sh_->slots[k];
   char* dst = slot(s);
   // the slot's previous message (s - n) released, and that release executed: a
-  // host poll of the shared counter, never a wait dispatched on the GPU
-  if (s >= uint64_t(n)) wait_counter("a free slot", &sh_->freed, s - uint64_t(n) + 1, timeout_s);
+  // host poll of the release counter, never a wait dispatched on the producer's stream
+  if (s >= uint64_t(n)) wait_freed(s - uint64_t(n) + 1, timeout_s);
   c.bytes = bytes;
   c.bytes_seq.store(s + 1, std::memory_order_release);
   if (host_mode()) {

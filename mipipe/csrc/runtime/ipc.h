@@ -10,8 +10,12 @@
 // Message s lands in slot k = s mod nslots:
 //
 //   sender host:   waits (host poll, never a GPU wait) until the receiver has
-//                  released message s - nslots: the shared block's `freed`
-//                  counter >= s - nslots + 1;
+//                  released message s - nslots: the link's release counter
+//                  >= s - nslots + 1.  The counter is one more line behind
+//                  the full flags, in the receiver's device memory; the sender
+//                  reads it through its mapping of the ring with an 8-byte
+//                  device-to-host copy on a stream of its own, only when a
+//                  send finds its slot not known to be free;
 //   sender stream: event-wait for the producer (a barrier packet); copy
 //                  src -> slot k; copy the lap tag of message s (lap
 //                  s / nslots; one of two constant 64 KiB lines in the
@@ -25,8 +29,7 @@
 //                  lap's bit) (in order with its own work: it only spins while
 //                  that stream has nothing else to run), read slot k in place
 //                  or copy it out, then hipStreamWriteValue64(freed = s + 1)
-//                  into the shared block -- host memory registered with the
-//                  receiver's GPU -- which the sender's host polls.
+//                  into the release counter, which the sender's host polls.
 //
 // The lap tag alternates between two bits (lap parity): the flag of slot k
 // holds lap q - 1's bit until lap q's copy lands, and lap q + 1 cannot be
@@ -122,6 +125,7 @@ class Link {
  private:
   Link() = default;
   void wait_counter(const char* what, const void* counter, uint64_t need, double timeout_s) const;
+  void wait_freed(uint64_t need, double timeout_s);
   char* slot(uint64_t seq) const;
   void dma(void* dst, const void* src, size_t bytes, hipStream_t s, const char* what);
 
@@ -136,8 +140,9 @@ class Link {
   std::vector<char*> chunk_;      // device: the receiver's slot allocations (each <= 1 GiB)
   bool owns_ring_ = false;
   char* tags_ = nullptr;          // sender: the two lap tags (device memory) the flag copies read
-  bool registered_ = false;       // receiver: the shm header is registered with its GPU
-  uint64_t* freed_dev_ = nullptr; // receiver: device address of the shared `freed` counter
+  uint64_t* freed_dev_ = nullptr; // device mode: the release counter, the line behind the full flags
+  uint64_t* freed_host_ = nullptr;  // sender: pinned word the polls of the release counter land in
+  hipStream_t poll_stream_ = nullptr;  // sender: the stream those polls run on
   bool nocu_refused_ = false;     // the runtime refused hipMemcpyDeviceToDeviceNoCU: plain kinds instead
   hipStream_t copy_stream_ = nullptr;
   hipEvent_t* events_ = nullptr;  // one per slot: sender after the flag copy, receiver after the release

@@ -12,12 +12,14 @@ handles with ``wait()``), built on the native :class:`mipipe._C.IpcLink`
   into the receiver's full flag -- with the ``sdma`` engines both are
   ``hipMemcpyDeviceToDeviceNoCU`` copies, so the link's copy stream runs on
   the DMA engines and dispatches no kernel at all; the slot being free is a
-  host-side check of a counter in the shared block (never a GPU-side wait);
+  host-side check of the link's release counter (never a wait on the
+  producer's stream);
 * the receiver's compute stream waits for the flag (``hipStreamWaitValue64``,
   in order with its own work) and reads the slot IN PLACE
   (:meth:`IpcChannels.recv_act_view`: the slot is the receive buffer, one
-  copy per message), then releases it by writing the shared release counter
-  (host memory registered with its GPU) on that same stream.
+  copy per message), then releases it by writing the link's release counter
+  (a word of its own device memory behind the flags, which the sender reads
+  through its mapping of the ring) on that same stream.
 
 Neither host waits for the other inside a step (a slot per message of the
 step): completion is stream-ordered end to end, as the reference's ``Wait``

@@ -229,8 +229,11 @@ def test_stage_overlap_on_one_gpu():
     x = torch.randn(8, 1024, device=DEV, requires_grad=True)
     out = {}
     try:
-        pipe(x)  # warm-up (streams, kernels)
+        # warm-up (streams, kernels) of BOTH directions: the first launch of a kernel loads its code object, which
+        # takes tens of milliseconds on some hosts -- as much as the margin of the backward bound below
+        pipe(x).sum().backward()
         torch.cuda.synchronize()
+        x.grad = None
         fwd = _timed(lambda: out.__setitem__("y", pipe(x)))
         bwd = _timed(lambda: out["y"].sum().backward())
     finally:

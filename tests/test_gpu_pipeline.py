@@ -7,9 +7,11 @@
   (LN / GEMM-epilogue / attention / embedding dropout): ``always`` and
   ``except_last`` gradients are BIT-IDENTICAL to ``never``, for the engine and
   for ``Pipe`` (``/root/reference/README.md:517-537``);
-* multi-GPU: ``Pipe`` over ``cuda:0..N-1`` (native peer copies over xGMI) and
-  the engine over RCCL (``nccl`` backend, one rank per GPU) against the
-  single-rank engine -- skipped on a one-GPU box (``multigpu``).
+* multi-GPU: an N-stage ``Pipe`` over ``cuda:0..N-1`` (native peer copies over
+  xGMI; with fewer GPUs the stages share them, still N partitions), and the
+  engine over RCCL (``nccl`` backend, one rank per GPU, which RCCL refuses on
+  a shared GPU) against the single-rank engine -- the latter skipped on a
+  one-GPU box (``multigpu``).
 """
 import copy
 import dataclasses
@@ -52,10 +54,12 @@ def _ngpu():
 
 # ------------------------------------------------------------------ Pipe on our kernels
 def _pipe_vs_sequential(devices, checkpoint, copy_streams=None, dropout=0.0, defer_wgrad=False):
-    cfg = _cfg(dropout=dropout)
+    n = len(devices)
+    cfg = _cfg(dropout=dropout, layers=max(2, (n - 1) // 2))  # 2 + 2 x layers blocks: at least one per device
     m, mb = 4, 2
     torch.manual_seed(0)
     blocks = build_lm_blocks(cfg, dtype=torch.bfloat16)
+    assert len(blocks) >= n
     ref_blocks = copy.deepcopy(blocks)
     # reference: one device, the whole mini-batch in one pass
     ref = torch.nn.Sequential(*ref_blocks).to(DEV).train()
@@ -69,13 +73,14 @@ def _pipe_vs_sequential(devices, checkpoint, copy_streams=None, dropout=0.0, def
     ref_opt.fold_grads()
 
     # pipe: blocks spread evenly over the devices
-    n = len(devices)
-    per = (len(blocks) + n - 1) // n
-    parts = [torch.nn.Sequential(*blocks[i * per:(i + 1) * per]).to(devices[i]) for i in range(n)
-             if blocks[i * per:(i + 1) * per]]
+    sizes = [len(blocks) // n + (i < len(blocks) % n) for i in range(n)]
+    starts = [sum(sizes[:i]) for i in range(n)]
+    parts = [torch.nn.Sequential(*blocks[s:s + k]).to(devices[i]) for i, (s, k) in enumerate(zip(starts, sizes))]
     model = torch.nn.Sequential(*parts).train()
     opt = FlatAdam(model.parameters(), lr=1e-3, defer_wgrad=defer_wgrad)
-    pipe = Pipe(model, chunks=m, checkpoint=checkpoint, copy_streams=copy_streams)
+    # stages that share a GPU (see _stage_devices) stay partitions of their own: one child each
+    balance = [1] * len(parts) if len(set(devices)) < len(devices) else None
+    pipe = Pipe(model, chunks=m, checkpoint=checkpoint, copy_streams=copy_streams, balance=balance)
     try:
         opt.zero_grad()
         out = pipe(x).local_value()
@@ -116,26 +121,30 @@ def test_pipe_lm_bf16_one_gpu(checkpoint):
     _pipe_vs_sequential([DEV], checkpoint)
 
 
-@pytest.mark.multigpu
+def _stage_devices(n):
+    """The devices of an n-stage Pipe: cuda:0..n-1, wrapped round-robin onto the GPUs present.  With n GPUs every
+    stage has its own; with fewer, the stages that share one remain separate partitions (stage streams, copy streams
+    and Copy / Wait at every boundary), so the n-stage schedule runs on any machine with a GPU."""
+    return [torch.device("cuda", d % _ngpu()) for d in range(n)]
+
+
 @pytest.mark.parametrize("ngpu", [2, 4])
 def test_pipe_deferred_wgrad_multi_gpu(ngpu):
     """Deferred weight gradients queued by several devices' autograd threads are
-    each launched on their own device at fold_grads."""
-    if _ngpu() < ngpu:
-        pytest.skip(f"needs {ngpu} GPUs")
-    _pipe_vs_sequential([torch.device("cuda", d) for d in range(ngpu)], "except_last", defer_wgrad=True)
+    each launched on their own device at fold_grads (stages beyond the GPUs
+    present share them: _stage_devices)."""
+    _pipe_vs_sequential(_stage_devices(ngpu), "except_last", defer_wgrad=True)
 
 
-@pytest.mark.multigpu
 @pytest.mark.parametrize("ngpu", [2, 4, 8])
 @pytest.mark.parametrize("checkpoint,copy_streams", [("never", None), ("except_last", None), ("always", 2),
                                                      ("except_last", 1)])
 def test_pipe_lm_bf16_multi_gpu(ngpu, checkpoint, copy_streams):
-    """Pipe over cuda:0..N-1 (peer copies over xGMI on copy streams) == nn.Sequential on one GPU."""
-    if _ngpu() < ngpu:
-        pytest.skip(f"needs {ngpu} GPUs")
-    pipe = _pipe_vs_sequential([torch.device("cuda", d) for d in range(ngpu)], checkpoint, copy_streams)
-    assert len(pipe.devices) == ngpu
+    """Pipe of N stages over cuda:0..N-1 (peer copies over xGMI on copy streams; stages beyond the GPUs present
+    share them: _stage_devices) == nn.Sequential on one GPU."""
+    devices = _stage_devices(ngpu)
+    pipe = _pipe_vs_sequential(devices, checkpoint, copy_streams)
+    assert len(pipe.devices) == ngpu and list(pipe.devices) == devices
 
 
 def test_pipe_copy_stream_pool():
