@@ -1949,6 +1949,77 @@ void py_attention_dsink(Tensor lse, Tensor delta, Tensor sinks, Tensor dsinks, b
                   (int)lse.size(1), (int)lse.size(2), accumulate, cur_stream(lse));
 }
 
+// Attention with separate QK and V head dims (attention_mla.hip): q, k [B, S, H, Dqk] and v [B, S, H, Dv], bf16,
+// each with strides of its own (check_bshd: unit stride on the last axis, the others keeping 16-byte alignment).
+AttnStrides bshd_strides(const Tensor& t) { return AttnStrides{t.stride(0), t.stride(1), t.stride(2)}; }
+
+void check_mla(const Tensor& t, const char* name, const Tensor& q, int64_t D) {
+  check_bshd(t, name);
+  MP_CHECK(t.scalar_type() == at::kBFloat16 && t.device() == q.device(), "attention_mla: ", name,
+           " must be bf16 on q's device");
+  MP_CHECK(t.size(0) == q.size(0) && t.size(1) == q.size(1) && t.size(2) == q.size(2) && t.size(3) == D,
+           "attention_mla: ", name, " must be [B, S, H, ", D, "] with q's B, S and H, got ", t.sizes());
+  MP_CHECK(t.stride(0) >= 0 && t.stride(1) >= 0 && t.stride(2) >= 0, "attention_mla: ", name, " has a negative stride");
+}
+
+void fill_mla(AttnMlaArgs& a, const Tensor& q, const Tensor& k, const Tensor& v, bool causal, double p, double scale) {
+  MP_CHECK(q.dim() == 4, "attention_mla: q must be [B, S, H, Dqk]");
+  check_mla(q, "q", q, q.size(3));
+  check_mla(k, "k", q, q.size(3));
+  MP_CHECK(v.dim() == 4, "attention_mla: v must be [B, S, H, Dv]");
+  check_mla(v, "v", q, v.size(3));
+  MP_CHECK(p >= 0.0 && p < 1.0, "attention_mla: bad dropout p");
+  a.q = q.data_ptr(); a.k = k.data_ptr(); a.v = v.data_ptr();
+  a.sq = bshd_strides(q); a.sk = bshd_strides(k); a.sv = bshd_strides(v);
+  a.B = (int)q.size(0); a.S = (int)q.size(1); a.H = (int)q.size(2); a.Dqk = (int)q.size(3); a.Dv = (int)v.size(3);
+  MP_CHECK(q.size(1) <= INT32_MAX && attention_dims_supported(a.S, a.Dqk, a.Dv), "attention_mla: unsupported S=",
+           q.size(1), " Dqk=", a.Dqk, " Dv=", a.Dv, " (S % 64 == 0, head dims (192, 128))");
+  a.scale = (float)scale; a.p = (float)p; a.causal = causal;
+}
+
+// Returns (o [B, S, H, Dv], lse [B, H, S], seed, offset); the Philox draw is py_attention_fwd's.
+std::tuple<Tensor, Tensor, int64_t, int64_t> py_attention_mla_fwd(Tensor q, Tensor k, Tensor v, bool causal, double p,
+                                                                  double scale) {
+  AttnMlaArgs a;
+  fill_mla(a, q, k, v, causal, p, scale);
+  at::hip::HIPGuardMasqueradingAsCUDA guard(q.device());
+  auto o = at::empty({a.B, a.S, a.H, a.Dv}, q.options());
+  auto lse = at::empty({a.B, a.H, a.S}, q.options().dtype(at::kFloat));
+  uint64_t seed = 0, offset = 0;
+  if (p > 0.0) std::tie(seed, offset) = philox_draw(q.device(), 4);
+  a.o = o.data_ptr(); a.so = bshd_strides(o);
+  a.lse = ptr<float>(lse);
+  a.seed = seed; a.offset = offset;
+  const char* why = attention_mla_fwd(a, cur_stream(q));
+  MP_CHECK(why == nullptr, "attention_mla: ", why);
+  return {o, lse, (int64_t)seed, (int64_t)offset};
+}
+
+void py_attention_mla_bwd(Tensor dout, Tensor q, Tensor k, Tensor v, Tensor o, Tensor lse, bool causal, double p,
+                          double scale, int64_t seed, int64_t offset, Tensor dq, Tensor dk, Tensor dv) {
+  AttnMlaArgs a;
+  fill_mla(a, q, k, v, causal, p, scale);
+  check_mla(o, "o", q, a.Dv);
+  check_mla(dout, "dout", q, a.Dv);
+  check_mla(dq, "dq", q, a.Dqk);
+  check_mla(dk, "dk", q, a.Dqk);
+  check_mla(dv, "dv", q, a.Dv);
+  MP_CHECK(lse.is_cuda() && lse.device() == q.device() && lse.scalar_type() == at::kFloat && lse.is_contiguous() &&
+               lse.dim() == 3 && lse.size(0) == a.B && lse.size(1) == a.H && lse.size(2) == a.S,
+           "attention_mla_bwd: lse must be the forward's contiguous fp32 [B, H, S]");
+  at::hip::HIPGuardMasqueradingAsCUDA guard(q.device());
+  auto delta = at::empty({a.B, a.H, a.S}, q.options().dtype(at::kFloat));
+  a.o = o.data_ptr(); a.so = bshd_strides(o);
+  a.dout = dout.data_ptr(); a.sdo = bshd_strides(dout);
+  a.dq = dq.data_ptr(); a.sdq = bshd_strides(dq);
+  a.dk = dk.data_ptr(); a.sdk = bshd_strides(dk);
+  a.dv = dv.data_ptr(); a.sdv = bshd_strides(dv);
+  a.lse = ptr<float>(lse); a.delta = ptr<float>(delta);
+  a.seed = (uint64_t)seed; a.offset = (uint64_t)offset;
+  const char* why = attention_mla_bwd(a, cur_stream(q));
+  MP_CHECK(why == nullptr, "attention_mla_bwd: ", why);
+}
+
 // ------------------------------------------------------------------ optimizer
 Tensor py_sumsq(Tensor g) {
   check_cuda(g, "g");
@@ -2194,6 +2265,14 @@ PYBIND11_MODULE(_C, m) {
         py::arg("sinks") = py::none(), py::arg("dsinks") = py::none(), py::arg("dsinks_accumulate") = false);
   m.def("attention_dsink", &py_attention_dsink, py::arg("lse"), py::arg("delta"), py::arg("sinks"), py::arg("dsinks"),
         py::arg("accumulate") = false);
+  m.def("attention_dims_supported", [](int64_t S, int64_t Dqk, int64_t Dv) {
+    return S <= INT32_MAX && attention_dims_supported((int)S, (int)Dqk, (int)Dv);
+  });
+  m.def("attention_mla_fwd", &py_attention_mla_fwd, py::arg("q"), py::arg("k"), py::arg("v"), py::arg("causal"),
+        py::arg("p"), py::arg("scale"));
+  m.def("attention_mla_bwd", &py_attention_mla_bwd, py::arg("dout"), py::arg("q"), py::arg("k"), py::arg("v"),
+        py::arg("o"), py::arg("lse"), py::arg("causal"), py::arg("p"), py::arg("scale"), py::arg("seed"),
+        py::arg("offset"), py::arg("dq"), py::arg("dk"), py::arg("dv"));
   m.def("attention_long_supported", [](int64_t S, int64_t D) { return attention_long_supported((int)S, (int)D); });
   m.def("attention_long_set_fused_rng", &attention_long_set_fused_rng,
         "long-sequence attention: make the dropout keep words inside the forward kernel (true, default) or in a "

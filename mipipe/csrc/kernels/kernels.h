@@ -514,6 +514,38 @@ void attention_long_bwd(const AttnArgs& a, hipStream_t s);
 void attention_f32_fwd(const AttnArgs& a, hipStream_t s);
 void attention_f32_bwd(const AttnArgs& a, hipStream_t s);
 
+// Attention with separate QK and V head dims (attention_mla.hip): bf16, q / k / dq / dk [B, S, H, Dqk] and v / o /
+// dout / dv [B, S, H, Dv], every operand with its own strides in elements (unit stride on the last axis, the
+// others non-negative multiples of 8, bases 16-byte aligned).  k and v hold q's H heads.
+struct AttnStrides {
+  int64_t batch = 0, token = 0, head = 0;
+};
+struct AttnMlaArgs {
+  const void* q = nullptr;
+  const void* k = nullptr;
+  const void* v = nullptr;
+  void* o = nullptr;
+  const void* dout = nullptr;
+  void* dq = nullptr;
+  void* dk = nullptr;
+  void* dv = nullptr;
+  float* lse = nullptr;    // [B, H, S], log-sum-exp of the scaled scores
+  float* delta = nullptr;  // [B, H, S], written by the backward
+  AttnStrides sq, sk, sv, so, sdo, sdq, sdk, sdv;
+  int B = 0, H = 0, S = 0, Dqk = 0, Dv = 0;
+  float scale = 1.f, p = 0.f;
+  uint32_t threshold = 0;  // set by the launchers from p
+  uint64_t seed = 0, offset = 0;
+  bool causal = false;
+};
+// S > 0, S % 64 == 0, (Dqk, Dv) == (192, 128).
+bool attention_dims_supported(int S, int Dqk, int Dv);
+// Why the arguments are outside the kernels' contract (sizes, strides, alignment), or nullptr.
+const char* attention_mla_invalid(const AttnMlaArgs& a, bool backward);
+// Both check with attention_mla_invalid first and launch nothing when it objects: its message, else nullptr.
+const char* attention_mla_fwd(const AttnMlaArgs& a, hipStream_t s);
+const char* attention_mla_bwd(const AttnMlaArgs& a, hipStream_t s);
+
 // ------------------------------------------------------------------ loss
 // t_offset: logits are vocabulary columns [t_offset, t_offset + V) (split decoder).
 template <typename T>

@@ -98,6 +98,13 @@ fixed-order reduction (the same bits on every run; it goes straight into the
 parameter's fp32 ``main_grad`` where there is one).  Every padded shape stays
 native, the non-causal key mask included (a padded key still underflows against
 a running max the sink can only raise), unless there is a cap as well.
+
+Separate QK and V head dims: :func:`attention` takes a ``v`` whose head dim
+differs from ``q``'s and ``k``'s.  bf16 with dims (192, 128) -- multi-head latent
+attention as DeepSeek-V2 / V3 train it -- runs csrc/kernels/attention_mla.hip at
+``S % 64 == 0``, and causal at any other length by end padding; every operand is
+read with its own strides.  None of the options above is native there, nor is
+fp32 or another dim pair: those run :func:`attention_reference`.
 """
 from __future__ import annotations
 
@@ -402,6 +409,36 @@ class _Attention(torch.autograd.Function):
         return dq, dk, dv, None, None, None, None, None, None, None, dsinks
 
 
+def _strided_ok(t: Tensor) -> bool:
+    """``t [B, S, H, D]`` is readable in place by attention_mla.hip: unit stride on D, the other strides
+    non-negative multiples of 8 elements, a 16-byte aligned base."""
+    return (t.stride(3) == 1 and all(s >= 0 and s % 8 == 0 for s in t.stride()[:3])
+            and t.data_ptr() % 16 == 0)
+
+
+class _AttentionDims(torch.autograd.Function):
+    """``q, k [B, S, H, Dqk]`` and ``v [B, S, H, Dv]`` with ``Dv != Dqk`` in, ``o [B, S, H, Dv]`` out
+    (attention_mla.hip).  Each operand keeps its own strides; the gradients are fresh contiguous buffers."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, causal, p, scale):  # type: ignore[override]
+        q, k, v = (t if _strided_ok(t) else t.contiguous() for t in (q, k, v))
+        o, lse, seed, offset = kernels_for(q).attention_mla_fwd(q, k, v, causal, p, scale)
+        ctx.save_for_backward(q, k, v, o, lse)
+        ctx.scalars = (causal, p, scale, seed, offset)
+        return o
+
+    @staticmethod
+    def backward(ctx, do):  # type: ignore[override]
+        q, k, v, o, lse = ctx.saved_tensors
+        causal, p, scale, seed, offset = ctx.scalars
+        if not _strided_ok(do):
+            do = do.contiguous()
+        dq, dk, dv = (torch.empty(t.shape, dtype=t.dtype, device=t.device) for t in (q, k, v))
+        kernels_for(do).attention_mla_bwd(do, q, k, v, o, lse, causal, p, scale, seed, offset, dq, dk, dv)
+        return dq, dk, dv, None, None, None
+
+
 _noted = set()
 
 
@@ -613,6 +650,35 @@ def attention_gqa_packed(qkv: Tensor, n_kv_heads: int, causal: bool = False, dro
     return _packed(qkv, n_kv, causal, p, scale, window, softcap, docs, sinks)
 
 
+def _attention_dims(q: Tensor, k: Tensor, v: Tensor, causal: bool, p: float, scale: float, window: Optional[int],
+                    softcap: Optional[float], docs: Optional[Tensor], sinks: Optional[Tensor]) -> Tensor:
+    """:func:`attention` where ``v``'s head dim differs from ``q``'s and ``k``'s (``[B, H, S, D]`` tensors with
+    equal head counts).  bf16 on the GPU with the dims attention_mla.hip tiles and no option runs its kernels, a
+    causal sequence off the 64-token tile zero-padded at the end (no real query sees a pad key); everything else
+    is :func:`attention_reference`, noted once per shape on the GPU."""
+    S, D, Dv = q.shape[2], q.shape[3], v.shape[3]
+    sp = None
+    if q.is_cuda and q.dtype == torch.bfloat16 and not _is_generic(window, softcap, docs, sinks):
+        supported = kernels_for(q).attention_dims_supported
+        sp = next((s for s in ((S,) if not causal else (S, -(-S // 64) * 64)) if supported(s, D, Dv)), None)
+    if sp is None:
+        if q.is_cuda:
+            key = (S, D, Dv, q.dtype, window is not None, softcap is not None, docs is not None, sinks is not None)
+            if key not in _noted:
+                _noted.add(key)
+                import warnings
+
+                warnings.warn(f"mipipe attention: S={S} with head dims ({D}, {Dv}) {q.dtype} runs the eager math "
+                              "path (HIP kernels for differing head dims: bf16, (192, 128), S % 64 == 0 or causal, "
+                              "no window, cap, document bounds or sinks)", stacklevel=3)
+        return attention_reference(q, k, v, causal, p, scale, window=window, softcap=softcap, doc_bounds=docs,
+                                   sinks=sinks)
+    if sp != S:
+        q, k, v = (F.pad(t, (0, 0, 0, sp - S)) for t in (q, k, v))
+    o = _AttentionDims.apply(q.transpose(1, 2), k.transpose(1, 2), v.transpose(1, 2), causal, p, scale)
+    return o.transpose(1, 2)[:, :, :S]
+
+
 def attention(
     q: Tensor, k: Tensor, v: Tensor, causal: bool = False, dropout_p: float = 0.0, training: bool = True,
     scale: Optional[float] = None, *, window: Optional[int] = None, softcap: Optional[float] = None,
@@ -621,7 +687,11 @@ def attention(
     """``q, k, v [B, H, S, D]`` -> ``[B, H, S, D]``.  ``k`` and ``v`` may have fewer heads, ``Hkv | H``
     (grouped-query attention): separate tensors do not share q's strides, so their heads are repeated
     (autograd sums each group's gradient).  ``window``: sliding-window attention, ``softcap``: logit
-    soft-capping, ``doc_bounds``: document masks, ``sinks``: attention sinks (module doc)."""
+    soft-capping, ``doc_bounds``: document masks, ``sinks``: attention sinks (module doc).  ``v`` may have a
+    head dim of its own, ``[B, H, S, Dv]`` -> ``[B, H, S, Dv]`` (multi-head latent attention's 192 / 128): see
+    :func:`_attention_dims`; the default ``scale`` stays ``1 / sqrt(D)`` of ``q``."""
+    if k.shape[-1] != q.shape[-1]:
+        raise ValueError(f"attention: k's head dim {k.shape[-1]} differs from q's {q.shape[-1]} (only v may differ)")
     if k.shape[1] != q.shape[1]:
         if k.shape[1] != v.shape[1] or k.shape[1] <= 0 or q.shape[1] % k.shape[1] != 0:
             raise ValueError(f"attention: {k.shape[1]} / {v.shape[1]} K/V heads do not divide {q.shape[1]} query heads")
@@ -635,6 +705,8 @@ def attention(
     softcap = _check_softcap(softcap)
     docs = _check_docs(doc_bounds, causal, B, S)
     sinks = _check_sinks(sinks, q.shape[1], q.dtype)
+    if v.shape[-1] != D:  # before the plan, which knows one head dim
+        return _attention_dims(q, k, v, causal, p, scale, window, softcap, docs, sinks)
     plan = _plan(q.dtype, S, D, causal, scale, generic=_is_generic(window, softcap, docs, sinks), softcap=softcap,
                  sinks=sinks is not None) if q.is_cuda else None
     if plan is None:
