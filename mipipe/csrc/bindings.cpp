@@ -492,6 +492,70 @@ Tensor py_rope_heads(Tensor x, Tensor cos, Tensor sin, std::optional<Tensor> out
   return rope_impl(x, cos, sin, out, n_rot, pos0, inverse, "rope_heads");
 }
 
+// Multi-head latent attention's decoupled RoPE (llama.hip's mla_rope): q [B, S, H, Dn + R] and the R columns that
+// follow the Lkv latent columns of a [B, S, Lkv + R] tensor, R = twice the tables' width.
+struct MlaRopeDims {
+  int64_t B, S, H, Dn, R, Lkv;
+};
+MlaRopeDims mla_rope_check(const Tensor& q, const Tensor& ckv, const Tensor& cos, const Tensor& sin, const char* name) {
+  check_cuda(q, "q");
+  check_cuda(ckv, "ckv");
+  check_cuda(cos, "cos");
+  check_cuda(sin, "sin");
+  check_same(q, ckv, "q", "ckv");
+  MP_CHECK(q.dim() == 4 && ckv.dim() == 3 && ckv.size(0) == q.size(0) && ckv.size(1) == q.size(1), name,
+           ": q must be [B, S, H, Dn + R] and ckv [B, S, Lkv + R]");
+  MP_CHECK(cos.dim() == 2, name, ": cos / sin must be fp32 [>= S, R / 2]");
+  MlaRopeDims d{q.size(0), q.size(1), q.size(2), q.size(3) - 2 * cos.size(1), 2 * cos.size(1),
+                ckv.size(2) - 2 * cos.size(1)};
+  MP_CHECK((d.R == 32 || d.R == 64) && d.Dn >= 0 && d.Dn % 8 == 0 && d.Lkv >= 0 && d.Lkv % 8 == 0 && d.H > 0, name,
+           ": needs R in {32, 64} and Dn, Lkv multiples of 8, got R=", d.R, " Dn=", d.Dn, " Lkv=", d.Lkv);
+  MP_CHECK(d.S <= INT32_MAX / 2 && d.H * (d.Dn + d.R) <= INT32_MAX / 8 && d.H < INT32_MAX / 64, name,
+           ": shape too large");
+  for (auto* t : {&cos, &sin}) {
+    MP_CHECK(t->scalar_type() == at::kFloat && t->dim() == 2 && t->size(1) == d.R / 2 && t->size(0) >= d.S &&
+                 t->device() == q.device(),
+             name, ": cos / sin must be fp32 [>= S, R / 2] on q's device");
+  }
+  return d;
+}
+
+// Returns (q with the rope slices rotated, k_rope [B, S, R]); out: q itself (in place) or None (a new tensor).
+std::tuple<Tensor, Tensor> py_mla_rope_fwd(Tensor q, Tensor ckv, Tensor cos, Tensor sin, std::optional<Tensor> out) {
+  const MlaRopeDims d = mla_rope_check(q, ckv, cos, sin, "mla_rope_fwd");
+  MP_CHECK(!out.has_value() || out->data_ptr() == q.data_ptr(), "mla_rope_fwd: out must be q itself or None");
+  at::hip::HIPGuardMasqueradingAsCUDA guard(q.device());
+  Tensor o = out.has_value() ? q : at::empty_like(q);
+  Tensor kr = at::empty({d.B, d.S, d.R}, q.options());
+  auto s = cur_stream(q);
+  dispatch_fb(q, "mla_rope_fwd", [&](auto* tag) {
+    using T = std::remove_pointer_t<decltype(tag)>;
+    mla_rope<T>(cptr<T>(q), ptr<T>(o), cptr<T>(ckv), d.Lkv + d.R, d.Lkv, ptr<T>(kr), d.R, 0, cptr<float>(cos),
+                cptr<float>(sin), d.B, (int)d.S, (int)d.H, (int)d.Dn, (int)d.R, false, s);
+  });
+  return {o, kr};
+}
+
+// The inverse rotation: dq's rope slices into out (dq itself: in place; None: a new tensor, which is returned)
+// and dk_rope [B, S, R] into the last R columns of dckv [B, S, Lkv + R]; dckv's first Lkv columns are not touched.
+Tensor py_mla_rope_bwd(Tensor dq, Tensor dk_rope, Tensor cos, Tensor sin, Tensor dckv, std::optional<Tensor> out) {
+  const MlaRopeDims d = mla_rope_check(dq, dckv, cos, sin, "mla_rope_bwd");
+  check_cuda(dk_rope, "dk_rope");
+  check_same(dq, dk_rope, "dq", "dk_rope");
+  MP_CHECK(dk_rope.dim() == 3 && dk_rope.size(0) == d.B && dk_rope.size(1) == d.S && dk_rope.size(2) == d.R,
+           "mla_rope_bwd: dk_rope must be [B, S, R]");
+  MP_CHECK(!out.has_value() || out->data_ptr() == dq.data_ptr(), "mla_rope_bwd: out must be dq itself or None");
+  at::hip::HIPGuardMasqueradingAsCUDA guard(dq.device());
+  Tensor o = out.has_value() ? dq : at::empty_like(dq);
+  auto s = cur_stream(dq);
+  dispatch_fb(dq, "mla_rope_bwd", [&](auto* tag) {
+    using T = std::remove_pointer_t<decltype(tag)>;
+    mla_rope<T>(cptr<T>(dq), ptr<T>(o), cptr<T>(dk_rope), d.R, 0, ptr<T>(dckv), d.Lkv + d.R, d.Lkv, cptr<float>(cos),
+                cptr<float>(sin), d.B, (int)d.S, (int)d.H, (int)d.Dn, (int)d.R, true, s);
+  });
+  return o;
+}
+
 // ------------------------------------------------------------------ QK-norm
 // The checks the forward and the backward share: x [B, S, heads, D] contiguous with the first n_q heads Q and the
 // next n_k heads K, both weights [D] of x's dtype, tables (both or neither) fp32 [>= pos0 + S, D / 2].
@@ -1962,10 +2026,21 @@ void check_mla(const Tensor& t, const char* name, const Tensor& q, int64_t D) {
   MP_CHECK(t.stride(0) >= 0 && t.stride(1) >= 0 && t.stride(2) >= 0, "attention_mla: ", name, " has a negative stride");
 }
 
-void fill_mla(AttnMlaArgs& a, const Tensor& q, const Tensor& k, const Tensor& v, bool causal, double p, double scale) {
+// k_rope / dk_rope [B, S, 64] of the shared-rope call: bf16 on q's device, unit stride on the last axis.
+void check_mla_rope(const Tensor& t, const char* name, const Tensor& q) {
+  MP_CHECK(t.is_cuda() && t.scalar_type() == at::kBFloat16 && t.device() == q.device(), "attention_mla: ", name,
+           " must be bf16 on q's device");
+  MP_CHECK(t.dim() == 3 && t.size(0) == q.size(0) && t.size(1) == q.size(1) && t.size(2) == 64 && t.stride(2) == 1,
+           "attention_mla: ", name, " must be [B, S, 64] with q's B and S and unit stride on the last axis, got ",
+           t.sizes());
+  MP_CHECK(t.stride(0) >= 0 && t.stride(1) >= 0, "attention_mla: ", name, " has a negative stride");
+}
+
+void fill_mla(AttnMlaArgs& a, const Tensor& q, const Tensor& k, const Tensor& v, const std::optional<Tensor>& k_rope,
+              bool causal, double p, double scale) {
   MP_CHECK(q.dim() == 4, "attention_mla: q must be [B, S, H, Dqk]");
   check_mla(q, "q", q, q.size(3));
-  check_mla(k, "k", q, q.size(3));
+  check_mla(k, "k", q, k_rope.has_value() ? q.size(3) - 64 : q.size(3));
   MP_CHECK(v.dim() == 4, "attention_mla: v must be [B, S, H, Dv]");
   check_mla(v, "v", q, v.size(3));
   MP_CHECK(p >= 0.0 && p < 1.0, "attention_mla: bad dropout p");
@@ -1974,14 +2049,20 @@ void fill_mla(AttnMlaArgs& a, const Tensor& q, const Tensor& k, const Tensor& v,
   a.B = (int)q.size(0); a.S = (int)q.size(1); a.H = (int)q.size(2); a.Dqk = (int)q.size(3); a.Dv = (int)v.size(3);
   MP_CHECK(q.size(1) <= INT32_MAX && attention_dims_supported(a.S, a.Dqk, a.Dv), "attention_mla: unsupported S=",
            q.size(1), " Dqk=", a.Dqk, " Dv=", a.Dv, " (S % 64 == 0, head dims (192, 128))");
+  if (k_rope.has_value()) {
+    check_mla_rope(*k_rope, "k_rope", q);
+    a.k_rope = k_rope->data_ptr();
+    a.sk_rope = AttnStrides{k_rope->stride(0), k_rope->stride(1), 0};
+  }
   a.scale = (float)scale; a.p = (float)p; a.causal = causal;
 }
 
-// Returns (o [B, S, H, Dv], lse [B, H, S], seed, offset); the Philox draw is py_attention_fwd's.
+// Returns (o [B, S, H, Dv], lse [B, H, S], seed, offset); the Philox draw is py_attention_fwd's.  k_rope [B, S, 64]:
+// k is the 128-wide nope part and every head's rotary key columns are that one head, read in place.
 std::tuple<Tensor, Tensor, int64_t, int64_t> py_attention_mla_fwd(Tensor q, Tensor k, Tensor v, bool causal, double p,
-                                                                  double scale) {
+                                                                  double scale, std::optional<Tensor> k_rope) {
   AttnMlaArgs a;
-  fill_mla(a, q, k, v, causal, p, scale);
+  fill_mla(a, q, k, v, k_rope, causal, p, scale);
   at::hip::HIPGuardMasqueradingAsCUDA guard(q.device());
   auto o = at::empty({a.B, a.S, a.H, a.Dv}, q.options());
   auto lse = at::empty({a.B, a.H, a.S}, q.options().dtype(at::kFloat));
@@ -1995,20 +2076,32 @@ std::tuple<Tensor, Tensor, int64_t, int64_t> py_attention_mla_fwd(Tensor q, Tens
   return {o, lse, (int64_t)seed, (int64_t)offset};
 }
 
+// With k_rope, dk is the nope gradient [B, S, H, 128] and dk_rope [B, S, 64] the head-summed rope gradient; the
+// per-head fp32 partials [B, S, H, 64] (256 H bytes per token) live here for the call.
 void py_attention_mla_bwd(Tensor dout, Tensor q, Tensor k, Tensor v, Tensor o, Tensor lse, bool causal, double p,
-                          double scale, int64_t seed, int64_t offset, Tensor dq, Tensor dk, Tensor dv) {
+                          double scale, int64_t seed, int64_t offset, Tensor dq, Tensor dk, Tensor dv,
+                          std::optional<Tensor> k_rope, std::optional<Tensor> dk_rope) {
   AttnMlaArgs a;
-  fill_mla(a, q, k, v, causal, p, scale);
+  fill_mla(a, q, k, v, k_rope, causal, p, scale);
+  MP_CHECK(k_rope.has_value() == dk_rope.has_value(), "attention_mla_bwd: k_rope and dk_rope go together");
   check_mla(o, "o", q, a.Dv);
   check_mla(dout, "dout", q, a.Dv);
   check_mla(dq, "dq", q, a.Dqk);
-  check_mla(dk, "dk", q, a.Dqk);
+  check_mla(dk, "dk", q, k.size(3));
   check_mla(dv, "dv", q, a.Dv);
   MP_CHECK(lse.is_cuda() && lse.device() == q.device() && lse.scalar_type() == at::kFloat && lse.is_contiguous() &&
                lse.dim() == 3 && lse.size(0) == a.B && lse.size(1) == a.H && lse.size(2) == a.S,
            "attention_mla_bwd: lse must be the forward's contiguous fp32 [B, H, S]");
   at::hip::HIPGuardMasqueradingAsCUDA guard(q.device());
   auto delta = at::empty({a.B, a.H, a.S}, q.options().dtype(at::kFloat));
+  Tensor part;
+  if (dk_rope.has_value()) {
+    check_mla_rope(*dk_rope, "dk_rope", q);
+    part = at::empty({a.B, a.S, a.H, 64}, q.options().dtype(at::kFloat));
+    a.dk_rope_part = ptr<float>(part);
+    a.dk_rope = dk_rope->data_ptr();
+    a.sdk_rope = AttnStrides{dk_rope->stride(0), dk_rope->stride(1), 0};
+  }
   a.o = o.data_ptr(); a.so = bshd_strides(o);
   a.dout = dout.data_ptr(); a.sdo = bshd_strides(dout);
   a.dq = dq.data_ptr(); a.sdq = bshd_strides(dq);
@@ -2200,6 +2293,10 @@ PYBIND11_MODULE(_C, m) {
         py::arg("eps"), py::arg("save"));
   m.def("rope_packed", &py_rope_packed, py::arg("qkv"), py::arg("cos"), py::arg("sin"), py::arg("out") = py::none(),
         py::arg("pos0") = 0, py::arg("inverse") = false);
+  m.def("mla_rope_fwd", &py_mla_rope_fwd, py::arg("q"), py::arg("ckv"), py::arg("cos"), py::arg("sin"),
+        py::arg("out") = py::none());
+  m.def("mla_rope_bwd", &py_mla_rope_bwd, py::arg("dq"), py::arg("dk_rope"), py::arg("cos"), py::arg("sin"),
+        py::arg("dckv"), py::arg("out") = py::none());
   m.def("rope_heads", &py_rope_heads, py::arg("x"), py::arg("cos"), py::arg("sin"), py::arg("out") = py::none(),
         py::arg("n_rot"), py::arg("pos0") = 0, py::arg("inverse") = false,
         "x [B, S, heads, D]: the first n_rot heads of every token rotated, the rest passed through");
@@ -2269,10 +2366,11 @@ PYBIND11_MODULE(_C, m) {
     return S <= INT32_MAX && attention_dims_supported((int)S, (int)Dqk, (int)Dv);
   });
   m.def("attention_mla_fwd", &py_attention_mla_fwd, py::arg("q"), py::arg("k"), py::arg("v"), py::arg("causal"),
-        py::arg("p"), py::arg("scale"));
+        py::arg("p"), py::arg("scale"), py::arg("k_rope") = py::none());
   m.def("attention_mla_bwd", &py_attention_mla_bwd, py::arg("dout"), py::arg("q"), py::arg("k"), py::arg("v"),
         py::arg("o"), py::arg("lse"), py::arg("causal"), py::arg("p"), py::arg("scale"), py::arg("seed"),
-        py::arg("offset"), py::arg("dq"), py::arg("dk"), py::arg("dv"));
+        py::arg("offset"), py::arg("dq"), py::arg("dk"), py::arg("dv"), py::arg("k_rope") = py::none(),
+        py::arg("dk_rope") = py::none());
   m.def("attention_long_supported", [](int64_t S, int64_t D) { return attention_long_supported((int)S, (int)D); });
   m.def("attention_long_set_fused_rng", &attention_long_set_fused_rng,
         "long-sequence attention: make the dropout keep words inside the forward kernel (true, default) or in a "

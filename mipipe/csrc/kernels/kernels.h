@@ -130,6 +130,15 @@ void rope_packed(const T* qkv, const float* cos_t, const float* sin_t, T* out, i
 template <typename T>
 void rope_heads(const T* x, const float* cos_t, const float* sin_t, T* out, int64_t B, int S, int n_rot, int n_copy,
                 int D, int pos0, bool inverse, hipStream_t s);
+// Multi-head latent attention's decoupled RoPE in one launch: the last R features of every head of q [B, S, H,
+// Dn + R] (contiguous) are rotated into q_out (== q: in place; another tensor: the nope features are copied),
+// and R columns of ksrc (row stride ks_ld, first column ks_off) are rotated into R columns of kdst (kd_ld,
+// kd_off): the one key head all query heads share.  Pairs (i, i + R/2) inside the slice; cos / sin fp32 [>= S,
+// R/2]; R in {32, 64}, Dn, ks_* and kd_* multiples of 8.  inverse negates sin (the backward).
+template <typename T>
+void mla_rope(const T* q, T* q_out, const T* ksrc, int64_t ks_ld, int64_t ks_off, T* kdst, int64_t kd_ld,
+              int64_t kd_off, const float* cos_t, const float* sin_t, int64_t B, int S, int H, int Dn, int R,
+              bool inverse, hipStream_t s);
 // Grouped-query attention backward: dkv [B, S, 2, H, D] (contiguous) holds one dK and one dV partial per
 // QUERY head; each group of H / Hkv consecutive heads is summed in fp32, rounded once and stored into the
 // K (heads [H, H + Hkv)) and V (heads [H + Hkv, H + 2 Hkv)) slots of dqkv [B, S, H + 2 Hkv, D]
@@ -537,6 +546,16 @@ struct AttnMlaArgs {
   uint32_t threshold = 0;  // set by the launchers from p
   uint64_t seed = 0, offset = 0;
   bool causal = false;
+  // Shared rope key head (multi-head latent attention), appended: k_rope != nullptr selects the SHARED kernels.
+  // k and dk are then the 128-wide "nope" part [B, S, H, 128] and columns [128, 192) of every head's key are the
+  // one head k_rope [B, S, 64] (sk_rope / sdk_rope: batch and token strides, .head unused), read in place.  The
+  // backward leaves each head's fp32 partial of dk_rope in dk_rope_part [B, S, H, 64] (contiguous, 256 H bytes
+  // per token) and mla_reduce_dk_rope sums them over the heads into dk_rope (bf16).
+  const void* k_rope = nullptr;
+  AttnStrides sk_rope;
+  float* dk_rope_part = nullptr;
+  void* dk_rope = nullptr;
+  AttnStrides sdk_rope;
 };
 // S > 0, S % 64 == 0, (Dqk, Dv) == (192, 128).
 bool attention_dims_supported(int S, int Dqk, int Dv);

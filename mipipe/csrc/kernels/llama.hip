@@ -215,6 +215,72 @@ __global__ void __launch_bounds__(kThreads) rope_kernel(const T* qkv, const floa
   }
 }
 
+// Decoupled RoPE of multi-head latent attention, both rotations in one launch.  q [tokens, H, Dn + R]: the last R
+// features of every head are rotated (pairs (i, i + R/2) inside the slice), the Dn nope features are copied only
+// when q_out is another tensor.  The one shared key head: R columns of ksrc (row stride ks_ld, first column
+// ks_off) are rotated into R columns of kdst (kd_ld, kd_off) -- forward: the tail of ckv [tokens, Lkv + R] into a
+// contiguous k_rope [tokens, R]; backward (sign = -1): dk_rope into the tail of dckv.  Items per token: H * R / 16
+// query rotations (8 pairs each), R / 16 key rotations, then H * Dn / 8 copies.  16-byte accesses (Dn, R / 2,
+// ks_*, kd_* multiples of 8), fp32 arithmetic, one rounding at the store.
+template <typename T>
+__global__ void __launch_bounds__(kThreads) mla_rope_kernel(const T* q, T* q_out, const T* __restrict__ ksrc,
+                                                            T* __restrict__ kdst, const float* __restrict__ cos_t,
+                                                            const float* __restrict__ sin_t, int64_t tokens, int S,
+                                                            int H, int Dn, int R, int64_t ks_ld, int64_t ks_off,
+                                                            int64_t kd_ld, int64_t kd_off, float sign, int copy) {
+  const int half = R >> 1;
+  const int hvec = half >> 3;       // rotation items per head
+  const int rot = (H + 1) * hvec;   // per token: the H query heads, then the key head
+  const int nvec = Dn >> 3;
+  const int per_tok = rot + (copy ? H * nvec : 0);
+  const int D = Dn + R;
+  const int64_t nitems = tokens * per_tok;
+  const int64_t stride = (int64_t)gridDim.x * kThreads;
+  for (int64_t t = blockIdx.x * (int64_t)kThreads + threadIdx.x; t < nitems; t += stride) {
+    const int64_t tok = t / per_tok;
+    const int j = (int)(t - tok * per_tok);
+    if (j < rot) {
+      const int h = j / hvec, i = (j - h * hvec) * 8;
+      const T* src;
+      T* dst;
+      if (h < H) {
+        const int64_t e = (tok * H + h) * D + Dn + i;
+        src = q + e;
+        dst = q_out + e;
+      } else {
+        src = ksrc + tok * ks_ld + ks_off + i;
+        dst = kdst + tok * kd_ld + kd_off + i;
+      }
+      const int64_t te = (tok % S) * half + i;
+      float a[8], b[8], c[8], s[8], oa[8], ob[8];
+      Io<T>::load8(src, a);
+      Io<T>::load8(src + half, b);
+      Io<float>::load8(cos_t + te, c);
+      Io<float>::load8(sin_t + te, s);
+#pragma unroll
+      for (int k = 0; k < 8; ++k) {
+        const float sn = s[k] * sign;
+        oa[k] = a[k] * c[k] - b[k] * sn;
+        ob[k] = b[k] * c[k] + a[k] * sn;
+      }
+      Io<T>::store8(dst, oa);
+      Io<T>::store8(dst + half, ob);
+    } else {
+      const int h = (j - rot) / nvec, i = ((j - rot) - h * nvec) * 8;
+      const int64_t e = (tok * H + h) * D + i;
+      if (sizeof(T) == 2) {
+        *reinterpret_cast<u16x8*>(q_out + e) = *reinterpret_cast<const u16x8*>(q + e);
+      } else {
+        const float4* x = reinterpret_cast<const float4*>(q + e);
+        float4* o = reinterpret_cast<float4*>(q_out + e);
+        const float4 v0 = x[0], v1 = x[1];
+        o[0] = v0;
+        o[1] = v1;
+      }
+    }
+  }
+}
+
 // Grouped-query attention: the dK / dV kernels leave one partial per QUERY head
 // in dkv [tokens, 2, H, D]; item (token, which, kv head, 8 features) adds the
 // G = H / Hkv partials of its group in fp32 (in head order), rounds once and
@@ -305,6 +371,18 @@ void rope_packed(const T* qkv, const float* cos_t, const float* sin_t, T* out, i
 }
 
 template <typename T>
+void mla_rope(const T* q, T* q_out, const T* ksrc, int64_t ks_ld, int64_t ks_off, T* kdst, int64_t kd_ld,
+              int64_t kd_off, const float* cos_t, const float* sin_t, int64_t B, int S, int H, int Dn, int R,
+              bool inverse, hipStream_t s) {
+  const bool copy = q_out != q;
+  const int64_t nitems = B * S * ((int64_t)(H + 1) * (R / 16) + (copy ? (int64_t)H * (Dn / 8) : 0));
+  if (nitems == 0) return;
+  hipLaunchKernelGGL((mla_rope_kernel<T>), dim3((unsigned)grid_for(nitems)), dim3(kThreads), 0, s, q, q_out, ksrc,
+                     kdst, cos_t, sin_t, B * S, S, H, Dn, R, ks_ld, ks_off, kd_ld, kd_off, inverse ? -1.f : 1.f,
+                     copy ? 1 : 0);
+}
+
+template <typename T>
 void gqa_reduce_dkv(const T* dkv, T* dqkv, int64_t tokens, int H, int Hkv, int D, hipStream_t s) {
   const int64_t nitems = tokens * 2 * Hkv * (D / 8);
   if (nitems == 0) return;
@@ -324,6 +402,8 @@ template void rope_packed<float>(const float*, const float*, const float*, float
 template void rope_packed<bf16_t>(const bf16_t*, const float*, const float*, bf16_t*, int64_t, int, int, int, int, bool, hipStream_t);
 template void rope_heads<float>(const float*, const float*, const float*, float*, int64_t, int, int, int, int, int, bool, hipStream_t);
 template void rope_heads<bf16_t>(const bf16_t*, const float*, const float*, bf16_t*, int64_t, int, int, int, int, int, bool, hipStream_t);
+template void mla_rope<float>(const float*, float*, const float*, int64_t, int64_t, float*, int64_t, int64_t, const float*, const float*, int64_t, int, int, int, int, bool, hipStream_t);
+template void mla_rope<bf16_t>(const bf16_t*, bf16_t*, const bf16_t*, int64_t, int64_t, bf16_t*, int64_t, int64_t, const float*, const float*, int64_t, int, int, int, int, bool, hipStream_t);
 template void gqa_reduce_dkv<float>(const float*, float*, int64_t, int, int, int, hipStream_t);
 template void gqa_reduce_dkv<bf16_t>(const bf16_t*, bf16_t*, int64_t, int, int, int, hipStream_t);
 

@@ -2,6 +2,8 @@
 driver), GPT-2 style pre-norm causal decoder, LM embedding/head."""
 from .transformer import (
     FeedForwardBlock,
+    LatentAttentionCore,
+    MLADims,
     MoEFeedForwardBlock,
     SelfAttentionBlock,
     TransformerEncoderLayer,
@@ -16,6 +18,8 @@ __all__ = [
     "SelfAttentionBlock",
     "FeedForwardBlock",
     "MoEFeedForwardBlock",
+    "LatentAttentionCore",
+    "MLADims",
     "TransformerEncoderLayer",
     "transformer_blocks",
     "block_flops",

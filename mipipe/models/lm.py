@@ -22,8 +22,8 @@ from torch import Tensor, nn
 from .. import ops
 from ..ops.linear import mark_gemm_weight
 from ..ops.softcap import softcap_owned
-from .transformer import (GATED_ACTS, FeedForwardBlock, check_expert_gemm, check_global_every, layer_window,
-                          transformer_blocks)
+from .transformer import (GATED_ACTS, FeedForwardBlock, MLADims, check_expert_gemm, check_global_every, check_mla,
+                          layer_window, transformer_blocks)
 
 __all__ = [
     "Encoder",
@@ -236,6 +236,9 @@ class LMConfig:
     attn_scale: Optional[float] = None  # score scale; None = head_dim ** -0.5 (Gemma-2: query_pre_attn_scalar ** -0.5)
     global_every: Optional[int] = None  # layer i is global (no window) when (i + 1) % n == 0; needs window
     attn_sinks: bool = False          # a learned logit per query head in the softmax's denominator (gpt-oss): [nhead]
+    # Multi-head latent attention (DeepSeek-V2 / V3, Kimi K2): an MLADims, None = the usual core.  No entry of CONFIGS
+    # sets it: dataclasses.replace(CONFIGS["llama_tiny"], mla=MLADims(kv_lora_rank=64), nhead=2)
+    mla: Optional[MLADims] = None
     # Mixture-of-experts MLP in every layer (Mixtral, Qwen3-MoE): None = the dense MLP
     n_experts: Optional[int] = None   # experts per layer, each a gated MLP of width dim_feedforward
     experts_per_token: int = 2        # experts a token runs, weighted by the softmax over their router logits
@@ -248,13 +251,31 @@ class LMConfig:
     def __post_init__(self) -> None:
         check_global_every(self.global_every, self.window)
         check_expert_gemm(self.expert_gemm, self.capacity_factor)
+        check_mla(self.mla, rope=self.rope, norm=self.norm, n_kv_heads=self.n_kv_heads, head_dim=self.head_dim,
+                  window=self.window, qk_norm=self.qk_norm, attn_softcap=self.attn_softcap, attn_sinks=self.attn_sinks)
 
     def head_width(self) -> int:
         return self.d_model // self.nhead if self.head_dim is None else self.head_dim
 
     def attn_dim(self) -> int:
         """Width of the attention output before ``out_proj``: ``H D`` (``d_model`` unless ``head_dim`` is set)."""
+        if self.mla is not None:
+            return self.nhead * self.mla.v_dim
         return self.nhead * self.head_width()
+
+    def attn_proj_params(self) -> int:
+        """Elements of the attention core's projection weights: ``qkv_dim() * d_model``, or the latent projections'."""
+        if self.mla is not None:
+            return self.mla.proj_params(self.d_model, self.nhead)
+        return self.qkv_dim() * self.d_model
+
+    def attn_work_dim(self) -> float:
+        """Width the attention itself works at, in units of ``4 keys`` FLOPs per token: ``attn_dim()``, or for latent
+        attention ``H (Dn + R + Dv) / 2`` (scores and weighted sum have different widths)."""
+        if self.mla is not None:
+            m = self.mla
+            return self.nhead * (m.nope_dim + m.rope_dim + m.v_dim) / 2
+        return self.attn_dim()
 
     def qkv_dim(self) -> int:
         """Width of the QKV projection: ``(H + 2 Hkv) D`` (``3 d_model`` without grouped-query attention)."""
@@ -276,6 +297,8 @@ class LMConfig:
         nb = 1 if self.bias else 0
         norm = e * (2 if self.norm == "layer" else 1)
         qkv = self.qkv_dim()
+        if self.mla is not None:  # the latent projections and their two norms; bias-free by construction
+            return self._params_mla()
         if self.n_experts is not None:  # the router and the experts (bias-free) in place of the dense MLP
             mlp = self.n_experts * (e + f1 * e + e * f)
             layer = (qkv + self.attn_dim()) * e + 2 * norm + mlp + nb * (qkv + e)
@@ -292,6 +315,23 @@ class LMConfig:
             total += max(self.seq_len, 1024) * e
         if self.norm_first:
             total += norm
+        return total + (v * e + v)
+
+    def _params_mla(self) -> int:
+        e, f, v = self.d_model, self.dim_feedforward, self.vocab
+        f1 = 2 * f if self.activation in GATED_ACTS else f
+        nb = 1 if self.bias else 0
+        attn = self.attn_proj_params() + self.mla.norm_params() + self.attn_dim() * e + nb * e
+        if self.n_experts is not None:
+            mlp = self.n_experts * (e + f1 * e + e * f)
+        else:
+            mlp = f1 * e + e * f + nb * (f1 + e)
+        layer = attn + 2 * e + mlp + (2 * e if self.sandwich_norm else 0)
+        total = self.num_layers * layer + v * e
+        if self.encoder_positions() == "learned":
+            total += max(self.seq_len, 1024) * e
+        if self.norm_first:
+            total += e
         return total + (v * e + v)
 
 
@@ -454,8 +494,8 @@ def build_lm_blocks(cfg: LMConfig, *, device=None, dtype=None) -> List[nn.Module
                                  sandwich_norm=cfg.sandwich_norm, head_dim=cfg.head_dim, attn_scale=cfg.attn_scale,
                                  global_every=cfg.global_every, attn_sinks=cfg.attn_sinks, n_experts=cfg.n_experts,
                                  experts_per_token=cfg.experts_per_token, capacity_factor=cfg.capacity_factor,
-                                 moe_aux_coef=cfg.moe_aux_coef, expert_gemm=cfg.expert_gemm, device=device,
-                                 dtype=dtype)
+                                 moe_aux_coef=cfg.moe_aux_coef, expert_gemm=cfg.expert_gemm, mla=cfg.mla,
+                                 device=device, dtype=dtype)
     if cfg.act_dropout is not None:
         for b in blocks:
             if isinstance(b, FeedForwardBlock):

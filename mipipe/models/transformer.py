@@ -58,6 +58,15 @@ A]``.  ``attn_scale`` (``None`` means ``1 / sqrt(D)``) is the score scale
 ``global_every=n``: layer ``i`` with ``(i + 1) % n == 0`` is a global layer, built
 without the window.
 
+``mla=MLADims(kv_lora_rank=Lkv, ...)`` (DeepSeek-V2 / V3, Kimi K2; needs
+``rope=True`` and ``norm="rms"``, excludes ``n_kv_heads``, ``head_dim``,
+``window``, ``qk_norm``, ``attn_softcap`` and ``attn_sinks``) makes the attention
+core a :class:`LatentAttentionCore`: multi-head latent attention, whose keys and
+values are up-projected from one normalised ``Lkv``-wide latent per token and
+whose rotary features are decoupled -- ``R`` rotated features per query head
+against ONE rotated key head shared by all heads (``ops.mla_rope``,
+``ops.attention``'s ``k_rope=``).  The core returns ``o [B, S, nhead * v_dim]``.
+
 ``transformer_blocks(..., n_experts=Ne)`` replaces every layer's MLP with a
 :class:`MoEFeedForwardBlock` (Mixtral, Qwen3-MoE): ``Ne`` gated experts, a top-k
 softmax router with a fixed capacity per expert (``ops.moe_route`` /
@@ -68,6 +77,7 @@ from __future__ import annotations
 
 import math
 import os
+from dataclasses import dataclass
 from typing import List, Optional
 
 import torch
@@ -145,6 +155,8 @@ def _norm_fanout(mod: nn.Module, x: Tensor):
 
 __all__ = [
     "AttentionCore",
+    "LatentAttentionCore",
+    "MLADims",
     "AttentionOutput",
     "PackedAttentionCore",
     "PackedAttentionOutput",
@@ -344,6 +356,156 @@ class AttentionCore(nn.Module):
         return 2 * self.qkv_dim * e + 4 * keys * self.attn_dim
 
 
+@dataclass(frozen=True)
+class MLADims:
+    """The widths of a multi-head latent attention core (DeepSeek-V2's names): the key/value latent
+    ``kv_lora_rank``, the query latent ``q_lora_rank`` (``None``: a plain query projection), and per head
+    ``nope_dim`` position-free and ``rope_dim`` rotary query/key features and ``v_dim`` value features.  The defaults
+    are the (128 + 64, 128) heads attention_mla.hip tiles."""
+    kv_lora_rank: int
+    q_lora_rank: Optional[int] = None
+    nope_dim: int = 128
+    rope_dim: int = 64
+    v_dim: int = 128
+
+    def __post_init__(self) -> None:
+        for name in ("kv_lora_rank", "nope_dim", "rope_dim", "v_dim"):
+            if isinstance(getattr(self, name), bool) or not isinstance(getattr(self, name), int) or getattr(self, name) < 1:
+                raise ValueError(f"MLADims.{name} must be an int >= 1, got {getattr(self, name)!r}")
+        if self.q_lora_rank is not None and (isinstance(self.q_lora_rank, bool) or not isinstance(self.q_lora_rank, int)
+                                             or self.q_lora_rank < 1):
+            raise ValueError(f"MLADims.q_lora_rank must be an int >= 1 or None, got {self.q_lora_rank!r}")
+        if self.rope_dim % 2 != 0:
+            raise ValueError(f"MLADims.rope_dim must be even, got {self.rope_dim}")
+
+    def proj_params(self, d_model: int, nhead: int) -> int:
+        """Elements of the core's projection weights (the GEMMs of one token, in multiply-adds)."""
+        qk = nhead * (self.nope_dim + self.rope_dim)
+        q = qk * d_model if self.q_lora_rank is None else self.q_lora_rank * (d_model + qk)
+        return q + (self.kv_lora_rank + self.rope_dim) * d_model + nhead * (self.nope_dim + self.v_dim) * self.kv_lora_rank
+
+    def norm_params(self) -> int:
+        return self.kv_lora_rank + (self.q_lora_rank or 0)
+
+
+def check_mla(mla: Optional[MLADims], *, rope: bool, norm: str, n_kv_heads=None, head_dim=None, window=None,
+              qk_norm=False, attn_softcap=None, attn_sinks=False) -> None:
+    """``mla`` needs rotary positions and RMSNorm and excludes the options its kernels and layout do not have."""
+    if mla is None:
+        return
+    if not isinstance(mla, MLADims):
+        raise ValueError(f"mla must be an MLADims or None, got {mla!r}")
+    if not rope or norm != "rms":
+        raise ValueError(f"mla needs rope=True and norm='rms', got rope={rope}, norm={norm!r}")
+    given = {"n_kv_heads": n_kv_heads is not None, "head_dim": head_dim is not None, "window": window is not None,
+             "qk_norm": bool(qk_norm), "attn_softcap": attn_softcap is not None, "attn_sinks": bool(attn_sinks)}
+    bad = [k for k, v in given.items() if v]
+    if bad:
+        raise ValueError(f"mla does not combine with {', '.join(bad)}")
+
+
+class LatentAttentionCore(nn.Module):
+    """Multi-head latent attention (pre-norm: the norm first): ``x [B, S, E] -> o [B, S, A]``, ``A = nhead * v_dim``;
+    :class:`AttentionCore`'s surface, so :class:`AttentionOutput` and the packed units take it unchanged.
+
+    ``ckv = kv_a(x)`` is ``[Lkv | R]`` wide: the latent, RMS-normalised and up-projected by ``kv_b`` to every head's
+    ``Dn`` nope key features and ``Dv`` value features, and the one rotary key head.  ``q`` is ``q(x)``, or
+    ``q_b(RMSNorm(q_a(x)))`` with a query latent, ``Dn + R`` wide per head.  ``ops.mla_rope`` rotates the ``R``-wide
+    slices in one launch, and ``ops.attention`` reads the nope keys and the values as strided views of the ``kv_b``
+    output and the shared rope head in place (``k_rope=``).  No biases."""
+
+    def __init__(self, d_model: int, nhead: int, dropout: float, *, mla: MLADims, norm_first: bool, causal: bool,
+                 layer_norm_eps: float, norm: str = "rms", rope_base: float = 10000.0,
+                 attn_scale: Optional[float] = None, device=None, dtype=None) -> None:
+        super().__init__()
+        check_mla(mla, rope=True, norm=norm)
+        fk = {"device": device, "dtype": dtype}
+        self.d_model, self.nhead, self.mla = d_model, nhead, mla
+        self.attn_dim = nhead * mla.v_dim
+        if attn_scale is not None:
+            if (isinstance(attn_scale, bool) or not isinstance(attn_scale, (int, float))
+                    or not math.isfinite(attn_scale) or attn_scale <= 0):
+                raise ValueError(f"attn_scale must be a finite number > 0 or None, got {attn_scale!r}")
+            attn_scale = float(attn_scale)
+        self.attn_scale = attn_scale  # None: the op's own 1 / sqrt(nope_dim + rope_dim)
+        self.dropout, self.norm_first, self.causal, self.eps = dropout, norm_first, causal, layer_norm_eps
+        self.norm, self.rope_base = norm, rope_base
+        weight = lambda *shape: mark_gemm_weight(nn.Parameter(torch.empty(*shape, **fk)))  # noqa: E731
+        qk = nhead * (mla.nope_dim + mla.rope_dim)
+        self.kv_a_weight = weight(mla.kv_lora_rank + mla.rope_dim, d_model)
+        self.kv_norm_weight = nn.Parameter(torch.empty(mla.kv_lora_rank, **fk))
+        self.kv_b_weight = weight(nhead * (mla.nope_dim + mla.v_dim), mla.kv_lora_rank)
+        if mla.q_lora_rank is None:
+            self.q_weight = weight(qk, d_model)
+        else:
+            self.q_a_weight = weight(mla.q_lora_rank, d_model)
+            self.q_norm_weight = nn.Parameter(torch.empty(mla.q_lora_rank, **fk))
+            self.q_b_weight = weight(qk, mla.q_lora_rank)
+        if norm_first:
+            _init_norm(self, d_model, norm, fk)
+        empty = torch.empty(0, mla.rope_dim // 2, device=device, dtype=torch.float32)
+        self.register_buffer("rope_cos", empty, persistent=False)
+        self.register_buffer("rope_sin", empty.clone(), persistent=False)
+        self.reset_parameters()
+
+    def reset_parameters(self) -> None:
+        for name, p in self.named_parameters(recurse=False):
+            if name in ("kv_norm_weight", "q_norm_weight"):
+                nn.init.ones_(p)
+            elif name.endswith("_weight") and p.dim() == 2:
+                nn.init.xavier_uniform_(p)
+        if self.norm_first:
+            _reset_norm(self)
+
+    def _rope_tables(self, seq_len: int, device):
+        if (self.rope_cos.shape[0] < seq_len or self.rope_cos.device != device
+                or self.rope_cos.dtype != torch.float32):
+            self.rope_cos, self.rope_sin = ops.rope_tables(seq_len, self.mla.rope_dim, self.rope_base, device=device)
+        return self.rope_cos, self.rope_sin
+
+    def forward(self, x: Tensor) -> Tensor:
+        return self.forward_fanout(x, fanout=False)[0]
+
+    def forward_fanout(self, x: Tensor, fanout: bool = True):
+        """``(o, x')`` as :meth:`AttentionCore.forward_fanout`; only the pre-norm's fan-out is fused (a post-norm
+        ``x`` feeds two projections, whose gradients autograd adds)."""
+        if ops.current_documents() is not None:
+            raise ValueError("LatentAttentionCore: document bounds are set (ops.use_documents) but document masks "
+                             "are not supported on a multi-head latent attention core")
+        B, S, _ = x.shape
+        m, H = self.mla, self.nhead
+        xr = x
+        if self.norm_first:
+            if fanout:
+                x, xr = _norm_fanout(self, x)
+            else:
+                x = _norm(self, x, None, 0.0)
+        ckv = ops.linear(x, self.kv_a_weight, None)
+        if m.q_lora_rank is None:
+            q = ops.linear(x, self.q_weight, None)
+        else:
+            cq = ops.add_dropout_rms_norm(ops.linear(x, self.q_a_weight, None), None, self.q_norm_weight, self.eps,
+                                          0.0, self.training)
+            q = ops.linear(cq, self.q_b_weight, None)
+        cos, sin = self._rope_tables(S, x.device)
+        q, k_rope = ops.mla_rope(q.view(B, S, H, m.nope_dim + m.rope_dim), ckv, cos, sin)
+        # (the norm wants contiguous rows: fusing this split with it is a kernel of its own)
+        c = ops.add_dropout_rms_norm(ckv[..., :m.kv_lora_rank].contiguous(), None, self.kv_norm_weight, self.eps, 0.0,
+                                     self.training)
+        kv = ops.linear(c, self.kv_b_weight, None).view(B, S, H, m.nope_dim + m.v_dim)
+        # the two halves of the up-projection, read where they are
+        k_nope, v = kv[..., :m.nope_dim].transpose(1, 2), kv[..., m.nope_dim:].transpose(1, 2)
+        o = ops.attention(q.transpose(1, 2), k_nope, v, causal=self.causal, dropout_p=self.dropout,
+                          training=self.training, scale=self.attn_scale, k_rope=k_rope)
+        return o.transpose(1, 2).reshape(B, S, self.attn_dim), xr
+
+    def flops_per_token(self, seq_len: int) -> float:
+        m = self.mla
+        keys = seq_len * (0.5 if self.causal else 1.0)
+        # the scores are Dn + R wide and the weighted sum Dv: 2 (Dn + R) + 2 Dv = 4 (Dn + R + Dv) / 2 per key and head
+        return 2 * m.proj_params(self.d_model, self.nhead) + 4 * keys * self.nhead * (m.nope_dim + m.rope_dim + m.v_dim) / 2
+
+
 class AttentionOutput(nn.Module):
     """``out_proj`` + dropout + residual (+ LayerNorm for post-norm): ``(x, o) -> y``.
 
@@ -403,16 +565,23 @@ class SelfAttentionBlock(nn.Module):
                  rope: bool = False, rope_base: float = 10000.0, n_kv_heads: Optional[int] = None,
                  window: Optional[int] = None, qk_norm: bool = False, attn_softcap: Optional[float] = None,
                  sandwich_norm: bool = False, head_dim: Optional[int] = None, attn_scale: Optional[float] = None,
-                 attn_sinks: bool = False, device=None, dtype=None) -> None:
+                 attn_sinks: bool = False, mla: Optional[MLADims] = None, device=None, dtype=None) -> None:
         super().__init__()
-        if head_dim is None and d_model % nhead != 0:
+        check_mla(mla, rope=rope, norm=norm, n_kv_heads=n_kv_heads, head_dim=head_dim, window=window, qk_norm=qk_norm,
+                  attn_softcap=attn_softcap, attn_sinks=attn_sinks)
+        if head_dim is None and mla is None and d_model % nhead != 0:
             raise ValueError("d_model must be divisible by nhead")
         _check_sandwich(sandwich_norm, norm_first, norm, dropout)
-        self.core = AttentionCore(d_model, nhead, dropout, norm_first=norm_first, causal=causal,
-                                  layer_norm_eps=layer_norm_eps, norm=norm, bias=bias, rope=rope,
-                                  rope_base=rope_base, n_kv_heads=n_kv_heads, window=window, qk_norm=qk_norm,
-                                  attn_softcap=attn_softcap, head_dim=head_dim, attn_scale=attn_scale,
-                                  attn_sinks=attn_sinks, device=device, dtype=dtype)
+        if mla is not None:
+            self.core = LatentAttentionCore(d_model, nhead, dropout, mla=mla, norm_first=norm_first, causal=causal,
+                                            layer_norm_eps=layer_norm_eps, norm=norm, rope_base=rope_base,
+                                            attn_scale=attn_scale, device=device, dtype=dtype)
+        else:
+                self.core = AttentionCore(d_model, nhead, dropout, norm_first=norm_first, causal=causal,
+                                      layer_norm_eps=layer_norm_eps, norm=norm, bias=bias, rope=rope,
+                                      rope_base=rope_base, n_kv_heads=n_kv_heads, window=window, qk_norm=qk_norm,
+                                      attn_softcap=attn_softcap, head_dim=head_dim, attn_scale=attn_scale,
+                                      attn_sinks=attn_sinks, device=device, dtype=dtype)
         self.out = AttentionOutput(d_model, dropout, norm_first=norm_first, layer_norm_eps=layer_norm_eps,
                                    norm=norm, bias=bias, attn_dim=self.core.attn_dim, sandwich_norm=sandwich_norm,
                                    device=device, dtype=dtype)
@@ -860,13 +1029,14 @@ class TransformerEncoderLayer(nn.Sequential):
         head_dim: Optional[int] = None,
         attn_scale: Optional[float] = None,
         attn_sinks: bool = False,
+        mla: Optional[MLADims] = None,
     ) -> None:
         super().__init__(
             SelfAttentionBlock(d_model, nhead, dropout, norm_first=norm_first, causal=causal,
                                layer_norm_eps=layer_norm_eps, norm=norm, bias=bias, rope=rope, rope_base=rope_base,
                                n_kv_heads=n_kv_heads, window=window, qk_norm=qk_norm, attn_softcap=attn_softcap,
                                sandwich_norm=sandwich_norm, head_dim=head_dim, attn_scale=attn_scale,
-                               attn_sinks=attn_sinks, device=device, dtype=dtype),
+                               attn_sinks=attn_sinks, mla=mla, device=device, dtype=dtype),
             FeedForwardBlock(d_model, dim_feedforward, dropout, activation, norm_first=norm_first,
                              layer_norm_eps=layer_norm_eps, norm=norm, bias=bias, sandwich_norm=sandwich_norm,
                              device=device, dtype=dtype),
@@ -940,6 +1110,7 @@ def transformer_blocks(
     capacity_factor: Optional[float] = 1.25,
     moe_aux_coef: float = 0.01,
     expert_gemm: str = "loop",
+    mla: Optional[MLADims] = None,
     device=None,
     dtype=None,
 ) -> List[nn.Module]:
@@ -951,7 +1122,9 @@ def transformer_blocks(
     ``n_experts=Ne`` (``None``: dense) builds a :class:`MoEFeedForwardBlock` of ``Ne`` experts of width
     ``dim_feedforward`` in place of the :class:`FeedForwardBlock` of every layer (pre-norm, bias-free, gated
     activation, no sandwich norm); ``expert_gemm="grouped"`` (with ``capacity_factor=None``) selects its dropless
-    grouped-GEMM path."""
+    grouped-GEMM path.
+
+    ``mla=MLADims(...)`` (``None``: none) builds every layer's attention core as a :class:`LatentAttentionCore`."""
     check_global_every(global_every, window)
     blocks: List[nn.Module] = []
     if n_experts is not None:
@@ -962,7 +1135,7 @@ def transformer_blocks(
                                              bias=bias, rope=rope, rope_base=rope_base, n_kv_heads=n_kv_heads,
                                              window=layer_window(window, global_every, i), qk_norm=qk_norm,
                                              attn_softcap=attn_softcap, head_dim=head_dim, attn_scale=attn_scale,
-                                             attn_sinks=attn_sinks, device=device, dtype=dtype))
+                                             attn_sinks=attn_sinks, mla=mla, device=device, dtype=dtype))
             blocks.append(MoEFeedForwardBlock(d_model, dim_feedforward, n_experts, experts_per_token,
                                               capacity_factor=capacity_factor, aux_coef=moe_aux_coef,
                                               activation=activation, norm_first=norm_first, norm=norm, bias=bias,
@@ -974,7 +1147,8 @@ def transformer_blocks(
                                         rope_base=rope_base, n_kv_heads=n_kv_heads,
                                         window=layer_window(window, global_every, i), qk_norm=qk_norm,
                                         attn_softcap=attn_softcap, sandwich_norm=sandwich_norm, head_dim=head_dim,
-                                        attn_scale=attn_scale, attn_sinks=attn_sinks, device=device, dtype=dtype)
+                                        attn_scale=attn_scale, attn_sinks=attn_sinks, mla=mla, device=device,
+                                        dtype=dtype)
         blocks.extend(layer.children())
     return blocks
 

@@ -15,7 +15,8 @@ from .activation import bias_act_dropout
 from .softcap import softcap, softcap_owned, softcap_reference
 from .swiglu import swiglu, swiglu_reference
 from .geglu import geglu, geglu_reference
-from .rope import rope_heads, rope_packed, rope_projection, rope_reference, rope_tables
+from .rope import (mla_rope, mla_rope_reference, rope_heads, rope_packed, rope_projection, rope_reference,
+                   rope_tables)
 from .qknorm import qk_norm_rope_heads, qk_norm_rope_projection, qk_norm_rope_reference
 from .moe import (moe_assign, moe_assign_reference, moe_assign_sorted, moe_assign_sorted_reference, moe_attach_aux,
                   moe_capacity, moe_combine, moe_combine_reference, moe_dispatch, moe_dispatch_reference, moe_route,
@@ -58,6 +59,8 @@ __all__ = [
     "rope_projection",
     "rope_heads",
     "rope_reference",
+    "mla_rope",
+    "mla_rope_reference",
     "qk_norm_rope_heads",
     "qk_norm_rope_projection",
     "qk_norm_rope_reference",

@@ -105,6 +105,18 @@ attention as DeepSeek-V2 / V3 train it -- runs csrc/kernels/attention_mla.hip at
 ``S % 64 == 0``, and causal at any other length by end padding; every operand is
 read with its own strides.  None of the options above is native there, nor is
 fp32 or another dim pair: those run :func:`attention_reference`.
+
+Shared rope key head, ``k_rope`` -- ``[B, S, R]``, with ``k [B, H, S, D - R]`` the
+"nope" features: multi-head latent attention's keys are ``cat(k[:, h], k_rope)``
+for every head ``h``, one rotary head shared by all of them.  The native path
+(bf16, dims (128 + 64, 128), the lengths above, none of the options, K/V heads
+equal to the query heads) runs attention_mla.hip's SHARED kernels, which read
+``k_rope`` in place -- nothing is repeated or concatenated -- and give the bits
+of the call on the hand-concatenated K; ``dk_rope`` is the fixed-order fp32 sum
+of the heads' partials (a scratch of ``256 H`` bytes per token for the call),
+rounded once.  ``k`` and ``v`` may be the two halves of one ``[B, S, H, 256]``
+up-projection output.  Everything else concatenates and runs as it would
+without ``k_rope``, autograd summing the heads.
 """
 from __future__ import annotations
 
@@ -220,12 +232,17 @@ def use_documents(bounds: Optional[Tensor]):
 
 def attention_reference(q: Tensor, k: Tensor, v: Tensor, causal: bool, p: float, scale: Optional[float] = None,
                         *, window: Optional[int] = None, softcap: Optional[float] = None,
-                        doc_bounds: Optional[Tensor] = None, sinks: Optional[Tensor] = None) -> Tensor:
+                        doc_bounds: Optional[Tensor] = None, sinks: Optional[Tensor] = None,
+                        k_rope: Optional[Tensor] = None) -> Tensor:
     """Eager fp32 math on ``[B, H, S, D]`` (CPU path and test oracle).  ``window``: query ``i`` sees the keys
     ``i - window < j <= i`` only.  ``softcap``: the scaled scores become ``softcap * tanh(s / softcap)`` before
     the masks.  ``doc_bounds`` (int32 ``[B, 2, S]``): query ``i`` sees the keys ``j >= doc_bounds[b, 0, i]``
     only.  ``sinks`` (``[H]``): one more logit per query head in the softmax's denominator, with no value (the
-    module doc); the math then runs in fp64 for fp64 inputs."""
+    module doc); the math then runs in fp64 for fp64 inputs.  ``k_rope [B, S, R]``: the shared rope key head is
+    repeated behind every head's ``k [B, H, S, D - R]`` (autograd sums the heads)."""
+    if k_rope is not None:
+        _check_k_rope(q, k, k_rope)
+        k = _cat_rope(k, k_rope)
     d = q.shape[-1]
     scale = scale if scale is not None else 1.0 / math.sqrt(d)
     window = _check_window(window, bool(causal), q.shape[-2])
@@ -416,27 +433,38 @@ def _strided_ok(t: Tensor) -> bool:
             and t.data_ptr() % 16 == 0)
 
 
+def _rope_ok(t: Tensor) -> bool:
+    """``k_rope [B, S, R]`` is readable in place: :func:`_strided_ok` without a head axis."""
+    return t.stride(2) == 1 and all(s >= 0 and s % 8 == 0 for s in t.stride()[:2]) and t.data_ptr() % 16 == 0
+
+
 class _AttentionDims(torch.autograd.Function):
     """``q, k [B, S, H, Dqk]`` and ``v [B, S, H, Dv]`` with ``Dv != Dqk`` in, ``o [B, S, H, Dv]`` out
-    (attention_mla.hip).  Each operand keeps its own strides; the gradients are fresh contiguous buffers."""
+    (attention_mla.hip).  Each operand keeps its own strides; the gradients are fresh contiguous buffers.  With
+    ``k_rope [B, S, 64]`` (the shared rope key head) ``k`` is the nope part ``[B, S, H, Dqk - 64]``, nothing is
+    concatenated, and ``dk_rope`` comes back summed over the heads."""
 
     @staticmethod
-    def forward(ctx, q, k, v, causal, p, scale):  # type: ignore[override]
+    def forward(ctx, q, k, v, causal, p, scale, k_rope=None):  # type: ignore[override]
         q, k, v = (t if _strided_ok(t) else t.contiguous() for t in (q, k, v))
-        o, lse, seed, offset = kernels_for(q).attention_mla_fwd(q, k, v, causal, p, scale)
-        ctx.save_for_backward(q, k, v, o, lse)
+        if k_rope is not None and not _rope_ok(k_rope):
+            k_rope = k_rope.contiguous()
+        o, lse, seed, offset = kernels_for(q).attention_mla_fwd(q, k, v, causal, p, scale, k_rope)
+        ctx.save_for_backward(q, k, v, o, lse, k_rope)
         ctx.scalars = (causal, p, scale, seed, offset)
         return o
 
     @staticmethod
     def backward(ctx, do):  # type: ignore[override]
-        q, k, v, o, lse = ctx.saved_tensors
+        q, k, v, o, lse, k_rope = ctx.saved_tensors
         causal, p, scale, seed, offset = ctx.scalars
         if not _strided_ok(do):
             do = do.contiguous()
         dq, dk, dv = (torch.empty(t.shape, dtype=t.dtype, device=t.device) for t in (q, k, v))
-        kernels_for(do).attention_mla_bwd(do, q, k, v, o, lse, causal, p, scale, seed, offset, dq, dk, dv)
-        return dq, dk, dv, None, None, None
+        dk_rope = None if k_rope is None else torch.empty(k_rope.shape, dtype=k_rope.dtype, device=k_rope.device)
+        kernels_for(do).attention_mla_bwd(do, q, k, v, o, lse, causal, p, scale, seed, offset, dq, dk, dv, k_rope,
+                                          dk_rope)
+        return dq, dk, dv, None, None, None, dk_rope
 
 
 _noted = set()
@@ -650,20 +678,31 @@ def attention_gqa_packed(qkv: Tensor, n_kv_heads: int, causal: bool = False, dro
     return _packed(qkv, n_kv, causal, p, scale, window, softcap, docs, sinks)
 
 
+def _cat_rope(k: Tensor, k_rope: Tensor) -> Tensor:
+    """``k [B, H, S, Dn]`` with the shared ``k_rope [B, S, R]`` behind every head's features (differentiable: the
+    backward sums the heads)."""
+    return torch.cat((k, k_rope[:, None].expand(-1, k.shape[1], -1, -1)), dim=-1)
+
+
 def _attention_dims(q: Tensor, k: Tensor, v: Tensor, causal: bool, p: float, scale: float, window: Optional[int],
-                    softcap: Optional[float], docs: Optional[Tensor], sinks: Optional[Tensor]) -> Tensor:
+                    softcap: Optional[float], docs: Optional[Tensor], sinks: Optional[Tensor],
+                    k_rope: Optional[Tensor] = None) -> Tensor:
     """:func:`attention` where ``v``'s head dim differs from ``q``'s and ``k``'s (``[B, H, S, D]`` tensors with
     equal head counts).  bf16 on the GPU with the dims attention_mla.hip tiles and no option runs its kernels, a
     causal sequence off the 64-token tile zero-padded at the end (no real query sees a pad key); everything else
-    is :func:`attention_reference`, noted once per shape on the GPU."""
+    is :func:`attention_reference`, noted once per shape on the GPU.  ``k_rope [B, S, 64]``: ``k`` is the nope part
+    ``[B, H, S, D - 64]`` and the kernels read the shared rope head in place; the eager path concatenates."""
     S, D, Dv = q.shape[2], q.shape[3], v.shape[3]
     sp = None
-    if q.is_cuda and q.dtype == torch.bfloat16 and not _is_generic(window, softcap, docs, sinks):
+    if (q.is_cuda and q.dtype == torch.bfloat16 and not _is_generic(window, softcap, docs, sinks)
+            and (k_rope is None or k_rope.shape[-1] == 64)):
         supported = kernels_for(q).attention_dims_supported
         sp = next((s for s in ((S,) if not causal else (S, -(-S // 64) * 64)) if supported(s, D, Dv)), None)
     if sp is None:
         if q.is_cuda:
             key = (S, D, Dv, q.dtype, window is not None, softcap is not None, docs is not None, sinks is not None)
+            if k_rope is not None:
+                key += (k_rope.shape[-1],)
             if key not in _noted:
                 _noted.add(key)
                 import warnings
@@ -672,25 +711,42 @@ def _attention_dims(q: Tensor, k: Tensor, v: Tensor, causal: bool, p: float, sca
                               "path (HIP kernels for differing head dims: bf16, (192, 128), S % 64 == 0 or causal, "
                               "no window, cap, document bounds or sinks)", stacklevel=3)
         return attention_reference(q, k, v, causal, p, scale, window=window, softcap=softcap, doc_bounds=docs,
-                                   sinks=sinks)
+                                   sinks=sinks, k_rope=k_rope)
     if sp != S:
         q, k, v = (F.pad(t, (0, 0, 0, sp - S)) for t in (q, k, v))
-    o = _AttentionDims.apply(q.transpose(1, 2), k.transpose(1, 2), v.transpose(1, 2), causal, p, scale)
+        k_rope = None if k_rope is None else F.pad(k_rope, (0, 0, 0, sp - S))
+    o = _AttentionDims.apply(q.transpose(1, 2), k.transpose(1, 2), v.transpose(1, 2), causal, p, scale, k_rope)
     return o.transpose(1, 2)[:, :, :S]
+
+
+def _check_k_rope(q: Tensor, k: Tensor, k_rope: Tensor) -> None:
+    """``k_rope [B, S, R]`` of q's dtype and device, with ``k`` the ``D - R`` features before it."""
+    if not isinstance(k_rope, Tensor) or k_rope.dim() != 3 or k_rope.dtype != q.dtype or k_rope.device != q.device:
+        raise ValueError("attention: k_rope must be a [B, S, R] tensor of q's dtype and device, got "
+                         f"{tuple(k_rope.shape) if isinstance(k_rope, Tensor) else k_rope!r}")
+    B, _, S, D = q.shape
+    R = k_rope.shape[-1]
+    if tuple(k_rope.shape[:2]) != (B, S) or R <= 0 or k.shape[-1] + R != D:
+        raise ValueError(f"attention: k_rope {tuple(k_rope.shape)} must be [B, S, R] = [{B}, {S}, R] with k's head "
+                         f"dim {k.shape[-1]} + R equal to q's {D}")
 
 
 def attention(
     q: Tensor, k: Tensor, v: Tensor, causal: bool = False, dropout_p: float = 0.0, training: bool = True,
     scale: Optional[float] = None, *, window: Optional[int] = None, softcap: Optional[float] = None,
-    doc_bounds: Optional[Tensor] = None, sinks: Optional[Tensor] = None,
+    doc_bounds: Optional[Tensor] = None, sinks: Optional[Tensor] = None, k_rope: Optional[Tensor] = None,
 ) -> Tensor:
     """``q, k, v [B, H, S, D]`` -> ``[B, H, S, D]``.  ``k`` and ``v`` may have fewer heads, ``Hkv | H``
     (grouped-query attention): separate tensors do not share q's strides, so their heads are repeated
     (autograd sums each group's gradient).  ``window``: sliding-window attention, ``softcap``: logit
     soft-capping, ``doc_bounds``: document masks, ``sinks``: attention sinks (module doc).  ``v`` may have a
     head dim of its own, ``[B, H, S, Dv]`` -> ``[B, H, S, Dv]`` (multi-head latent attention's 192 / 128): see
-    :func:`_attention_dims`; the default ``scale`` stays ``1 / sqrt(D)`` of ``q``."""
-    if k.shape[-1] != q.shape[-1]:
+    :func:`_attention_dims`; the default ``scale`` stays ``1 / sqrt(D)`` of ``q``.  ``k_rope [B, S, R]`` is
+    multi-head latent attention's shared rotary key head: ``k`` is then ``[B, H, S, D - R]`` and every head's key
+    is ``cat(k[:, h], k_rope)`` (module doc)."""
+    if k_rope is not None:
+        _check_k_rope(q, k, k_rope)
+    elif k.shape[-1] != q.shape[-1]:
         raise ValueError(f"attention: k's head dim {k.shape[-1]} differs from q's {q.shape[-1]} (only v may differ)")
     if k.shape[1] != q.shape[1]:
         if k.shape[1] != v.shape[1] or k.shape[1] <= 0 or q.shape[1] % k.shape[1] != 0:
@@ -705,8 +761,10 @@ def attention(
     softcap = _check_softcap(softcap)
     docs = _check_docs(doc_bounds, causal, B, S)
     sinks = _check_sinks(sinks, q.shape[1], q.dtype)
+    if k_rope is not None and v.shape[-1] == D:  # one head dim: the plan's op on the concatenated K
+        k, k_rope = _cat_rope(k, k_rope), None
     if v.shape[-1] != D:  # before the plan, which knows one head dim
-        return _attention_dims(q, k, v, causal, p, scale, window, softcap, docs, sinks)
+        return _attention_dims(q, k, v, causal, p, scale, window, softcap, docs, sinks, k_rope)
     plan = _plan(q.dtype, S, D, causal, scale, generic=_is_generic(window, softcap, docs, sinks), softcap=softcap,
                  sinks=sinks is not None) if q.is_cuda else None
     if plan is None:

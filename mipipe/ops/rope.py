@@ -17,6 +17,12 @@ last ``n_copy`` through" on ``[B, S, n_rot + n_copy, D]``: the layout above is
 ``(2H, H)``, and a grouped-query projection ``[B, S, H + 2 Hkv, D]`` (Q heads,
 then ``Hkv`` K heads, then ``Hkv`` V heads) is ``(H + Hkv, Hkv)``
 (:func:`rope_heads`, ``rope_projection(..., n_kv_heads=Hkv)``).
+
+Multi-head latent attention rotates a slice, not whole heads (:func:`mla_rope`,
+kernel ``mla_rope`` of the same file): the last ``R`` features of every
+``Dn + R``-wide query head, and the ``R`` columns behind the ``Lkv`` latent
+columns of the down-projection, which become the one key head every query head
+shares.  The pair is ``(i, i + R/2)`` inside the slice, as above.
 """
 from __future__ import annotations
 
@@ -27,7 +33,8 @@ from torch import Tensor
 
 from ._util import kernels_for
 
-__all__ = ["rope_tables", "rope_packed", "rope_heads", "rope_projection", "rope_reference"]
+__all__ = ["rope_tables", "rope_packed", "rope_heads", "rope_projection", "rope_reference", "mla_rope",
+           "mla_rope_reference"]
 
 
 def rope_tables(max_len: int, head_dim: int, base: float = 10000.0, device=None) -> Tuple[Tensor, Tensor]:
@@ -194,3 +201,81 @@ def rope_projection(proj: Tensor, cos: Tensor, sin: Tensor, nhead: int, pos0: in
         return rope_reference(proj.view(shape5), cos, sin, pos0)
     inplace = proj.is_contiguous() and not (torch.is_grad_enabled() and proj.requires_grad)
     return _RopePacked.apply(proj.contiguous(), cos, sin, int(pos0), inplace, shape5).view(shape5)
+
+
+def mla_rope_reference(q: Tensor, ckv: Tensor, cos: Tensor, sin: Tensor, inverse: bool = False) -> Tuple[Tensor, Tensor]:
+    """Eager :func:`mla_rope` (CPU path and test oracle); the arithmetic runs in the wider of q's and the tables'
+    dtypes."""
+    S, half = q.shape[1], cos.shape[1]
+    R = 2 * half
+    wide = torch.promote_types(q.dtype, cos.dtype)
+    c, s = cos[:S].to(wide), sin[:S].to(wide)
+    if inverse:
+        s = -s
+
+    def rot(x, c, s):
+        a, b = x[..., :half].to(wide), x[..., half:].to(wide)
+        return torch.cat((a * c - b * s, b * c + a * s), dim=-1).to(x.dtype)
+
+    q_out = torch.cat((q[..., :-R], rot(q[..., -R:], c[:, None], s[:, None])), dim=-1)
+    return q_out, rot(ckv[..., -R:], c, s)
+
+
+class _MlaRope(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, q, ckv, cos, sin, inplace):  # type: ignore[override]
+        ctx.save_for_backward(cos, sin)
+        ctx.ckv_shape = ckv.shape
+        if inplace:
+            ctx.mark_dirty(q)
+        q_out, k_rope = kernels_for(q).mla_rope_fwd(q, ckv, cos, sin, q if inplace else None)
+        return (q if inplace else q_out), k_rope
+
+    @staticmethod
+    def backward(ctx, dq, dk_rope):  # type: ignore[override]
+        cos, sin = ctx.saved_tensors
+        # a gradient autograd handed over as it is may be shared with another consumer: only a copy made here is
+        # rotated in its own storage
+        own = not dq.is_contiguous()
+        dq = dq.contiguous()
+        dckv = dq.new_zeros(ctx.ckv_shape)  # the latent columns get no gradient from here
+        dq = kernels_for(dq).mla_rope_bwd(dq, dk_rope.contiguous(), cos, sin, dckv, dq if own else None)
+        return dq, dckv, None, None, None
+
+
+_mla_noted = set()
+
+
+def mla_rope(q: Tensor, ckv: Tensor, cos: Tensor, sin: Tensor) -> Tuple[Tensor, Tensor]:
+    """Multi-head latent attention's decoupled RoPE: ``q [B, S, H, Dn + R]`` and ``ckv [B, S, Lkv + R]`` (both
+    contiguous) -> ``(q', k_rope)``: ``q`` with the last ``R`` features of every head rotated and a new contiguous
+    ``k_rope [B, S, R]``, the rotated last ``R`` columns of ``ckv``.  ``cos`` / ``sin``: fp32 ``[>= S, R / 2]``
+    (:func:`rope_tables` ``(S, R, base)``); positions ``0 .. S - 1``.
+
+    One kernel launch does both rotations.  ``q`` is rotated in its own storage when no graph is being recorded and
+    into a new tensor (nope features copied) under autograd -- :func:`rope_projection`'s rule, with the same bits
+    either way.  The backward is the inverse rotation; ``ckv``'s gradient is zero in its ``Lkv`` latent columns.
+    ``R`` in {32, 64} and ``Dn``, ``Lkv`` multiples of 8 run the kernel; the CPU and any other shape run
+    :func:`mla_rope_reference` (noted once per shape on the GPU)."""
+    if q.dim() != 4 or ckv.dim() != 3 or cos.dim() != 2 or cos.shape != sin.shape or ckv.shape[:2] != q.shape[:2]:
+        raise ValueError(f"mla_rope: q must be [B, S, H, Dn + R] and ckv [B, S, Lkv + R] with cos / sin [>= S, R / 2], "
+                         f"got {tuple(q.shape)}, {tuple(ckv.shape)}, {tuple(cos.shape)}")
+    R = 2 * cos.shape[1]
+    Dn, Lkv = q.shape[3] - R, ckv.shape[2] - R
+    if Dn < 0 or Lkv < 0 or cos.shape[0] < q.shape[1]:
+        raise ValueError(f"mla_rope: R={R} from the tables does not fit q {tuple(q.shape)}, ckv {tuple(ckv.shape)} "
+                         f"or the tables are shorter than S")
+    if not q.is_cuda:
+        return mla_rope_reference(q, ckv, cos, sin)
+    if R not in (32, 64) or Dn % 8 or Lkv % 8 or q.dtype not in (torch.bfloat16, torch.float32) or ckv.dtype != q.dtype:
+        key = (Dn, R, Lkv, q.dtype)
+        if key not in _mla_noted:
+            _mla_noted.add(key)
+            import warnings
+
+            warnings.warn(f"mipipe mla_rope: Dn={Dn} R={R} Lkv={Lkv} {q.dtype} runs the eager path (HIP kernel: bf16 "
+                          "or fp32, R in {32, 64}, Dn and Lkv multiples of 8)", stacklevel=2)
+        return mla_rope_reference(q, ckv, cos, sin)
+    graph = torch.is_grad_enabled() and (q.requires_grad or ckv.requires_grad)
+    inplace = q.is_contiguous() and not graph
+    return _MlaRope.apply(q.contiguous(), ckv.contiguous(), cos, sin, inplace)

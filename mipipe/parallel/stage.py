@@ -70,6 +70,8 @@ def block_costs(cfg: LMConfig, split_decoder: bool = False) -> List[float]:
         keys = (w * (w + 1) / 2 + (s - w) * w) / s if w is not None and w < s else s * (0.5 if cfg.causal else 1.0)
         # the QKV projection is (H + 2 Hkv) D wide (3 e without grouped-query attention), the scores and the
         # weighted sum H D = A wide (e unless the head dim is the config's own)
+        if cfg.mla is not None:  # the latent projections; scores Dn + R and weighted sum Dv wide (LatentAttentionCore)
+            return 3.0 * (2 * cfg.attn_proj_params() + 4 * keys * cfg.attn_work_dim()) + 3.0 * 10 * e
         return 3.0 * (2 * cfg.qkv_dim() * e + 4 * keys * cfg.attn_dim()) + 3.0 * 10 * e
 
     out = 3.0 * (2 * e * cfg.attn_dim()) + 3.0 * 10 * e  # + LN/dropout traffic
