@@ -1880,6 +1880,30 @@ void fill_options(AttnArgs& a, const char* who, const Tensor& q, bool causal, in
   a.kv_len = (int)kv_len;
 }
 
+// What a forward makes itself, under the device guard, filled into `a` (AttnArgs or AttnMlaArgs, after its
+// fill_*): o [B, S, H, Dv], lse [B, H, S] in fp32 and the Philox draw (none at p == 0).  Returns (o, lse).
+template <typename Args>
+std::pair<Tensor, Tensor> attn_fwd_out(Args& a, const Tensor& q, int64_t Dv, double p) {
+  auto o = at::empty({a.B, a.S, a.H, Dv}, q.options());
+  auto lse = at::empty({a.B, a.H, a.S}, q.options().dtype(at::kFloat));
+  if (p > 0.0) std::tie(a.seed, a.offset) = philox_draw(q.device(), 4);
+  a.o = o.data_ptr(); a.lse = ptr<float>(lse);
+  return {o, lse};
+}
+
+// What a backward makes itself, under the device guard, filled into `a` with the forward's draw: delta [B, H, S]
+// in fp32, once `lse` is seen to be what the forward returned.  Returns delta.
+template <typename Args>
+Tensor attn_bwd_delta(Args& a, const char* who, const Tensor& lse, const Tensor& q, int64_t seed, int64_t offset) {
+  MP_CHECK(lse.is_cuda() && lse.device() == q.device() && lse.scalar_type() == at::kFloat && lse.is_contiguous() &&
+               lse.dim() == 3 && lse.size(0) == a.B && lse.size(1) == a.H && lse.size(2) == a.S,
+           who, ": lse must be the forward's contiguous fp32 [B, H, S]");
+  auto delta = at::empty({a.B, a.H, a.S}, q.options().dtype(at::kFloat));
+  a.lse = ptr<float>(lse); a.delta = ptr<float>(delta);
+  a.seed = (uint64_t)seed; a.offset = (uint64_t)offset;
+  return delta;
+}
+
 // Returns (o, lse, seed, offset, dropout keep bits): the bits tensor (int32
 // [B*H, S/32, S]) is non-empty only for the long-sequence kernels with p > 0
 // and must be handed back to attention_bwd.  A windowed call (0 < window < S) or a soft-capped one returns none.
@@ -1896,13 +1920,9 @@ std::tuple<Tensor, Tensor, int64_t, int64_t, Tensor> py_attention_fwd(Tensor q, 
   fill_options(a, "attention", q, causal, kv_len, window, softcap, doc_bounds, sinks);
   MP_CHECK(p >= 0.0 && p < 1.0, "attention: bad dropout p");
   at::hip::HIPGuardMasqueradingAsCUDA guard(q.device());
-  auto o = at::empty({a.B, a.S, a.H, a.D}, q.options());
-  auto lse = at::empty({a.B, a.H, a.S}, q.options().dtype(at::kFloat));
-  uint64_t seed = 0, offset = 0;
-  if (p > 0.0) std::tie(seed, offset) = philox_draw(q.device(), 4);
-  a.o = o.data_ptr(); a.sb_o = o.stride(0); a.ld_o = o.stride(1); a.sh_o = o.stride(2);
-  a.lse = ptr<float>(lse);
-  a.scale = (float)scale; a.p = (float)p; a.seed = seed; a.offset = offset; a.causal = causal;
+  const auto [o, lse] = attn_fwd_out(a, q, a.D, p);
+  a.sb_o = o.stride(0); a.ld_o = o.stride(1); a.sh_o = o.stride(2);
+  a.scale = (float)scale; a.p = (float)p; a.causal = causal;
   Tensor bits = at::empty({0}, q.options().dtype(at::kInt));
   if (q.scalar_type() == at::kFloat) {
     attention_f32_fwd(a, cur_stream(q));
@@ -1912,7 +1932,7 @@ std::tuple<Tensor, Tensor, int64_t, int64_t, Tensor> py_attention_fwd(Tensor q, 
       const std::vector<int64_t> shape = {(int64_t)a.B * a.H, a.S / 32, a.S};
       reuse = words && words->defined() && words->sizes() == at::IntArrayRef(shape) &&
               words->scalar_type() == at::kInt && words->is_contiguous() && words->device() == q.device() &&
-              (uint64_t)words_seed == seed && (uint64_t)words_offset == offset;
+              (uint64_t)words_seed == a.seed && (uint64_t)words_offset == a.offset;
       bits = reuse ? *words : at::empty(shape, q.options().dtype(at::kInt));
       a.dmask = reinterpret_cast<uint32_t*>(bits.data_ptr());
     }
@@ -1921,7 +1941,7 @@ std::tuple<Tensor, Tensor, int64_t, int64_t, Tensor> py_attention_fwd(Tensor q, 
   } else {
     attention_fwd(a, cur_stream(q));
   }
-  return {o, lse, (int64_t)seed, (int64_t)offset, bits};
+  return {o, lse, (int64_t)a.seed, (int64_t)a.offset, bits};
 }
 
 void py_attention_bwd(Tensor dout, Tensor q, Tensor k, Tensor v, Tensor o, Tensor lse, bool causal, double p,
@@ -1949,9 +1969,8 @@ void py_attention_bwd(Tensor dout, Tensor q, Tensor k, Tensor v, Tensor o, Tenso
   MP_CHECK(dq.sizes() == q.sizes() && dk.sizes() == k.sizes() && dv.sizes() == k.sizes() &&
                dk.scalar_type() == q.scalar_type() && dv.scalar_type() == q.scalar_type(),
            "attention_bwd: gradient buffers must have q's / k's / v's shapes and dtype");
-  MP_CHECK(lse.scalar_type() == at::kFloat && lse.numel() == (int64_t)a.B * a.H * a.S, "attention_bwd: bad lse");
   at::hip::HIPGuardMasqueradingAsCUDA guard(q.device());
-  auto delta = at::empty({a.B, a.H, a.S}, q.options().dtype(at::kFloat));
+  auto delta = attn_bwd_delta(a, "attention_bwd", lse, q, seed, offset);
   a.o = o.data_ptr(); a.dout = dout.data_ptr();
   a.sb_o = o.stride(0); a.ld_o = o.stride(1); a.sh_o = o.stride(2);
   a.dq = dq.data_ptr(); a.dk = dk.data_ptr(); a.dv = dv.data_ptr();
@@ -1973,8 +1992,7 @@ void py_attention_bwd(Tensor dout, Tensor q, Tensor k, Tensor v, Tensor o, Tenso
     a.dv = static_cast<char*>(dkv.data_ptr()) + (int64_t)a.H * a.D * es;
     a.sb_dkv = dkv.stride(0); a.ld_dkv = dkv.stride(1); a.sh_dkv = dkv.stride(3);
   }
-  a.lse = ptr<float>(lse); a.delta = ptr<float>(delta);
-  a.scale = (float)scale; a.p = (float)p; a.seed = (uint64_t)seed; a.offset = (uint64_t)offset; a.causal = causal;
+  a.scale = (float)scale; a.p = (float)p; a.causal = causal;
   if (q.scalar_type() == at::kFloat) {
     attention_f32_bwd(a, cur_stream(q));
   } else if (runs_long(a, q)) {
@@ -2057,23 +2075,18 @@ void fill_mla(AttnMlaArgs& a, const Tensor& q, const Tensor& k, const Tensor& v,
   a.scale = (float)scale; a.p = (float)p; a.causal = causal;
 }
 
-// Returns (o [B, S, H, Dv], lse [B, H, S], seed, offset); the Philox draw is py_attention_fwd's.  k_rope [B, S, 64]:
+// Returns (o [B, S, H, Dv], lse [B, H, S], seed, offset).  k_rope [B, S, 64]:
 // k is the 128-wide nope part and every head's rotary key columns are that one head, read in place.
 std::tuple<Tensor, Tensor, int64_t, int64_t> py_attention_mla_fwd(Tensor q, Tensor k, Tensor v, bool causal, double p,
                                                                   double scale, std::optional<Tensor> k_rope) {
   AttnMlaArgs a;
   fill_mla(a, q, k, v, k_rope, causal, p, scale);
   at::hip::HIPGuardMasqueradingAsCUDA guard(q.device());
-  auto o = at::empty({a.B, a.S, a.H, a.Dv}, q.options());
-  auto lse = at::empty({a.B, a.H, a.S}, q.options().dtype(at::kFloat));
-  uint64_t seed = 0, offset = 0;
-  if (p > 0.0) std::tie(seed, offset) = philox_draw(q.device(), 4);
-  a.o = o.data_ptr(); a.so = bshd_strides(o);
-  a.lse = ptr<float>(lse);
-  a.seed = seed; a.offset = offset;
+  const auto [o, lse] = attn_fwd_out(a, q, a.Dv, p);
+  a.so = bshd_strides(o);
   const char* why = attention_mla_fwd(a, cur_stream(q));
   MP_CHECK(why == nullptr, "attention_mla: ", why);
-  return {o, lse, (int64_t)seed, (int64_t)offset};
+  return {o, lse, (int64_t)a.seed, (int64_t)a.offset};
 }
 
 // With k_rope, dk is the nope gradient [B, S, H, 128] and dk_rope [B, S, 64] the head-summed rope gradient; the
@@ -2089,11 +2102,8 @@ void py_attention_mla_bwd(Tensor dout, Tensor q, Tensor k, Tensor v, Tensor o, T
   check_mla(dq, "dq", q, a.Dqk);
   check_mla(dk, "dk", q, k.size(3));
   check_mla(dv, "dv", q, a.Dv);
-  MP_CHECK(lse.is_cuda() && lse.device() == q.device() && lse.scalar_type() == at::kFloat && lse.is_contiguous() &&
-               lse.dim() == 3 && lse.size(0) == a.B && lse.size(1) == a.H && lse.size(2) == a.S,
-           "attention_mla_bwd: lse must be the forward's contiguous fp32 [B, H, S]");
   at::hip::HIPGuardMasqueradingAsCUDA guard(q.device());
-  auto delta = at::empty({a.B, a.H, a.S}, q.options().dtype(at::kFloat));
+  auto delta = attn_bwd_delta(a, "attention_mla_bwd", lse, q, seed, offset);
   Tensor part;
   if (dk_rope.has_value()) {
     check_mla_rope(*dk_rope, "dk_rope", q);
@@ -2107,8 +2117,6 @@ void py_attention_mla_bwd(Tensor dout, Tensor q, Tensor k, Tensor v, Tensor o, T
   a.dq = dq.data_ptr(); a.sdq = bshd_strides(dq);
   a.dk = dk.data_ptr(); a.sdk = bshd_strides(dk);
   a.dv = dv.data_ptr(); a.sdv = bshd_strides(dv);
-  a.lse = ptr<float>(lse); a.delta = ptr<float>(delta);
-  a.seed = (uint64_t)seed; a.offset = (uint64_t)offset;
   const char* why = attention_mla_bwd(a, cur_stream(q));
   MP_CHECK(why == nullptr, "attention_mla_bwd: ", why);
 }

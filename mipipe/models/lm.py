@@ -23,7 +23,7 @@ from .. import ops
 from ..ops.linear import mark_gemm_weight
 from ..ops.softcap import softcap_owned
 from .transformer import (GATED_ACTS, FeedForwardBlock, MLADims, check_expert_gemm, check_global_every, check_mla,
-                          layer_window, transformer_blocks)
+                          check_positive, layer_window, transformer_blocks)
 
 __all__ = [
     "Encoder",
@@ -142,12 +142,7 @@ class Decoder(nn.Module):
         super().__init__()
         fk = {"device": device, "dtype": dtype}
         self.ntoken = ntoken
-        if final_softcap is not None:
-            if (isinstance(final_softcap, bool) or not isinstance(final_softcap, (int, float))
-                    or not math.isfinite(final_softcap) or final_softcap <= 0):
-                raise ValueError(f"final_softcap must be a finite number > 0 or None, got {final_softcap!r}")
-            final_softcap = float(final_softcap)
-        self.final_softcap = final_softcap
+        self.final_softcap = check_positive("final_softcap", final_softcap)
         self.padded = (ntoken + pad_to - 1) // pad_to * pad_to
         self.weight = mark_gemm_weight(nn.Parameter(torch.empty(self.padded, d_model, **fk)))
         self.bias = nn.Parameter(torch.zeros(self.padded, **fk))

@@ -153,6 +153,23 @@ def _norm_fanout(mod: nn.Module, x: Tensor):
     return ops.layer_norm_fanout(x, mod.norm_weight, mod.norm_bias, mod.eps)
 
 
+def check_positive(name: str, value) -> Optional[float]:
+    """The option ``name`` validated: ``None`` (not set) or a finite number > 0, returned as a float."""
+    if value is None:
+        return None
+    if isinstance(value, bool) or not isinstance(value, (int, float)) or not math.isfinite(value) or value <= 0:
+        raise ValueError(f"{name} must be a finite number > 0 or None, got {value!r}")
+    return float(value)
+
+
+def _rope_tables(mod: nn.Module, seq_len: int, dim: int, device):
+    """``mod``'s cos / sin buffers for ``seq_len`` positions of a ``dim``-wide rotary head: rebuilt when too short,
+    on another device, or cast by a module-wide ``.to(dtype)`` (the kernel reads fp32)."""
+    if mod.rope_cos.shape[0] < seq_len or mod.rope_cos.device != device or mod.rope_cos.dtype != torch.float32:
+        mod.rope_cos, mod.rope_sin = ops.rope_tables(seq_len, dim, mod.rope_base, device=device)
+    return mod.rope_cos, mod.rope_sin
+
+
 __all__ = [
     "AttentionCore",
     "LatentAttentionCore",
@@ -194,18 +211,8 @@ class AttentionCore(nn.Module):
             raise ValueError(f"head_dim must be an int >= 1 or None, got {head_dim!r}")
         self.d_model, self.nhead, self.head_dim = d_model, nhead, head_dim
         self.attn_dim = nhead * head_dim  # width of o: d_model unless head_dim is given
-        if attn_scale is not None:
-            if (isinstance(attn_scale, bool) or not isinstance(attn_scale, (int, float))
-                    or not math.isfinite(attn_scale) or attn_scale <= 0):
-                raise ValueError(f"attn_scale must be a finite number > 0 or None, got {attn_scale!r}")
-            attn_scale = float(attn_scale)
-        self.attn_scale = attn_scale  # None: the ops' own 1 / sqrt(head_dim)
-        if attn_softcap is not None:
-            if (isinstance(attn_softcap, bool) or not isinstance(attn_softcap, (int, float))
-                    or not math.isfinite(attn_softcap) or attn_softcap <= 0):
-                raise ValueError(f"attn_softcap must be a finite number > 0 or None, got {attn_softcap!r}")
-            attn_softcap = float(attn_softcap)
-        self.attn_softcap = attn_softcap
+        self.attn_scale = check_positive("attn_scale", attn_scale)  # None: the ops' own 1 / sqrt(head_dim)
+        self.attn_softcap = check_positive("attn_softcap", attn_softcap)
         if window is not None:
             if isinstance(window, bool) or not isinstance(window, int) or window < 1:
                 raise ValueError(f"window must be an int >= 1 or None, got {window!r}")
@@ -256,14 +263,6 @@ class AttentionCore(nn.Module):
         if self.attn_sinks:
             nn.init.zeros_(self.sinks)
 
-    def _rope_tables(self, seq_len: int, device):
-        # rebuilt when too short, on another device, or cast by a module-wide .to(dtype): the kernel reads fp32
-        if (self.rope_cos.shape[0] < seq_len or self.rope_cos.device != device
-                or self.rope_cos.dtype != torch.float32):
-            cos, sin = ops.rope_tables(seq_len, self.head_dim, self.rope_base, device=device)
-            self.rope_cos, self.rope_sin = cos, sin
-        return self.rope_cos, self.rope_sin
-
     def forward(self, x: Tensor) -> Tensor:
         return self.forward_fanout(x, fanout=False)[0]
 
@@ -302,44 +301,22 @@ class AttentionCore(nn.Module):
             qkv, xr = ops.linear_fanout(x, self.in_proj_weight, self.in_proj_bias)
         else:
             qkv = ops.linear(x, self.in_proj_weight, self.in_proj_bias)
-        # The projection output viewed as [B, S, 3, H, D] feeds the kernel in
-        # place; its output [B, S, H, D] is already [B, S, E] -- no transposes.
+        # The projection output viewed as [B, S, H + 2 Hkv, D] feeds the kernel in place -- the K/V heads read by
+        # every query head of their group; Hkv == H is [B, S, 3, H, D] byte for byte -- and its output [B, S, H, D]
+        # is already [B, S, E]: no transposes.
         Hkv = self.n_kv_heads
+        cos, sin = _rope_tables(self, S, D, qkv.device) if self.rope else (None, None)
         if self.qk_norm:
             # Q and K heads normalised (and rotated, with rope) in one pass: where rope_projection runs otherwise
-            cos, sin = self._rope_tables(S, qkv.device) if self.rope else (None, None)
-            qkv_n = ops.qk_norm_rope_projection(qkv, self.q_norm_weight, self.k_norm_weight, self.eps, cos, sin, H,
-                                                n_kv_heads=Hkv)
-            if Hkv != H:
-                o = ops.attention_gqa_packed(qkv_n, Hkv, causal=self.causal, dropout_p=self.dropout,
-                                             training=self.training, scale=self.attn_scale, window=self.window,
-                                             softcap=self.attn_softcap, doc_bounds=docs, sinks=sinks)
-            else:
-                o = ops.attention_packed(qkv_n, causal=self.causal, dropout_p=self.dropout, training=self.training,
-                                         scale=self.attn_scale, window=self.window, softcap=self.attn_softcap,
-                                         doc_bounds=docs, sinks=sinks)
-            return o.reshape(B, S, E), xr
-        if Hkv != H:
-            # grouped-query attention: [B, S, H + 2 Hkv, D], the K/V heads read in place by every query head
-            # of their group
-            if self.rope:
-                cos, sin = self._rope_tables(S, qkv.device)
-                qkv4 = ops.rope_projection(qkv, cos, sin, H, n_kv_heads=Hkv)
-            else:
-                qkv4 = qkv.view(B, S, H + 2 * Hkv, D)
-            o = ops.attention_gqa_packed(qkv4, Hkv, causal=self.causal, dropout_p=self.dropout,
-                                         training=self.training, scale=self.attn_scale, window=self.window,
-                                         softcap=self.attn_softcap, doc_bounds=docs, sinks=sinks)
-            return o.reshape(B, S, E), xr
-        if self.rope:
+            qkv = ops.qk_norm_rope_projection(qkv, self.q_norm_weight, self.k_norm_weight, self.eps, cos, sin, H,
+                                              n_kv_heads=Hkv)
+        elif self.rope:
             # Q and K rotated: in the projection's own output where no graph is recorded, else into a new tensor
-            cos, sin = self._rope_tables(S, qkv.device)
-            qkv5 = ops.rope_projection(qkv, cos, sin, H)
-        else:
-            qkv5 = qkv.view(B, S, 3, H, D)
-        o = ops.attention_packed(qkv5, causal=self.causal, dropout_p=self.dropout, training=self.training,
-                                 scale=self.attn_scale, window=self.window, softcap=self.attn_softcap,
-                                 doc_bounds=docs, sinks=sinks)
+            qkv = ops.rope_projection(qkv, cos, sin, H, n_kv_heads=Hkv)
+        # (both ops return [B, S, 3, H, D] for Hkv == H: the reshape is a view)
+        o = ops.attention_gqa_packed(qkv.reshape(B, S, H + 2 * Hkv, D), Hkv, causal=self.causal,
+                                     dropout_p=self.dropout, training=self.training, scale=self.attn_scale,
+                                     window=self.window, softcap=self.attn_softcap, doc_bounds=docs, sinks=sinks)
         return o.reshape(B, S, E), xr
 
     def flops_per_token(self, seq_len: int) -> float:
@@ -422,12 +399,7 @@ class LatentAttentionCore(nn.Module):
         fk = {"device": device, "dtype": dtype}
         self.d_model, self.nhead, self.mla = d_model, nhead, mla
         self.attn_dim = nhead * mla.v_dim
-        if attn_scale is not None:
-            if (isinstance(attn_scale, bool) or not isinstance(attn_scale, (int, float))
-                    or not math.isfinite(attn_scale) or attn_scale <= 0):
-                raise ValueError(f"attn_scale must be a finite number > 0 or None, got {attn_scale!r}")
-            attn_scale = float(attn_scale)
-        self.attn_scale = attn_scale  # None: the op's own 1 / sqrt(nope_dim + rope_dim)
+        self.attn_scale = check_positive("attn_scale", attn_scale)  # None: the op's own 1 / sqrt(nope_dim + rope_dim)
         self.dropout, self.norm_first, self.causal, self.eps = dropout, norm_first, causal, layer_norm_eps
         self.norm, self.rope_base = norm, rope_base
         weight = lambda *shape: mark_gemm_weight(nn.Parameter(torch.empty(*shape, **fk)))  # noqa: E731
@@ -457,12 +429,6 @@ class LatentAttentionCore(nn.Module):
         if self.norm_first:
             _reset_norm(self)
 
-    def _rope_tables(self, seq_len: int, device):
-        if (self.rope_cos.shape[0] < seq_len or self.rope_cos.device != device
-                or self.rope_cos.dtype != torch.float32):
-            self.rope_cos, self.rope_sin = ops.rope_tables(seq_len, self.mla.rope_dim, self.rope_base, device=device)
-        return self.rope_cos, self.rope_sin
-
     def forward(self, x: Tensor) -> Tensor:
         return self.forward_fanout(x, fanout=False)[0]
 
@@ -487,7 +453,7 @@ class LatentAttentionCore(nn.Module):
             cq = ops.add_dropout_rms_norm(ops.linear(x, self.q_a_weight, None), None, self.q_norm_weight, self.eps,
                                           0.0, self.training)
             q = ops.linear(cq, self.q_b_weight, None)
-        cos, sin = self._rope_tables(S, x.device)
+        cos, sin = _rope_tables(self, S, m.rope_dim, x.device)
         q, k_rope = ops.mla_rope(q.view(B, S, H, m.nope_dim + m.rope_dim), ckv, cos, sin)
         # (the norm wants contiguous rows: fusing this split with it is a kernel of its own)
         c = ops.add_dropout_rms_norm(ckv[..., :m.kv_lora_rank].contiguous(), None, self.kv_norm_weight, self.eps, 0.0,

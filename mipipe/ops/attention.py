@@ -100,23 +100,20 @@ native, the non-causal key mask included (a padded key still underflows against
 a running max the sink can only raise), unless there is a cap as well.
 
 Separate QK and V head dims: :func:`attention` takes a ``v`` whose head dim
-differs from ``q``'s and ``k``'s.  bf16 with dims (192, 128) -- multi-head latent
-attention as DeepSeek-V2 / V3 train it -- runs csrc/kernels/attention_mla.hip at
-``S % 64 == 0``, and causal at any other length by end padding; every operand is
-read with its own strides.  None of the options above is native there, nor is
-fp32 or another dim pair: those run :func:`attention_reference`.
+differs from ``q``'s and ``k``'s -- multi-head latent attention as DeepSeek-V2 /
+V3 train it.  The kernels are csrc/kernels/attention_mla.hip (``_plan``'s last
+row); every operand is read with its own strides.
 
 Shared rope key head, ``k_rope`` -- ``[B, S, R]``, with ``k [B, H, S, D - R]`` the
 "nope" features: multi-head latent attention's keys are ``cat(k[:, h], k_rope)``
-for every head ``h``, one rotary head shared by all of them.  The native path
-(bf16, dims (128 + 64, 128), the lengths above, none of the options, K/V heads
-equal to the query heads) runs attention_mla.hip's SHARED kernels, which read
-``k_rope`` in place -- nothing is repeated or concatenated -- and give the bits
-of the call on the hand-concatenated K; ``dk_rope`` is the fixed-order fp32 sum
-of the heads' partials (a scratch of ``256 H`` bytes per token for the call),
-rounded once.  ``k`` and ``v`` may be the two halves of one ``[B, S, H, 256]``
-up-projection output.  Everything else concatenates and runs as it would
-without ``k_rope``, autograd summing the heads.
+for every head ``h``, one rotary head shared by all of them.  On that row of the
+plan attention_mla.hip's SHARED kernels read ``k_rope`` in place -- nothing is
+repeated or concatenated -- and give the bits of the call on the
+hand-concatenated K; ``dk_rope`` is the fixed-order fp32 sum of the heads'
+partials (a scratch of ``256 H`` bytes per token for the call), rounded once.
+``k`` and ``v`` may be the two halves of one ``[B, S, H, 256]`` up-projection
+output.  Everything else concatenates and runs as it would without ``k_rope``,
+autograd summing the heads.
 """
 from __future__ import annotations
 
@@ -426,44 +423,38 @@ class _Attention(torch.autograd.Function):
         return dq, dk, dv, None, None, None, None, None, None, None, dsinks
 
 
-def _strided_ok(t: Tensor) -> bool:
-    """``t [B, S, H, D]`` is readable in place by attention_mla.hip: unit stride on D, the other strides
-    non-negative multiples of 8 elements, a 16-byte aligned base."""
-    return (t.stride(3) == 1 and all(s >= 0 and s % 8 == 0 for s in t.stride()[:3])
-            and t.data_ptr() % 16 == 0)
-
-
-def _rope_ok(t: Tensor) -> bool:
-    """``k_rope [B, S, R]`` is readable in place: :func:`_strided_ok` without a head axis."""
-    return t.stride(2) == 1 and all(s >= 0 and s % 8 == 0 for s in t.stride()[:2]) and t.data_ptr() % 16 == 0
+def _in_place(t: Optional[Tensor]) -> Optional[Tensor]:
+    """``t`` (``[B, S, H, D]``, or ``k_rope [B, S, R]``; None passes) where attention_mla.hip can read it in place,
+    a contiguous copy otherwise.  Mirrors ``check_mla`` (on ``check_bshd``) and ``check_mla_rope`` in bindings.cpp:
+    unit stride on the last axis, every leading stride a non-negative multiple of 8 elements (16 bytes of bf16), a
+    16-byte aligned base."""
+    if t is None or (t.stride(-1) == 1 and all(s >= 0 and s % 8 == 0 for s in t.stride()[:-1])
+                     and t.data_ptr() % 16 == 0):
+        return t
+    return t.contiguous()
 
 
 class _AttentionDims(torch.autograd.Function):
     """``q, k [B, S, H, Dqk]`` and ``v [B, S, H, Dv]`` with ``Dv != Dqk`` in, ``o [B, S, H, Dv]`` out
-    (attention_mla.hip).  Each operand keeps its own strides; the gradients are fresh contiguous buffers.  With
-    ``k_rope [B, S, 64]`` (the shared rope key head) ``k`` is the nope part ``[B, S, H, Dqk - 64]``, nothing is
-    concatenated, and ``dk_rope`` comes back summed over the heads."""
+    (attention_mla.hip).  It stands beside :func:`_forward` / :func:`_backward` for what their binding does not
+    take: each operand, ``do`` included, keeps its own strides (the gradients are fresh contiguous buffers), and
+    with ``k_rope [B, S, 64]`` (the shared rope key head) ``k`` is the nope part ``[B, S, H, Dqk - 64]``, nothing is
+    concatenated, and ``dk_rope`` comes back summed over the heads.  No options, no keep words."""
 
     @staticmethod
     def forward(ctx, q, k, v, causal, p, scale, k_rope=None):  # type: ignore[override]
-        q, k, v = (t if _strided_ok(t) else t.contiguous() for t in (q, k, v))
-        if k_rope is not None and not _rope_ok(k_rope):
-            k_rope = k_rope.contiguous()
+        q, k, v, k_rope = (_in_place(t) for t in (q, k, v, k_rope))
         o, lse, seed, offset = kernels_for(q).attention_mla_fwd(q, k, v, causal, p, scale, k_rope)
-        ctx.save_for_backward(q, k, v, o, lse, k_rope)
+        ctx.save_for_backward(q, k, v, k_rope, o, lse)
         ctx.scalars = (causal, p, scale, seed, offset)
         return o
 
     @staticmethod
     def backward(ctx, do):  # type: ignore[override]
-        q, k, v, o, lse, k_rope = ctx.saved_tensors
-        causal, p, scale, seed, offset = ctx.scalars
-        if not _strided_ok(do):
-            do = do.contiguous()
-        dq, dk, dv = (torch.empty(t.shape, dtype=t.dtype, device=t.device) for t in (q, k, v))
-        dk_rope = None if k_rope is None else torch.empty(k_rope.shape, dtype=k_rope.dtype, device=k_rope.device)
-        kernels_for(do).attention_mla_bwd(do, q, k, v, o, lse, causal, p, scale, seed, offset, dq, dk, dv, k_rope,
-                                          dk_rope)
+        q, k, v, k_rope, o, lse = ctx.saved_tensors
+        dq, dk, dv, dk_rope = (None if t is None else torch.empty(t.shape, dtype=t.dtype, device=t.device)
+                               for t in (q, k, v, k_rope))
+        kernels_for(do).attention_mla_bwd(_in_place(do), q, k, v, o, lse, *ctx.scalars, dq, dk, dv, k_rope, dk_rope)
         return dq, dk, dv, None, None, None, dk_rope
 
 
@@ -471,10 +462,15 @@ _noted = set()
 
 
 def _note_math_path(S: int, D: int, dtype, window: Optional[int] = None, softcap: Optional[float] = None,
-                    docs: bool = False, sinks: bool = False, stacklevel: int = 3) -> None:
-    """Shapes outside the kernels' tiling use the eager math path; say so once per shape."""
+                    docs: bool = False, sinks: bool = False, Dv: Optional[int] = None, rope: int = 0,
+                    stacklevel: int = 3) -> None:
+    """Shapes outside the kernels' tiling use the eager math path; say so once per shape.  ``Dv``: v's head dim
+    where it differs from ``D``, ``rope``: the width of the call's ``k_rope`` (0: none)."""
     # (set, key tag, the call's words, the warning's tail) per option, in the key's order
     notes = [
+        (Dv not in (None, D), ("dims", Dv, rope), f" Dv={Dv}" + (f" k_rope={rope}" if rope else ""),
+         ".  A V head dim of its own is native in bf16 only, for head dims (192, 128) (k_rope: 128 + 64) with S % "
+         "64 == 0 or causal, and with no window, cap, document bounds or sinks"),
         (window is not None, "window", f" window={window}",
          ".  fp32 sliding-window attention is not native: the window runs on the bf16 kernels only"),
         (softcap is not None, "softcap", f" softcap={softcap}",
@@ -517,9 +513,11 @@ _KEY_MASK = -32768.0  # exact in bf16; times the query's 1 and any scale >= 2^-8
 
 
 def _plan(dtype: torch.dtype, S: int, D: int, causal: bool, scale: float, *, generic: bool,
-          softcap: Optional[float], sinks: bool) -> Optional[Tuple[int, int, int, bool]]:
+          softcap: Optional[float], sinks: bool, Dv: Optional[int] = None,
+          rope: int = 0) -> Optional[Tuple[int, int, int, bool]]:
     """``(sp, dp, kv_len, key_mask)`` a GPU call of (S, D) runs at on the kernels, or None (the eager path).
-    ``generic``: the call has a window ``< S``, a cap, document bounds or sinks.  ``sp`` / ``dp`` are the padded
+    ``generic``: the call has a window ``< S``, a cap, document bounds or sinks.  ``Dv``: v's head dim (None: ``D``),
+    ``rope``: the width of a ``k_rope`` that was not concatenated into k (0: none).  ``sp`` / ``dp`` are the padded
     sequence length and head dim, ``kv_len`` (0 = none) the key bound the fp32 kernels mask past themselves, and
     ``key_mask`` says that the caller masks the padded keys through the spare feature ``D`` (the module doc).
 
@@ -538,10 +536,21 @@ def _plan(dtype: torch.dtype, S: int, D: int, causal: bool, scale: float, *, gen
     generic with sinks    bf16 only; the plain answer, the key mask included unless there is a cap
                           (the sink only raises the row's running max, so a masked key underflows as
                           it does without one)
+    ``Dv != D``           bf16 only, not generic, ``rope`` 0 or 64 (attention_mla.hip): ``(S, D)`` where
+                          the extension tiles ``(S, D, Dv)`` as it is -- head dims (192, 128), ``S % 64
+                          == 0`` -- and, causal, end padding to the next multiple of 64.  No feature
+                          padding, key mask or key bound
     ====================  ===========================================================================
     """
     bf16 = dtype == torch.bfloat16
     if generic and not bf16:
+        return None
+    if Dv not in (None, D):
+        if generic or not bf16 or rope not in (0, 64):
+            return None
+        for sp in (S, -(-S // 64) * 64) if causal else (S,):
+            if kernels_for().attention_dims_supported(sp, D, Dv):
+                return sp, D, 0, False
         return None
     if _gpu_ok(dtype, S, D):
         return S, D, 0, False
@@ -574,8 +583,9 @@ def _pad_docs(docs: Tensor, S: int, sp: int) -> Tensor:
 
 
 def _run_padded(run, ts, seq: int, heads: int, S: int, D: int, sp: int, dp: int, key_mask) -> Tensor:
-    """``run(*ts)`` with every tensor of ``ts`` zero-padded to ``sp`` along axis ``seq`` and to ``dp`` along the
-    last, and the result (same axes) sliced back to ``S`` and ``D``.  ``key_mask``, where the plan asks for one:
+    """``run(*ts)`` with every tensor of ``ts`` zero-padded by ``sp - S`` along axis ``seq`` and by ``dp - D`` along
+    the last, and the result (same axes) sliced back to ``S`` and, where features were padded, to ``D`` (without:
+    the result's width is its own, v's under differing head dims).  ``key_mask``, where the plan asks for one:
     ``((i, h), (j, g))`` -- the queries are the heads ``h`` (a slice of axis ``heads``) of ``ts[i]``, the keys the
     heads ``g`` of ``ts[j]`` -- sets the spare feature ``D`` to 1 in every query and to -32768 in every padded key."""
     if (sp, dp) == (S, D):
@@ -592,7 +602,9 @@ def _run_padded(run, ts, seq: int, heads: int, S: int, D: int, sp: int, dp: int,
         for i, c in marks.items():
             ts[i] = ts[i] + c
     cut = [slice(None)] * 4
-    cut[seq], cut[-1] = slice(0, S), slice(0, D)
+    cut[seq] = slice(0, S)
+    if dp != D:
+        cut[-1] = slice(0, D)
     return run(*ts)[tuple(cut)]
 
 
@@ -684,41 +696,6 @@ def _cat_rope(k: Tensor, k_rope: Tensor) -> Tensor:
     return torch.cat((k, k_rope[:, None].expand(-1, k.shape[1], -1, -1)), dim=-1)
 
 
-def _attention_dims(q: Tensor, k: Tensor, v: Tensor, causal: bool, p: float, scale: float, window: Optional[int],
-                    softcap: Optional[float], docs: Optional[Tensor], sinks: Optional[Tensor],
-                    k_rope: Optional[Tensor] = None) -> Tensor:
-    """:func:`attention` where ``v``'s head dim differs from ``q``'s and ``k``'s (``[B, H, S, D]`` tensors with
-    equal head counts).  bf16 on the GPU with the dims attention_mla.hip tiles and no option runs its kernels, a
-    causal sequence off the 64-token tile zero-padded at the end (no real query sees a pad key); everything else
-    is :func:`attention_reference`, noted once per shape on the GPU.  ``k_rope [B, S, 64]``: ``k`` is the nope part
-    ``[B, H, S, D - 64]`` and the kernels read the shared rope head in place; the eager path concatenates."""
-    S, D, Dv = q.shape[2], q.shape[3], v.shape[3]
-    sp = None
-    if (q.is_cuda and q.dtype == torch.bfloat16 and not _is_generic(window, softcap, docs, sinks)
-            and (k_rope is None or k_rope.shape[-1] == 64)):
-        supported = kernels_for(q).attention_dims_supported
-        sp = next((s for s in ((S,) if not causal else (S, -(-S // 64) * 64)) if supported(s, D, Dv)), None)
-    if sp is None:
-        if q.is_cuda:
-            key = (S, D, Dv, q.dtype, window is not None, softcap is not None, docs is not None, sinks is not None)
-            if k_rope is not None:
-                key += (k_rope.shape[-1],)
-            if key not in _noted:
-                _noted.add(key)
-                import warnings
-
-                warnings.warn(f"mipipe attention: S={S} with head dims ({D}, {Dv}) {q.dtype} runs the eager math "
-                              "path (HIP kernels for differing head dims: bf16, (192, 128), S % 64 == 0 or causal, "
-                              "no window, cap, document bounds or sinks)", stacklevel=3)
-        return attention_reference(q, k, v, causal, p, scale, window=window, softcap=softcap, doc_bounds=docs,
-                                   sinks=sinks, k_rope=k_rope)
-    if sp != S:
-        q, k, v = (F.pad(t, (0, 0, 0, sp - S)) for t in (q, k, v))
-        k_rope = None if k_rope is None else F.pad(k_rope, (0, 0, 0, sp - S))
-    o = _AttentionDims.apply(q.transpose(1, 2), k.transpose(1, 2), v.transpose(1, 2), causal, p, scale, k_rope)
-    return o.transpose(1, 2)[:, :, :S]
-
-
 def _check_k_rope(q: Tensor, k: Tensor, k_rope: Tensor) -> None:
     """``k_rope [B, S, R]`` of q's dtype and device, with ``k`` the ``D - R`` features before it."""
     if not isinstance(k_rope, Tensor) or k_rope.dim() != 3 or k_rope.dtype != q.dtype or k_rope.device != q.device:
@@ -740,8 +717,8 @@ def attention(
     (grouped-query attention): separate tensors do not share q's strides, so their heads are repeated
     (autograd sums each group's gradient).  ``window``: sliding-window attention, ``softcap``: logit
     soft-capping, ``doc_bounds``: document masks, ``sinks``: attention sinks (module doc).  ``v`` may have a
-    head dim of its own, ``[B, H, S, Dv]`` -> ``[B, H, S, Dv]`` (multi-head latent attention's 192 / 128): see
-    :func:`_attention_dims`; the default ``scale`` stays ``1 / sqrt(D)`` of ``q``.  ``k_rope [B, S, R]`` is
+    head dim of its own, ``[B, H, S, Dv]`` -> ``[B, H, S, Dv]`` (multi-head latent attention's 192 / 128): the
+    last row of :func:`_plan`'s table; the default ``scale`` stays ``1 / sqrt(D)`` of ``q``.  ``k_rope [B, S, R]`` is
     multi-head latent attention's shared rotary key head: ``k`` is then ``[B, H, S, D - R]`` and every head's key
     is ``cat(k[:, h], k_rope)`` (module doc)."""
     if k_rope is not None:
@@ -761,27 +738,30 @@ def attention(
     softcap = _check_softcap(softcap)
     docs = _check_docs(doc_bounds, causal, B, S)
     sinks = _check_sinks(sinks, q.shape[1], q.dtype)
-    if k_rope is not None and v.shape[-1] == D:  # one head dim: the plan's op on the concatenated K
+    Dv = v.shape[-1]
+    if k_rope is not None and Dv == D:  # one head dim: the plan's op on the concatenated K
         k, k_rope = _cat_rope(k, k_rope), None
-    if v.shape[-1] != D:  # before the plan, which knows one head dim
-        return _attention_dims(q, k, v, causal, p, scale, window, softcap, docs, sinks, k_rope)
+    rope = 0 if k_rope is None else k_rope.shape[-1]
     plan = _plan(q.dtype, S, D, causal, scale, generic=_is_generic(window, softcap, docs, sinks), softcap=softcap,
-                 sinks=sinks is not None) if q.is_cuda else None
+                 sinks=sinks is not None, Dv=Dv, rope=rope) if q.is_cuda else None
     if plan is None:
         if q.is_cuda:
-            _note_math_path(S, D, q.dtype, window, softcap, docs is not None, sinks is not None)
+            _note_math_path(S, D, q.dtype, window, softcap, docs is not None, sinks is not None, Dv, rope)
         return attention_reference(q, k, v, causal, p, scale, window=window, softcap=softcap, doc_bounds=docs,
-                                   sinks=sinks)
+                                   sinks=sinks, k_rope=k_rope)
     sp, dp, kv_len, key_mask = plan
     if docs is not None:
         docs = _pad_docs(docs.to(q.device), S, sp)
 
-    def run(q, k, v):
+    def run(q, k, v, *kr):  # kr: k_rope as [B, 1, S, R], so that it pads with the others
         qs, ks, vs = (t.transpose(1, 2) for t in (q, k, v))
+        if Dv != D:  # attention_mla.hip: each operand read with its own strides
+            return _AttentionDims.apply(qs, ks, vs, causal, p, scale, kr[0].squeeze(1) if kr else None).transpose(1, 2)
         # (the fp32 key-bound path has always run on contiguous copies)
         if kv_len or not (qs.stride() == ks.stride() == vs.stride()) or qs.stride(3) != 1:
             qs, ks, vs = (t.contiguous() for t in (qs, ks, vs))
         o = _Attention.apply(qs, ks, vs, causal, p, scale, kv_len, window or 0, softcap or 0.0, docs, sinks)
         return o.transpose(1, 2)
 
-    return _run_padded(run, (q, k, v), 2, 1, S, D, sp, dp, ((0, slice(None)), (1, slice(None))) if key_mask else None)
+    ts = (q, k, v) if k_rope is None else (q, k, v, k_rope[:, None])
+    return _run_padded(run, ts, 2, 1, S, D, sp, dp, ((0, slice(None)), (1, slice(None))) if key_mask else None)

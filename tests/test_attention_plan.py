@@ -40,3 +40,47 @@ def test_plan_reproduces_the_recorded_table(stub_kernels):
         if got != (None if w is None else tuple(w)):
             wrong.append((dt, causal, S, D, sc, name, got, w))
     assert not wrong, f"{len(wrong)} rows differ, the first: {wrong[:5]}"
+
+
+def test_plan_differing_dims(stub_kernels):
+    """The plan's row for a V head dim of its own: it asks the extension's ``attention_dims_supported`` (stubbed
+    with attention_mla.hip's tiling, (192, 128) at ``S % 64 == 0``), and only for ``Dv != D``."""
+    stub = A.kernels_for()
+    asked = []
+
+    def dims_supported(S, Dqk, Dv):
+        asked.append((S, Dqk, Dv))
+        return S > 0 and S % 64 == 0 and (Dqk, Dv) == (192, 128)
+
+    stub.attention_dims_supported = dims_supported
+    bf16, f32 = torch.bfloat16, torch.float32
+
+    def plan(dtype, S, D, Dv, causal, generic=False, **kw):
+        return A._plan(dtype, S, D, causal, D ** -0.5, generic=generic, softcap=None, sinks=False, Dv=Dv, **kw)
+
+    for causal in (False, True):
+        for S in (64, 192):
+            assert plan(bf16, S, 192, 128, causal) == (S, 192, 0, False)
+            assert plan(bf16, S, 192, 128, causal, rope=64) == (S, 192, 0, False)
+            assert plan(bf16, S, 192, 128, causal, rope=32) is None  # the kernels read a 64-wide shared head
+            assert plan(bf16, S, 192, 128, causal, generic=True) is None
+            assert plan(f32, S, 192, 128, causal) is None
+            assert plan(bf16, S, 96, 64, causal) is None
+        assert plan(bf16, 100, 192, 128, causal, generic=True) is None
+        assert plan(f32, 100, 192, 128, causal) is None
+    assert plan(bf16, 100, 192, 128, True) == (128, 192, 0, False)  # causal end padding
+    assert plan(bf16, 100, 192, 128, True, rope=64) == (128, 192, 0, False)
+    assert plan(bf16, 100, 192, 128, False) is None
+    assert plan(bf16, 100, 96, 64, True) is None
+    assert asked and all(dv != d for _, d, dv in asked)
+
+    def never(S, Dqk, Dv):
+        raise AssertionError("attention_dims_supported asked for equal head dims")
+
+    stub.attention_dims_supported = never
+    for S in (64, 192):
+        for causal in (False, True):
+            assert plan(bf16, S, 128, 128, causal) == (S, 128, 0, False)
+            assert plan(bf16, S, 128, None, causal) == (S, 128, 0, False)
+    assert plan(bf16, 100, 128, 128, True) == plan(bf16, 100, 128, None, True) == (128, 128, 0, False)
+    assert plan(f32, 64, 64, 64, False, generic=True) is None

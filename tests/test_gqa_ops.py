@@ -99,6 +99,27 @@ def test_default_n_kv_heads_is_plain_mha(rope):
     assert blocks[0].core.in_proj_weight.shape == ((H + 4) * D, E)
 
 
+@pytest.mark.parametrize("rope", [False, True])
+def test_default_core_is_attention_packed_on_its_projection(rope):
+    """The core's one attention call, with as many K/V heads as query heads, gives the bits of
+    ``ops.attention_packed`` on the core's own (rotated) projection, in the output and the input gradient."""
+    S = 16
+    torch.manual_seed(4)
+    core = AttentionCore(E, H, 0.0, norm_first=False, causal=True, layer_norm_eps=1e-5, rope=rope, n_kv_heads=None)
+    g = torch.Generator().manual_seed(5)
+    x, do = torch.randn(2, S, E, generator=g), torch.randn(2, S, E, generator=g)
+    xa, xb = x.clone().requires_grad_(), x.clone().requires_grad_()
+    qkv = ops.linear(xb, core.in_proj_weight, core.in_proj_bias)
+    if rope:
+        qkv = ops.rope_projection(qkv, *ops.rope_tables(S, D, core.rope_base, device=x.device), H)
+    want = ops.attention_packed(qkv.view(2, S, 3, H, D), causal=True).reshape(2, S, E)
+    got = core(xa)
+    assert torch.equal(got, want)
+    got.backward(do)
+    want.backward(do)
+    assert torch.equal(xa.grad, xb.grad)
+
+
 # ------------------------------------------------------------------ 3. counts and costs
 def _decoder_padding(cfg):
     """Zero rows (weight and bias) that pad the decoder's vocabulary to a multiple of 256."""

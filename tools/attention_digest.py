@@ -5,7 +5,8 @@
 The cases walk every branch of the dispatch in ``mipipe/ops/attention.py`` at its smallest shape (B = 2, H = 4)
 through the three entry points: the S = 128, generic and long-sequence kernels, causal end padding, feature padding
 with the spare-feature key mask, the fp32 key bound, grouped-query heads in place and repeated, and a window, a soft
-cap, document bounds and sinks alone and together, with and without dropout.  Inputs are made on the CPU from a fixed
+cap, document bounds and sinks alone and together, with and without dropout, and ``attention`` with a V head dim of
+its own, (192, 128), with and without the shared rope key head.  Inputs are made on the CPU from a fixed
 seed and ``torch.manual_seed`` runs before each case, so two builds that dispatch alike print the same lines: run it
 at two commits on one machine and ``diff`` the outputs.  Only the public entry points are used.
 """
@@ -83,6 +84,38 @@ def run(name: str, entry: str, dtype, S: int, D: int, causal: bool, p: float, wh
     print(f"{name:<44} o={sha(o)} d={grads} dsinks={sha(None if sinks is None else sinks.grad)}", flush=True)
 
 
+def run_dims(name: str, S: int, causal: bool, p: float, rope: bool = False, which: str = "",
+             layout: str = "plain") -> None:
+    """``attention`` with a V head dim of its own, bf16 (192, 128); ``rope``: the keys are 128 nope features and the
+    shared rope key head ``k_rope [B, S, 64]``.  ``layout``: ``"plain"`` -- contiguous ``[B, H, S, D]`` leaves;
+    ``"views"`` -- q a transposed ``[B, S, H, D]``, k and v two slices of one projection output and ``k_rope`` a slice
+    of a wider row, each readable in place; ``"offset"`` -- the same slices 8 bytes off the 16-byte alignment, which
+    the op copies."""
+    gen = torch.Generator().manual_seed(1234)
+    leaf = lambda *shape: torch.randn(*shape, generator=gen).to(BF).to(DEV).requires_grad_()  # noqa: E731
+    dqk, dv, r = 192, 128, 64
+    dk = dqk - r if rope else dqk
+    if layout == "plain":
+        leaves = [leaf(B, H, S, dqk), leaf(B, H, S, dk), leaf(B, H, S, dv)] + ([leaf(B, S, r)] if rope else [])
+        q, k, v, kr = leaves + ([] if rope else [None])
+    else:
+        at = 0 if layout == "views" else 4
+        leaves = [leaf(B, S, H, dqk + 8), leaf(B, S, H, dk + dv + 8)] + ([leaf(B, S, r + 8)] if rope else [])
+        q = leaves[0][..., at:at + dqk].transpose(1, 2)
+        k = leaves[1][..., at:at + dk].transpose(1, 2)
+        v = leaves[1][..., at + dk:at + dk + dv].transpose(1, 2)
+        kr = leaves[2][..., at:at + r] if rope else None
+    kw, sinks = options(S, which, gen)
+    g = torch.randn(B, H, S, dv, generator=gen).to(BF).to(DEV)
+    torch.manual_seed(7)
+    o = attention(q, k, v, causal, p, True, k_rope=kr, **kw)
+    o.backward(g)
+    if DEV.type == "cuda":
+        torch.cuda.synchronize()
+    grads = " ".join(sha(t.grad) for t in leaves)  # q, k, v and k_rope's, or the buffers' they are slices of
+    print(f"{name:<44} o={sha(o)} d={grads} dsinks={sha(None if sinks is None else sinks.grad)}", flush=True)
+
+
 def main() -> None:
     warnings.simplefilter("ignore")  # the eager-path notes: the cases below take that path on purpose
     tag = lambda c, p: ("c" if c else "n") + ("_p" if p else "")  # noqa: E731
@@ -119,6 +152,18 @@ def main() -> None:
         run(f"eager_s72_d32_cs_{entry}_n", entry, BF, 72, 32, False, 0.0, "cs", n_kv=n_kv)
         run(f"eager_s72_d256_{entry}_n", entry, BF, 72, 256, False, 0.0, n_kv=n_kv)
         run(f"eager_f32_s64_d64_wcds_{entry}_c", entry, F32, 64, 64, True, 0.0, "wcds", n_kv=n_kv)
+    # a V head dim of its own, (192, 128), alone and with the shared rope key head (128 + 64)
+    for rope in (False, True):
+        r = "_rope" if rope else ""
+        for p in (0.0, 0.25):
+            for S in (64, 192):
+                for causal in (False, True):
+                    run_dims(f"dims{r}_s{S}_{tag(causal, p)}", S, causal, p, rope)
+            run_dims(f"dims{r}_s100_pad_{tag(True, p)}", 100, True, p, rope)  # end padding
+        run_dims(f"dims{r}_s128_views_c_p", 128, True, 0.25, rope, layout="views")
+        run_dims(f"dims{r}_s128_offset_c_p", 128, True, 0.25, rope, layout="offset")
+        run_dims(f"eager_dims{r}_s64_w_c", 64, True, 0.0, rope, "w")  # no native form: a window, an untiled length
+        run_dims(f"eager_dims{r}_s100_n", 100, False, 0.0, rope)
 
 
 if __name__ == "__main__":
