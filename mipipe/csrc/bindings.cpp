@@ -756,6 +756,77 @@ Tensor py_moe_route_bwd(Tensor logits, Tensor idx, Tensor gate, Tensor dgate, st
   return dlogits;
 }
 
+// The sigmoid router (kernels.h): (idx int32 [T, k], gate fp32 [T, k], probs_sum fp32 [Ne]) of logits [T, Ne].
+std::tuple<Tensor, Tensor, Tensor> py_moe_route_sigmoid_fwd(Tensor logits, std::optional<Tensor> bias, int64_t k,
+                                                            int64_t n_group, int64_t topk_group, bool renorm,
+                                                            double scale) {
+  const char* name = "moe_route_sigmoid_fwd";
+  check_cuda(logits, "logits");
+  MP_CHECK(logits.dim() == 2, name, ": logits must be [T, Ne]");
+  const int64_t T = logits.size(0), Ne = logits.size(1);
+  MP_CHECK(Ne <= 256 && k <= 8 && n_group >= 1 && n_group <= 256 && topk_group >= 1 && topk_group <= 8 &&
+               moe_route_sigmoid_supported((int)Ne, (int)k, (int)n_group, (int)topk_group),
+           name, ": needs 2 <= Ne <= 256, 1 <= k <= min(8, Ne), n_group dividing Ne and, with n_group > 1, groups of a "
+           "power of two in [2, 64] experts, 1 <= topk_group <= min(8, n_group) and topk_group * Ne / n_group >= k, got "
+           "Ne=", Ne, ", k=", k, ", n_group=", n_group, ", topk_group=", topk_group);
+  MP_CHECK(T * Ne < (int64_t(1) << 40), name, ": too many tokens");
+  if (bias.has_value()) moe_check_f32(*bias, logits, Ne, name, "bias");
+  at::hip::HIPGuardMasqueradingAsCUDA guard(logits.device());
+  auto idx = at::empty({T, k}, logits.options().dtype(at::kInt));
+  auto gate = at::empty({T, k}, logits.options().dtype(at::kFloat));
+  auto probs = at::empty({Ne}, logits.options().dtype(at::kFloat));
+  if (T == 0) {
+    probs.zero_();
+    return {idx, gate, probs};
+  }
+  const int nparts = moe_route_parts(T, (int)Ne);
+  auto part = at::empty({nparts, Ne}, logits.options().dtype(at::kFloat));
+  auto s = cur_stream(logits);
+  dispatch_fb(logits, name, [&](auto* tag) {
+    using T_ = std::remove_pointer_t<decltype(tag)>;
+    moe_route_sigmoid_fwd<T_>(cptr<T_>(logits), optr<float>(bias), ptr<int32_t>(idx), ptr<float>(gate),
+                              ptr<float>(part), nparts, T, (int)Ne, (int)k, (int)n_group, (int)topk_group, renorm,
+                              (float)scale, s);
+  });
+  reduce_parts(ptr<float>(part), nullptr, nparts, (int)Ne, probs.data_ptr(), nullptr, true, false, s);
+  return {idx, gate, probs};
+}
+
+Tensor py_moe_route_sigmoid_bwd(Tensor logits, Tensor idx, Tensor dgate, std::optional<Tensor> dprobs, bool renorm,
+                                double scale) {
+  const char* name = "moe_route_sigmoid_bwd";
+  check_cuda(logits, "logits");
+  MP_CHECK(logits.dim() == 2 && idx.dim() == 2 && idx.size(0) == logits.size(0), name,
+           ": logits must be [T, Ne] and idx [T, k]");
+  const int64_t T = logits.size(0), Ne = logits.size(1), k = idx.size(1);
+  MP_CHECK(Ne <= 256 && k <= 8 && moe_route_supported((int)Ne, (int)k), name,
+           ": needs 2 <= Ne <= 256 and 1 <= k <= min(8, Ne), got Ne=", Ne, ", k=", k);
+  moe_check_i32(idx, logits, T * k, name, "idx");
+  moe_check_f32(dgate, logits, T * k, name, "dgate");
+  if (dprobs.has_value()) moe_check_f32(*dprobs, logits, Ne, name, "dprobs");
+  at::hip::HIPGuardMasqueradingAsCUDA guard(logits.device());
+  auto dlogits = at::empty_like(logits);
+  auto s = cur_stream(logits);
+  dispatch_fb(logits, name, [&](auto* tag) {
+    using T_ = std::remove_pointer_t<decltype(tag)>;
+    moe_route_sigmoid_bwd<T_>(cptr<T_>(logits), cptr<int32_t>(idx), cptr<float>(dgate), optr<float>(dprobs),
+                              ptr<T_>(dlogits), T, (int)Ne, (int)k, renorm, (float)scale, s);
+  });
+  return dlogits;
+}
+
+// In place: bias[e] += rate * sign(mean(load) - load[e]), load[e] = 0.
+void py_moe_bias_update(Tensor bias, Tensor load, double rate) {
+  const char* name = "moe_bias_update";
+  check_cuda(bias, "bias");
+  const int64_t Ne = bias.numel();
+  MP_CHECK(bias.dim() == 1 && bias.scalar_type() == at::kFloat && Ne >= 1 && Ne <= 256, name,
+           ": bias must be fp32 [Ne] with 1 <= Ne <= 256");
+  moe_check_i32(load, bias, Ne, name, "load");
+  at::hip::HIPGuardMasqueradingAsCUDA guard(bias.device());
+  moe_bias_update(ptr<float>(bias), ptr<int32_t>(load), (int)Ne, (float)rate, cur_stream(bias));
+}
+
 // (slot int32 [T, k], src int32 [Ne * C], counts int32 [Ne]) of idx [T, k].
 std::tuple<Tensor, Tensor, Tensor> py_moe_assign(Tensor idx, int64_t n_experts, int64_t capacity) {
   const char* name = "moe_assign";
@@ -2327,6 +2398,16 @@ PYBIND11_MODULE(_C, m) {
         "logits [T, Ne] -> (idx int32 [T, k], gate fp32 [T, k], probs_sum fp32 [Ne])");
   m.def("moe_route_bwd", &py_moe_route_bwd, py::arg("logits"), py::arg("idx"), py::arg("gate"), py::arg("dgate"),
         py::arg("dprobs") = py::none());
+  m.def("moe_route_sigmoid_supported", [](int64_t n_experts, int64_t k, int64_t n_group, int64_t topk_group) {
+    return n_experts <= 256 && k <= 8 && n_group >= 1 && n_group <= 256 && topk_group >= 1 && topk_group <= 8 &&
+           moe_route_sigmoid_supported((int)n_experts, (int)k, (int)n_group, (int)topk_group);
+  });
+  m.def("moe_route_sigmoid_fwd", &py_moe_route_sigmoid_fwd, py::arg("logits"), py::arg("bias"), py::arg("k"),
+        py::arg("n_group"), py::arg("topk_group"), py::arg("renorm"), py::arg("scale"),
+        "logits [T, Ne], bias fp32 [Ne] or None -> (idx int32 [T, k], gate fp32 [T, k], probs_sum fp32 [Ne])");
+  m.def("moe_route_sigmoid_bwd", &py_moe_route_sigmoid_bwd, py::arg("logits"), py::arg("idx"), py::arg("dgate"),
+        py::arg("dprobs"), py::arg("renorm"), py::arg("scale"));
+  m.def("moe_bias_update", &py_moe_bias_update, py::arg("bias"), py::arg("load"), py::arg("rate"));
   m.def("moe_assign", &py_moe_assign, py::arg("idx"), py::arg("n_experts"), py::arg("capacity"),
         "idx int32 [T, k] -> (slot int32 [T, k], src int32 [Ne * C], counts int32 [Ne])");
   m.def("moe_assign_sorted", &py_moe_assign_sorted, py::arg("idx"), py::arg("n_experts"), py::arg("rows"),

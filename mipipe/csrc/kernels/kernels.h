@@ -209,6 +209,24 @@ void moe_gather_tokens(const T* ye, const int32_t* slot, const float* w, const T
 template <typename T>
 void moe_combine_bwd(const T* dy, const T* ye, const float* gate, const int32_t* src, T* dye, float* dgate,
                      int64_t nslots, int64_t tokens, int k, int E, hipStream_t s);
+// The sigmoid router (moe_sigmoid.hip).  moe_route_supported(Ne, k), n_group divides Ne, and with n_group > 1 the
+// group size Gs = Ne / n_group is a power of two in [2, 64], 1 <= topk_group <= min(8, n_group) and topk_group * Gs
+// >= k; n_group == 1 takes topk_group == 1.
+bool moe_route_sigmoid_supported(int Ne, int k, int n_group, int topk_group);
+// s = sigmoid(logits), c = s + bias (bias fp32 [Ne], optional): the topk_group groups with the largest sum of their
+// two best c stay eligible, idx [T, k] the k largest eligible c in descending order (lower group, lower expert first
+// among equals), gate [T, k] = scale s_j / (sum_j s_j + 1e-20) (renorm) or scale s_j; part [nparts, Ne] (nparts =
+// moe_route_parts) per-block sums over tokens of s / sum_e s, for reduce_parts.
+template <typename T>
+void moe_route_sigmoid_fwd(const T* logits, const float* bias, int32_t* idx, float* gate, float* part, int nparts,
+                           int64_t tokens, int Ne, int k, int n_group, int topk_group, bool renorm, float scale,
+                           hipStream_t s);
+// dlogits [T, Ne] from dgate [T, k] and the optional dprobs [Ne]; s is recomputed from the logits.
+template <typename T>
+void moe_route_sigmoid_bwd(const T* logits, const int32_t* idx, const float* dgate, const float* dprobs, T* dlogits,
+                           int64_t tokens, int Ne, int k, bool renorm, float scale, hipStream_t s);
+// bias[e] += rate * sign(mean(load) - load[e]), load[e] = 0: one block, Ne <= 256.
+void moe_bias_update(float* bias, int32_t* load, int Ne, float rate, hipStream_t s);
 
 // ------------------------------------------------------------------ elementwise
 enum Activation : int { kActNone = 0, kActRelu = 1, kActGelu = 2 };

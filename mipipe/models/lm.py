@@ -23,7 +23,7 @@ from .. import ops
 from ..ops.linear import mark_gemm_weight
 from ..ops.softcap import softcap_owned
 from .transformer import (GATED_ACTS, FeedForwardBlock, MLADims, check_expert_gemm, check_global_every, check_mla,
-                          check_positive, layer_window, transformer_blocks)
+                          check_moe_router, check_positive, layer_window, transformer_blocks)
 
 __all__ = [
     "Encoder",
@@ -241,11 +241,23 @@ class LMConfig:
     moe_aux_coef: float = 0.01        # weight of the load-balancing term in the router's gradient
     expert_gemm: str = "loop"         # "loop": one GEMM per expert on capacity slices; "grouped": dropless, needs
     #                                   capacity_factor=None (MoEFeedForwardBlock)
+    # DeepSeek-V3's router and shared experts.  No entry of CONFIGS sets them: dataclasses.replace(CONFIGS["moe_tiny"],
+    # moe_router="sigmoid", moe_n_group=2, moe_topk_group=1, moe_routed_scale=2.5, n_shared_experts=1)
+    moe_router: str = "softmax"       # "sigmoid": sigmoid scores, selection on score + a non-learned fp32 bias
+    moe_n_group: int = 1              # groups of neighbouring experts; only the moe_topk_group best stay eligible
+    moe_topk_group: int = 1
+    moe_routed_scale: float = 1.0     # constant factor on the routed experts' weights
+    moe_norm_topk_prob: bool = True   # weights renormalised over the selected experts
+    n_shared_experts: int = 0         # a dense gated MLP of width n * dim_feedforward on every token, added
+    moe_bias_rate: float = 0.0        # step of the selection bias per update_router_bias(); 0: the bias stays
     qk_norm: bool = False             # per-head RMSNorm on Q and K before the rotation (Qwen3): two [head_dim] weights
 
     def __post_init__(self) -> None:
         check_global_every(self.global_every, self.window)
         check_expert_gemm(self.expert_gemm, self.capacity_factor)
+        check_moe_router(self.moe_router, self.n_experts, self.experts_per_token, self.moe_n_group,
+                         self.moe_topk_group, self.moe_routed_scale, self.moe_norm_topk_prob, self.n_shared_experts,
+                         self.moe_bias_rate)
         check_mla(self.mla, rope=self.rope, norm=self.norm, n_kv_heads=self.n_kv_heads, head_dim=self.head_dim,
                   window=self.window, qk_norm=self.qk_norm, attn_softcap=self.attn_softcap, attn_sinks=self.attn_sinks)
 
@@ -295,7 +307,7 @@ class LMConfig:
         if self.mla is not None:  # the latent projections and their two norms; bias-free by construction
             return self._params_mla()
         if self.n_experts is not None:  # the router and the experts (bias-free) in place of the dense MLP
-            mlp = self.n_experts * (e + f1 * e + e * f)
+            mlp = self.n_experts * (e + f1 * e + e * f) + self.n_shared_experts * (f1 * e + e * f)
             layer = (qkv + self.attn_dim()) * e + 2 * norm + mlp + nb * (qkv + e)
         else:
             layer = (qkv + self.attn_dim()) * e + 2 * norm + f1 * e + e * f + nb * (qkv + e + f1 + e)
@@ -318,7 +330,7 @@ class LMConfig:
         nb = 1 if self.bias else 0
         attn = self.attn_proj_params() + self.mla.norm_params() + self.attn_dim() * e + nb * e
         if self.n_experts is not None:
-            mlp = self.n_experts * (e + f1 * e + e * f)
+            mlp = self.n_experts * (e + f1 * e + e * f) + self.n_shared_experts * (f1 * e + e * f)
         else:
             mlp = f1 * e + e * f + nb * (f1 + e)
         layer = attn + 2 * e + mlp + (2 * e if self.sandwich_norm else 0)
@@ -489,7 +501,10 @@ def build_lm_blocks(cfg: LMConfig, *, device=None, dtype=None) -> List[nn.Module
                                  sandwich_norm=cfg.sandwich_norm, head_dim=cfg.head_dim, attn_scale=cfg.attn_scale,
                                  global_every=cfg.global_every, attn_sinks=cfg.attn_sinks, n_experts=cfg.n_experts,
                                  experts_per_token=cfg.experts_per_token, capacity_factor=cfg.capacity_factor,
-                                 moe_aux_coef=cfg.moe_aux_coef, expert_gemm=cfg.expert_gemm, mla=cfg.mla,
+                                 moe_aux_coef=cfg.moe_aux_coef, expert_gemm=cfg.expert_gemm, moe_router=cfg.moe_router,
+                                 moe_n_group=cfg.moe_n_group, moe_topk_group=cfg.moe_topk_group,
+                                 moe_routed_scale=cfg.moe_routed_scale, moe_norm_topk_prob=cfg.moe_norm_topk_prob,
+                                 n_shared_experts=cfg.n_shared_experts, moe_bias_rate=cfg.moe_bias_rate, mla=cfg.mla,
                                  device=device, dtype=dtype)
     if cfg.act_dropout is not None:
         for b in blocks:

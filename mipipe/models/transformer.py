@@ -84,6 +84,7 @@ import torch
 from torch import Tensor, nn
 
 from .. import ops
+from ..checkpoint import is_recomputing, recompute_expected
 from ..ops.linear import ActFold, mark_gemm_weight
 
 # Fan-out fusion of the residual-branch gradient (see AttentionCore.forward_fanout);
@@ -802,6 +803,46 @@ def check_expert_gemm(expert_gemm: str, capacity_factor: Optional[float]) -> Non
         raise ValueError(f"expert_gemm='grouped' is dropless: it needs capacity_factor=None, got {capacity_factor!r}")
 
 
+MOE_ROUTERS = ("softmax", "sigmoid")
+
+
+def _is_int(v, lo: int) -> bool:
+    return isinstance(v, int) and not isinstance(v, bool) and v >= lo
+
+
+def check_moe_router(router: str, n_experts: Optional[int], experts_per_token: int, n_group: int, topk_group: int,
+                     routed_scale: float, norm_topk_prob: bool, n_shared_experts: int,
+                     bias_update_rate: float) -> None:
+    """The router options of :class:`MoEFeedForwardBlock` (and ``LMConfig``'s fields of the same meaning); with
+    ``n_experts=None`` (a dense config) only their own ranges are checked."""
+    if router not in MOE_ROUTERS:
+        raise ValueError(f"router must be one of {MOE_ROUTERS}, got {router!r}")
+    if not _is_int(n_shared_experts, 0):
+        raise ValueError(f"n_shared_experts must be an int >= 0, got {n_shared_experts!r}")
+    if not _is_int(n_group, 1):
+        raise ValueError(f"n_group must be an int >= 1, got {n_group!r}")
+    if not _is_int(topk_group, 1) or topk_group > n_group:
+        raise ValueError(f"topk_group must be an int in [1, n_group] = [1, {n_group}], got {topk_group!r}")
+    if not math.isfinite(routed_scale):
+        raise ValueError(f"routed_scale must be finite, got {routed_scale!r}")
+    if not (math.isfinite(bias_update_rate) and bias_update_rate >= 0):
+        raise ValueError(f"bias_update_rate must be a finite number >= 0, got {bias_update_rate!r}")
+    if router == "softmax":
+        if n_group != 1 or topk_group != 1 or routed_scale != 1.0 or norm_topk_prob is not True or bias_update_rate:
+            raise ValueError("n_group, topk_group, routed_scale, norm_topk_prob and bias_update_rate belong to "
+                             "router='sigmoid'; router='softmax' takes their defaults only")
+        return
+    if n_experts is None:
+        return
+    if n_experts % n_group != 0:
+        raise ValueError(f"n_group must divide n_experts={n_experts}, got {n_group}")
+    if n_group > 1 and n_experts // n_group < 2:
+        raise ValueError(f"n_group={n_group} leaves groups of one expert; a group's score needs two")
+    if n_group > 1 and topk_group * (n_experts // n_group) < experts_per_token:
+        raise ValueError(f"topk_group={topk_group} groups of {n_experts // n_group} experts hold fewer than "
+                         f"experts_per_token={experts_per_token}")
+
+
 class MoEFeedForwardBlock(nn.Module):
     """Mixture-of-experts MLP half of a pre-norm layer (Mixtral, Qwen3-MoE): ``x + sum_j gate_j expert_{idx_j}(norm(x))``
     with ``n_experts`` gated MLPs (``activation="swiglu"`` or ``"geglu"``) of which every token runs its
@@ -831,12 +872,27 @@ class MoEFeedForwardBlock(nn.Module):
     ``k T + 64 Ne`` rows, not ``Ne ceil64(T)``), and the experts run as ``ops.grouped_linear(w1)``, the gate op once,
     ``ops.grouped_linear(w2)``: three GEMM launches and one gate launch per direction whatever ``Ne``, no
     concatenation.  Nothing is dropped: ``last_drop_fraction`` is exactly 0.  Its weight gradients run in the
-    backward, not in the deferred flush.  ``"loop"`` (the default) is the path described above."""
+    backward, not in the deferred flush.  ``"loop"`` (the default) is the path described above.
+
+    ``router="sigmoid"`` is DeepSeek-V3's gate (``ops.moe_route(score="sigmoid")``): sigmoid scores, ``n_group``
+    groups of neighbouring experts of which the ``topk_group`` best stay eligible, selection on score plus
+    ``router_bias``, weights from the unbiased scores of the selected experts, renormalised (``norm_topk_prob``) or
+    not, times ``routed_scale``.  ``router_bias [Ne]`` is a persistent buffer that stays fp32 whatever the module is
+    cast to; ``expert_load [Ne]`` (int32) counts the choices per expert of every training forward (not of a
+    checkpoint's recompute, not under ``no_grad``), and :meth:`update_router_bias` moves the bias by
+    ``bias_update_rate`` against it (auxiliary-loss-free balancing; rate 0: never).  The load-balancing term above
+    works unchanged on ``probs_sum``, the normalised scores ``s / sum_e s_e`` summed over the tokens.
+
+    ``n_shared_experts=n`` adds one dense gated MLP of width ``n * dim_feedforward`` on every token (``shared_w1 [2 n
+    F, E]``, ``shared_w2 [E, n F]``, GEMM weights) to the routed output, with either router.  With the defaults
+    neither buffers nor shared weights exist and the forward is the one described first."""
 
     def __init__(self, d_model: int, dim_feedforward: int, n_experts: int, experts_per_token: int = 2, *,
                  capacity_factor: Optional[float] = 1.25, aux_coef: float = 0.01, activation: str = "swiglu",
                  norm_first: bool = True, norm: str = "rms", layer_norm_eps: float = 1e-5, bias: bool = False,
-                 expert_gemm: str = "loop", device=None, dtype=None) -> None:
+                 expert_gemm: str = "loop", router: str = "softmax", n_group: int = 1, topk_group: int = 1,
+                 routed_scale: float = 1.0, norm_topk_prob: bool = True, n_shared_experts: int = 0,
+                 bias_update_rate: float = 0.0, device=None, dtype=None) -> None:
         super().__init__()
         fk = {"device": device, "dtype": dtype}
         if not norm_first or bias:
@@ -863,6 +919,18 @@ class MoEFeedForwardBlock(nn.Module):
             [mark_gemm_weight(nn.Parameter(torch.empty(2 * dim_feedforward, d_model, **fk))) for _ in range(n_experts)])
         self.experts_w2 = nn.ParameterList(
             [mark_gemm_weight(nn.Parameter(torch.empty(d_model, dim_feedforward, **fk))) for _ in range(n_experts)])
+        check_moe_router(router, n_experts, experts_per_token, n_group, topk_group, routed_scale, norm_topk_prob,
+                         n_shared_experts, bias_update_rate)
+        self.router, self.n_group, self.topk_group = router, n_group, topk_group
+        self.routed_scale, self.norm_topk_prob = float(routed_scale), bool(norm_topk_prob)
+        self.n_shared_experts, self.bias_update_rate = n_shared_experts, float(bias_update_rate)
+        if router == "sigmoid":
+            self.register_buffer("router_bias", torch.zeros(n_experts, device=device, dtype=torch.float32))
+            self.register_buffer("expert_load", torch.zeros(n_experts, device=device, dtype=torch.int32))
+        if n_shared_experts:
+            fs = n_shared_experts * dim_feedforward
+            self.shared_w1 = mark_gemm_weight(nn.Parameter(torch.empty(2 * fs, d_model, **fk)))
+            self.shared_w2 = mark_gemm_weight(nn.Parameter(torch.empty(d_model, fs, **fk)))
         self.last_aux: Optional[Tensor] = None
         self.last_drop_fraction: Optional[Tensor] = None
         self.reset_parameters()
@@ -870,15 +938,40 @@ class MoEFeedForwardBlock(nn.Module):
     def reset_parameters(self) -> None:
         _reset_norm(self)
         nn.init.normal_(self.router_weight, std=0.02)
-        for w in list(self.experts_w1) + list(self.experts_w2):
+        shared = [self.shared_w1, self.shared_w2] if getattr(self, "n_shared_experts", 0) else []
+        for w in list(self.experts_w1) + list(self.experts_w2) + shared:
             nn.init.kaiming_uniform_(w, a=math.sqrt(5))
+
+    def _apply(self, fn, recurse=True):
+        """``router_bias`` stays fp32 through a dtype cast (its steps of ``bias_update_rate`` vanish in bf16): the
+        cast is applied, then the buffer is restored in fp32 on the device the cast left it on."""
+        bias = getattr(self, "router_bias", None)
+        super()._apply(fn, recurse)
+        if bias is not None and self.router_bias.dtype != torch.float32:
+            self.router_bias = bias.to(device=self.router_bias.device, dtype=torch.float32)
+        return self
+
+    def update_router_bias(self) -> None:
+        """Auxiliary-loss-free balancing (``ops.moe_bias_update``): ``router_bias[e] += bias_update_rate *
+        sign(mean(load) - load[e])`` over the ``expert_load`` gathered since the last call, which it clears.  A
+        no-op at rate 0 and for a softmax router.  :class:`~mipipe.parallel.engine.PipelineEngine` calls it at the
+        end of every step; outside the engine call it after the optimizer step."""
+        if getattr(self, "router", "softmax") != "sigmoid" or self.bias_update_rate == 0.0:
+            return
+        ops.moe_bias_update(self.router_bias, self.expert_load, self.bias_update_rate)
 
     def route(self, logits: Tensor, tokens: int):
         """``(gate, slot, src, capacity)`` of the router ``logits [T, Ne]``; records the logging scalars and, when a
         graph is recorded, attaches the load-balancing gradient to the gate.  The grouped path returns ``(offsets,
         tile_expert)`` of the sorted layout in the capacity's place."""
         ne, k = self.n_experts, self.experts_per_token
-        idx, gate, probs_sum = ops.moe_route(logits, k)
+        sigmoid = getattr(self, "router", "softmax") == "sigmoid"
+        if sigmoid:
+            idx, gate, probs_sum = ops.moe_route(logits, k, score="sigmoid", bias=self.router_bias,
+                                                 n_group=self.n_group, topk_group=self.topk_group,
+                                                 renormalize=self.norm_topk_prob, scale=self.routed_scale)
+        else:
+            idx, gate, probs_sum = ops.moe_route(logits, k)
         if getattr(self, "expert_gemm", "loop") == "grouped":
             slot, src, counts, offsets, tile_expert = ops.moe_assign_sorted(idx, ne)
             cap = (offsets, tile_expert)
@@ -886,6 +979,11 @@ class MoEFeedForwardBlock(nn.Module):
             cap = ops.moe_capacity(tokens, ne, k, self.capacity_factor)
             slot, src, counts = ops.moe_assign(idx, ne, cap)
         attach = self.aux_coef != 0.0 and torch.is_grad_enabled() and gate.requires_grad
+        # the load counts a training forward once: one that records a graph, or the first (no-grad) forward of a
+        # checkpointed partition whose backward will recompute it; the recomputed forward itself does not count
+        if sigmoid and ((torch.is_grad_enabled() and not is_recomputing()) or recompute_expected()):
+            with torch.no_grad():
+                self.expert_load += counts
         with torch.no_grad():
             load = counts.to(probs_sum.dtype)
             self.last_aux = (load * probs_sum).sum() * (ne / (float(tokens) * tokens * k))
@@ -921,12 +1019,18 @@ class MoEFeedForwardBlock(nn.Module):
             ye = self.experts_grouped(ops.moe_dispatch(x2, slot, src), *cap)
         else:
             ye = self.experts(ops.moe_dispatch(x2, slot, src), cap)
-        return ops.moe_combine(ye, gate, slot, src, residual=xr.reshape(-1, shape[-1])).view(shape)
+        y = ops.moe_combine(ye, gate, slot, src, residual=xr.reshape(-1, shape[-1]))
+        if getattr(self, "n_shared_experts", 0):   # one dense gated MLP on every token, added to the routed output
+            act = ops.swiglu if self.activation == "swiglu" else ops.geglu
+            y = ops.linear_residual(act(ops.linear(x2, self.shared_w1)), self.shared_w2, None, y)
+        return y.view(shape)
 
     def flops_per_token(self, seq_len: int) -> float:
-        """The model's FLOPs: the router and the ``experts_per_token`` active experts, not the capacity padding."""
+        """The model's FLOPs: the router, the ``experts_per_token`` active experts (not the capacity padding) and the
+        shared experts."""
         e, f = self.d_model, self.dim_feedforward
-        return 2 * e * self.n_experts + self.experts_per_token * (2 * e * 2 * f + 2 * e * f)
+        active = self.experts_per_token + getattr(self, "n_shared_experts", 0)
+        return 2 * e * self.n_experts + active * (2 * e * 2 * f + 2 * e * f)
 
 
 class PackedFeedForwardIn(nn.Module):
@@ -1076,6 +1180,13 @@ def transformer_blocks(
     capacity_factor: Optional[float] = 1.25,
     moe_aux_coef: float = 0.01,
     expert_gemm: str = "loop",
+    moe_router: str = "softmax",
+    moe_n_group: int = 1,
+    moe_topk_group: int = 1,
+    moe_routed_scale: float = 1.0,
+    moe_norm_topk_prob: bool = True,
+    n_shared_experts: int = 0,
+    moe_bias_rate: float = 0.0,
     mla: Optional[MLADims] = None,
     device=None,
     dtype=None,
@@ -1088,7 +1199,10 @@ def transformer_blocks(
     ``n_experts=Ne`` (``None``: dense) builds a :class:`MoEFeedForwardBlock` of ``Ne`` experts of width
     ``dim_feedforward`` in place of the :class:`FeedForwardBlock` of every layer (pre-norm, bias-free, gated
     activation, no sandwich norm); ``expert_gemm="grouped"`` (with ``capacity_factor=None``) selects its dropless
-    grouped-GEMM path.
+    grouped-GEMM path.  ``moe_router="sigmoid"`` with ``moe_n_group``, ``moe_topk_group``, ``moe_routed_scale``,
+    ``moe_norm_topk_prob`` and ``moe_bias_rate`` is DeepSeek-V3's router and ``n_shared_experts`` its always-on
+    experts (the block's ``router``, ``n_group``, ``topk_group``, ``routed_scale``, ``norm_topk_prob``,
+    ``bias_update_rate`` and ``n_shared_experts``).
 
     ``mla=MLADims(...)`` (``None``: none) builds every layer's attention core as a :class:`LatentAttentionCore`."""
     check_global_every(global_every, window)
@@ -1105,7 +1219,10 @@ def transformer_blocks(
             blocks.append(MoEFeedForwardBlock(d_model, dim_feedforward, n_experts, experts_per_token,
                                               capacity_factor=capacity_factor, aux_coef=moe_aux_coef,
                                               activation=activation, norm_first=norm_first, norm=norm, bias=bias,
-                                              expert_gemm=expert_gemm, device=device, dtype=dtype))
+                                              expert_gemm=expert_gemm, router=moe_router, n_group=moe_n_group,
+                                              topk_group=moe_topk_group, routed_scale=moe_routed_scale,
+                                              norm_topk_prob=moe_norm_topk_prob, n_shared_experts=n_shared_experts,
+                                              bias_update_rate=moe_bias_rate, device=device, dtype=dtype))
         return blocks
     for i in range(num_layers):
         layer = TransformerEncoderLayer(d_model, nhead, dim_feedforward, dropout, activation,

@@ -19,8 +19,8 @@ from .rope import (mla_rope, mla_rope_reference, rope_heads, rope_packed, rope_p
                    rope_tables)
 from .qknorm import qk_norm_rope_heads, qk_norm_rope_projection, qk_norm_rope_reference
 from .moe import (moe_assign, moe_assign_reference, moe_assign_sorted, moe_assign_sorted_reference, moe_attach_aux,
-                  moe_capacity, moe_combine, moe_combine_reference, moe_dispatch, moe_dispatch_reference, moe_route,
-                  moe_route_reference, moe_sorted_rows)
+                  moe_bias_update, moe_capacity, moe_combine, moe_combine_reference, moe_dispatch,
+                  moe_dispatch_reference, moe_route, moe_route_reference, moe_sorted_rows)
 from .grouped_linear import grouped_linear, grouped_linear_reference
 from .loss import cross_entropy
 from .embedding import embed_scale_posenc_dropout
@@ -77,6 +77,7 @@ __all__ = [
     "moe_assign_sorted",
     "moe_assign_sorted_reference",
     "moe_sorted_rows",
+    "moe_bias_update",
     "grouped_linear",
     "grouped_linear_reference",
     "cross_entropy",

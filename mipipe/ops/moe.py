@@ -32,7 +32,11 @@ The dropless variant of the second step, for ``ops.grouped_linear``::
 
     slot, src, counts, offsets, tile_expert = moe_assign_sorted(idx, Ne)
 
-sorts the choices by expert into ``R = moe_sorted_rows(T, Ne, k)`` rows, every expert's segment padded to whole
+``moe_route(..., score="sigmoid", bias=, n_group=, topk_group=, renormalize=, scale=)`` is DeepSeek-V3's gate
+(sigmoid scores, group-limited selection on score plus bias, weights from the unbiased scores: see
+:func:`moe_route`), and :func:`moe_bias_update` its auxiliary-loss-free balancing step.
+
+``moe_assign_sorted`` sorts the choices by expert into ``R = moe_sorted_rows(T, Ne, k)`` rows, every expert's segment padded to whole
 128-row tiles (see :func:`moe_assign_sorted`); dispatch and combine take its tables unchanged.
 """
 from __future__ import annotations
@@ -48,7 +52,8 @@ from ._util import kernels_for
 
 __all__ = ["moe_route", "moe_assign", "moe_dispatch", "moe_combine", "moe_capacity", "moe_route_reference",
            "moe_assign_reference", "moe_dispatch_reference", "moe_combine_reference", "moe_attach_aux",
-           "moe_assign_sorted", "moe_assign_sorted_reference", "moe_sorted_rows", "MAX_EXPERTS", "MAX_TOP_K"]
+           "moe_assign_sorted", "moe_assign_sorted_reference", "moe_sorted_rows", "moe_bias_update", "MAX_EXPERTS",
+           "MAX_TOP_K"]
 
 MAX_EXPERTS = 256
 MAX_TOP_K = 8
@@ -76,8 +81,33 @@ def moe_capacity(tokens: int, n_experts: int, k: int, capacity_factor: Optional[
 
 
 # ------------------------------------------------------------------ references
-def moe_route_reference(logits: Tensor, k: int) -> Tuple[Tensor, Tensor, Tensor]:
-    """Eager route (CPU path and test oracle): a stable descending sort of the fp32 values (fp64 stays fp64)."""
+def _sigmoid_route_reference(logits: Tensor, k: int, bias: Optional[Tensor], n_group: int, topk_group: int,
+                             renormalize: bool, scale: float) -> Tuple[Tensor, Tensor, Tensor]:
+    """The six steps of the sigmoid route (:func:`moe_route`), eager, in the promoted dtype."""
+    wide = torch.promote_types(logits.dtype, torch.float32)
+    T, Ne = logits.shape
+    s = torch.sigmoid(logits.to(wide))
+    c = s if bias is None else s + bias.to(wide)
+    if n_group > 1:
+        score = c.view(T, n_group, Ne // n_group).topk(2, dim=-1).values.sum(-1)
+        best = torch.sort(score, dim=-1, descending=True, stable=True).indices[:, :topk_group]
+        keep = torch.zeros(T, n_group, dtype=torch.bool, device=c.device).scatter_(1, best, True)
+        c = c.masked_fill(~keep.repeat_interleave(Ne // n_group, dim=1), float("-inf"))
+    idx = torch.sort(c, dim=-1, descending=True, stable=True).indices[:, :k]
+    gate = s.gather(1, idx)
+    if renormalize:
+        gate = gate / (gate.sum(-1, keepdim=True) + 1e-20)
+    probs_sum = (s / s.sum(-1, keepdim=True)).sum(0)
+    return idx.to(torch.int32), gate * scale, probs_sum
+
+
+def moe_route_reference(logits: Tensor, k: int, *, score: str = "softmax", bias: Optional[Tensor] = None,
+                        n_group: int = 1, topk_group: int = 1, renormalize: bool = True,
+                        scale: float = 1.0) -> Tuple[Tensor, Tensor, Tensor]:
+    """Eager route (CPU path and test oracle): a stable descending sort of the fp32 values (fp64 stays fp64).  The
+    keywords are :func:`moe_route`'s; they are not validated here."""
+    if score == "sigmoid":
+        return _sigmoid_route_reference(logits, k, bias, n_group, topk_group, renormalize, scale)
     wide = torch.promote_types(logits.dtype, torch.float32)
     lf = logits.to(wide)
     vals, order = torch.sort(lf, dim=-1, descending=True, stable=True)
@@ -183,15 +213,105 @@ class _MoeRoute(torch.autograd.Function):
         return kernels_for(logits).moe_route_bwd(logits, idx, gate, dgate, dprobs), None
 
 
-def moe_route(logits: Tensor, k: int) -> Tuple[Tensor, Tensor, Tensor]:
+class _MoeRouteSigmoid(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logits, bias, k, n_group, topk_group, renorm, scale):  # type: ignore[override]
+        ctx.set_materialize_grads(False)
+        idx, gate, probs_sum = kernels_for(logits).moe_route_sigmoid_fwd(logits, bias, k, n_group, topk_group, renorm,
+                                                                         scale)
+        ctx.save_for_backward(logits, idx)   # s is recomputed; the bias only selects and has no gradient
+        ctx.renorm, ctx.scale = renorm, scale
+        ctx.mark_non_differentiable(idx)
+        return idx, gate, probs_sum
+
+    @staticmethod
+    def backward(ctx, _didx, dgate, dprobs):  # type: ignore[override]
+        logits, idx = ctx.saved_tensors
+        if dgate is None and dprobs is None:
+            return (None,) * 7
+        dgate = torch.zeros(idx.shape, dtype=torch.float32, device=idx.device) if dgate is None \
+            else dgate.contiguous().float()
+        if dprobs is not None:
+            dprobs = dprobs.contiguous().float()
+        dlogits = kernels_for(logits).moe_route_sigmoid_bwd(logits, idx, dgate, dprobs, ctx.renorm, ctx.scale)
+        return (dlogits,) + (None,) * 6
+
+
+def _check_sigmoid(n_experts: int, k: int, bias: Optional[Tensor], n_group: int, topk_group: int, scale: float,
+                   like: Tensor) -> None:
+    name = "moe_route"
+    if bias is not None:
+        if not isinstance(bias, Tensor) or bias.shape != (n_experts,) or not bias.dtype.is_floating_point:
+            raise ValueError(f"{name}: bias must be a floating-point [Ne] = [{n_experts}] tensor, got "
+                             f"{tuple(bias.shape) if isinstance(bias, Tensor) else bias!r}")
+        if bias.device != like.device:
+            raise ValueError(f"{name}: bias is on {bias.device}, the logits on {like.device}")
+    if n_group < 1 or n_experts % n_group != 0:
+        raise ValueError(f"{name}: n_group must be >= 1 and divide the {n_experts} experts, got {n_group}")
+    if not 1 <= topk_group <= n_group:
+        raise ValueError(f"{name}: topk_group must be in [1, n_group] = [1, {n_group}], got {topk_group}")
+    if n_group > 1 and n_experts // n_group < 2:
+        raise ValueError(f"{name}: n_group={n_group} leaves groups of one expert; a group's score needs two")
+    if n_group > 1 and topk_group * (n_experts // n_group) < k:
+        raise ValueError(f"{name}: topk_group={topk_group} groups of {n_experts // n_group} experts hold fewer than "
+                         f"k={k}")
+    if not math.isfinite(scale):
+        raise ValueError(f"{name}: scale must be finite, got {scale!r}")
+
+
+def moe_route(logits: Tensor, k: int, *, score: str = "softmax", bias: Optional[Tensor] = None, n_group: int = 1,
+              topk_group: int = 1, renormalize: bool = True, scale: float = 1.0) -> Tuple[Tensor, Tensor, Tensor]:
     """``(idx, gate, probs_sum)`` of ``logits [T, Ne]`` (see the module docstring).  The logits are finite or
-    ``-inf`` with at least one finite value per row.  Differentiable in ``gate`` and ``probs_sum``."""
+    ``-inf`` with at least one finite value per row.  Differentiable in ``gate`` and ``probs_sum``.
+
+    ``score="sigmoid"`` is DeepSeek-V3's gate (kernels: csrc/kernels/moe_sigmoid.hip), per row in fp32:
+
+    1. ``s = sigmoid(logits)``;
+    2. the selection score ``c = s + bias`` (``bias [Ne]``, not learned, no gradient; ``c = s`` without);
+    3. with ``n_group > 1`` the experts form ``n_group`` groups of neighbours, a group's score is the sum of its
+       two largest ``c``, and only the ``topk_group`` best groups (the lower group first among equal scores) stay
+       eligible;
+    4. ``idx``: the ``k`` largest eligible ``c``, descending, the lower expert first among equal values;
+    5. ``gate = scale * s_j / (sum_j s_j + 1e-20)`` over the selected (``renormalize``) or ``scale * s_j``: the
+       unbiased sigmoids;
+    6. ``probs_sum``: ``s / sum_e s_e`` summed over the tokens, so :func:`moe_attach_aux` works unchanged.
+
+    A row needs one logit above -87 (a nonzero ``s``).  Native on the GPU for ``2 <= Ne <= 256``, ``k <= 8`` and,
+    with groups, a group size that is a power of two in [2, 64] and ``topk_group <= 8``; anything else (DeepSeek-V2's
+    groups of 20) runs the eager reference and says so once per shape.  An ineligible expert is never chosen.
+    Hugging Face's DeepSeek-V3 gate fills the ineligible scores with 0.0 instead and can pick one when fewer than
+    ``k`` eligible ``c`` are positive; ``topk_group * Ne / n_group >= k`` is required here, so the two differ in that
+    corner only.  With ``score="softmax"`` (the default) the other keywords must keep their defaults."""
     if logits.dim() != 2:
         raise ValueError(f"moe_route: logits must be [T, Ne], got {tuple(logits.shape)}")
     if not logits.dtype.is_floating_point:
         raise ValueError(f"moe_route: logits must be floating point, got {logits.dtype}")
     k = int(k)
     _check_k("moe_route", logits.shape[1], k)
+    if score not in ("softmax", "sigmoid"):
+        raise ValueError(f"moe_route: score must be 'softmax' or 'sigmoid', got {score!r}")
+    if score == "sigmoid":
+        n_group, topk_group, renormalize, scale = int(n_group), int(topk_group), bool(renormalize), float(scale)
+        ne = logits.shape[1]
+        _check_sigmoid(ne, k, bias, n_group, topk_group, scale, logits)
+        args = (k, n_group, topk_group, renormalize, scale)
+        if not logits.is_cuda:
+            return _sigmoid_route_reference(logits, k, bias, *args[1:])
+        why = None
+        if logits.dtype not in (torch.bfloat16, torch.float32):
+            why = "only bf16 and fp32 are native"
+        elif ne < 2:
+            why = "a single expert is not native"
+        elif not kernels_for(logits).moe_route_sigmoid_supported(ne, k, n_group, topk_group):
+            why = f"groups of {ne // n_group} experts (n_group={n_group}, topk_group={topk_group}) are not native"
+        if why is not None:
+            _note("moe_route", why, logits)
+            return _sigmoid_route_reference(logits, k, bias, *args[1:])
+        return _MoeRouteSigmoid.apply(logits.contiguous(), None if bias is None else bias.detach().contiguous().float(),
+                                      *args)
+    if bias is not None or n_group != 1 or topk_group != 1 or renormalize is not True or scale != 1.0:
+        raise ValueError("moe_route: bias, n_group, topk_group, renormalize and scale belong to score='sigmoid'; "
+                         "score='softmax' takes their defaults only")
     if not logits.is_cuda:
         return moe_route_reference(logits, k)
     if logits.dtype not in (torch.bfloat16, torch.float32):
@@ -224,6 +344,24 @@ def moe_attach_aux(gate: Tensor, probs_sum: Tensor, dprobs: Tensor) -> Tensor:
     if dprobs.shape != probs_sum.shape:
         raise ValueError(f"moe_attach_aux: dprobs {tuple(dprobs.shape)} must match probs_sum {tuple(probs_sum.shape)}")
     return _AttachAux.apply(gate, probs_sum, dprobs.to(probs_sum.dtype))
+
+
+def moe_bias_update(bias: Tensor, load: Tensor, rate: float) -> None:
+    """Auxiliary-loss-free balancing (DeepSeek-V3), in place: ``bias[e] += rate * sign(mean(load) - load[e])`` and
+    ``load[e] = 0``, for the selection ``bias [Ne]`` (fp32) and the ``load [Ne]`` (int32) of choices per expert since
+    the last update.  ``sign(0) = 0``: the comparison is ``sum(load)`` against ``Ne * load[e]`` in integers."""
+    if bias.dim() != 1 or bias.dtype != torch.float32:
+        raise ValueError(f"moe_bias_update: bias must be fp32 [Ne], got {tuple(bias.shape)} {bias.dtype}")
+    if load.shape != bias.shape or load.dtype != torch.int32 or load.device != bias.device:
+        raise ValueError(f"moe_bias_update: load must be int32 {tuple(bias.shape)} on {bias.device}, got "
+                         f"{tuple(load.shape)} {load.dtype} on {load.device}")
+    with torch.no_grad():
+        if bias.is_cuda:   # in place: the binding refuses a non-contiguous tensor or more than 256 experts
+            kernels_for(bias).moe_bias_update(bias, load, float(rate))
+            return
+        wide = load.long()
+        bias.add_(torch.sign(wide.sum() - wide * load.numel()).to(bias.dtype), alpha=float(rate))
+        load.zero_()
 
 
 # ------------------------------------------------------------------ assign

@@ -171,7 +171,8 @@ class PipelineEngine:
             SUM is the mean (:mod:`mipipe.parallel.data_parallel`).  Every
             :class:`~mipipe.models.transformer.MoEFeedForwardBlock` of the
             modules gets ``aux_scale = 1 / (chunks * grad_divisor)``, so its
-            load-balancing gradient is scaled like the loss's.
+            load-balancing gradient is scaled like the loss's, and
+            ``update_router_bias()`` at the end of every :meth:`step`.
         transport: how activations and gradients move between ranks when the
             engine builds its own channels (:func:`make_transport`):
             ``"auto"`` (default: self-tested IPC links, every rank falling
@@ -228,10 +229,9 @@ class PipelineEngine:
         self.grad_divisor = float(grad_divisor)
         # a mixture-of-experts block feeds its load-balancing gradient into its router's backward itself: it is
         # scaled like the loss's own backward (_loss_seed)
-        for mod in mods:
-            for sub in mod.modules():
-                if isinstance(sub, MoEFeedForwardBlock):
-                    sub.aux_scale = 1.0 / (self.chunks * self.grad_divisor)
+        self._moe_blocks = [sub for mod in mods for sub in mod.modules() if isinstance(sub, MoEFeedForwardBlock)]
+        for sub in self._moe_blocks:
+            sub.aux_scale = 1.0 / (self.chunks * self.grad_divisor)
         self._seeds: Dict[tuple, Tensor] = {}
         if schedule == "1f1b" and self.virtual > 1:
             raise ValueError("1f1b supports one chunk per rank")
@@ -436,7 +436,11 @@ class PipelineEngine:
         rank and micro-batch (``tools/engine_timeline.py``).
         """
         with label_range("engine step"):
-            return self._step(inputs, targets, doc_bounds)
+            stats = self._step(inputs, targets, doc_bounds)
+            # a sigmoid router's selection bias moves against the load this step counted (a no-op for every other)
+            for sub in self._moe_blocks:
+                sub.update_router_bias()
+            return stats
 
     def _step(self, inputs: Optional[Sequence[Tensor]] = None, targets: Optional[Sequence[Tensor]] = None,
               docs: Optional[Sequence[Tensor]] = None) -> StepStats:

@@ -102,7 +102,8 @@ def moe_cost(cfg: LMConfig, tokens: Optional[int] = None) -> float:
     micro-batch (default: 8 sequences, as :func:`boundary_terms`) -- and the traffic of the norm, the dispatch and
     the combine (``k`` rows gathered per token each way, forward and backward).  A grouped config
     (``cfg.expert_gemm == "grouped"``) runs ``k + 64 Ne / T`` rows per token: the true rows plus half a 128-row tile
-    of padding per expert."""
+    of padding per expert.  ``cfg.n_shared_experts`` adds a dense gated MLP of that many expert widths on every
+    token: its two GEMMs and its gate pass."""
     from ..ops.moe import moe_capacity
 
     e, f, ne, k = cfg.d_model, cfg.dim_feedforward, cfg.n_experts, cfg.experts_per_token
@@ -114,6 +115,8 @@ def moe_cost(cfg: LMConfig, tokens: Optional[int] = None) -> float:
     router = 3.0 * (2 * e * ne) + 3.0 * 10 * ne
     experts = rows * (3.0 * (2 * e * 2 * f) + 3.0 * 10 * f + 3.0 * (2 * e * f))
     passes = 3.0 * 10 * e + 3.0 * 5 * e * (rows + k)
+    if cfg.n_shared_experts:
+        experts += cfg.n_shared_experts * (3.0 * (2 * e * 2 * f) + 3.0 * 10 * f + 3.0 * (2 * e * f))
     return router + experts + passes
 
 
